@@ -20,6 +20,13 @@ Multi-GPU: one process per GPU, each an independent replica with its own stream(
 only the barrier and the max/sum over ranks.  Under torch.distributed.run the ranks come
 from the environment (WORLD_SIZE must equal --gpus); `python bench.py --gpus N` without it
 starts the N rank processes itself (before anything touches a GPU) and relays rank 0's line.
+A plain run sets up, warms up, times --steps transcriptions and prints the line.  `--full` adds
+what the headline figure does not need, after the timed region: the CPU baseline
+(`cpu_baseline`, the oracle on this host) and the encoder's two-plane timing
+(`encoder_rtf_2plane`).  `--dump-outputs DIR` writes what the last timed step computed (token
+ids, adapter rows) as DIR/<name>.npy; inputs and weights are seeded, so the files of two builds
+run with the same arguments compare one to one.
+
 `--dry-run` runs the same harness with a host-only placeholder step (no GPU, no model): it
 exists so the CPU tests can exercise the launcher and the over-ranks reduction.
 """
@@ -48,8 +55,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed transcriptions")
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=8, help="oracle decode steps in the CPU sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need, after the timed steps: the CPU baseline "
+                         "(cpu_baseline) and the encoder's two-plane timing (encoder_rtf_2plane)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): the token ids and the adapter rows of the transcription lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--cpu-steps", type=int, default=8,
+                    help="with --full: oracle decode steps in the CPU sample")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--streams", type=int, default=1,
                     help="config 4: streams per GPU decoded together (batched weight reads)")
@@ -193,6 +207,17 @@ def emit(d, out):
         out["rank_host"] = d.host
     if d.rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(d, path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (token ids are below 2^24,
+    so exact); ranks above 0 write <name>.rank<r>.npy.  The inputs are seeded, so two builds
+    run with the same arguments can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if d.rank:
+            name = f"{name}.rank{d.rank}"
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def parse_cpulist(text):
@@ -407,6 +432,11 @@ def encoder_flops(cfg, mel_chunks):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.long_context > 0 or args.stagger or args.streaming or args.clip_seconds > 0):
+        raise SystemExit("bench.py: --dump-outputs covers the jfk-shaped transcription lines "
+                         "(the default, --q8, --kv-fp16, --streams)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     d = Dist(args.gpus)
@@ -427,7 +457,7 @@ def main():
     d.host = {"cpu_affinity": affinity, "host_weights": w_how}
     if args.kv_fp16:
         model.set_kv_fp16(True)  # before any stream exists
-    keep_host = d.rank == 0 and d.world == 1 and not args.no_cpu_baseline
+    keep_host = args.full and d.rank == 0 and d.world == 1 and not args.no_cpu_baseline
     if not keep_host:
         del w
         w = None
@@ -467,10 +497,13 @@ def main():
     d.barrier()
     prof = st.profile()
     st.set_profiling(False)
+    if args.dump_outputs:
+        # what the last timed transcription returned, and the adapter rows its decoder read
+        dump_outputs(d, args.dump_outputs, {"tokens": runs[-1]["tokens"], "adapter": st.read_adapter()})
     # encoder_rtf is the exact figure (3 planes: f32-exact activations, the reference's sgemm
-    # precision); the approximate 2-plane split is timed after the timed region as an extra key
+    # precision); --full times the approximate 2-plane split after the timed region as an extra key
     enc_2plane = None
-    if gemm_planes() == 3:
+    if args.full and gemm_planes() == 3:
         vox_hip.set_gemm_planes(2)
         transcribe(st, mel_dev, cfg.mel_bins)
         d.barrier()
@@ -641,6 +674,8 @@ def dry_run(args, d):
         a = (a @ a) / np.float32(16.0)
     t1 = time.perf_counter()
     d.barrier()
+    if args.dump_outputs:
+        dump_outputs(d, args.dump_outputs, {"placeholder": a})
     wall = d.max(t1 - t0)
     steps_all = d.sum(args.steps * args.streams)
     out = {"metric": "bench.py harness dry run (no GPU; placeholder host step)", "value": round(steps_all / wall, 2),
@@ -997,6 +1032,13 @@ def bench_streams(args, d, cfg, model, st0, mel0, mel_dev0, rng):
         runs.append(transcribe_batch(batch, streams, mels, cfg.mel_bins))
     t1 = time.perf_counter()
     d.barrier()
+    if args.dump_outputs:
+        # every stream's ids of the last timed pass (one row each) and the first stream's adapter rows
+        toks = runs[-1]["tokens"]
+        ids = np.full((S, max(len(t) for t in toks)), -1.0, np.float32)
+        for i, t in enumerate(toks):
+            ids[i, :len(t)] = t
+        dump_outputs(d, args.dump_outputs, {"tokens": ids, "adapter": streams[0].read_adapter()})
     wall = d.max(t1 - t0)
     dec_s = d.max(sum(r["step_s"] for r in runs))
     steps_all = d.sum(sum(r["steps"] for r in runs))

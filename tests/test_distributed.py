@@ -66,6 +66,36 @@ def test_bench_launcher_dry_run_world2():
     assert o["value"] == pytest.approx(2 * 4 * 8 / (o["ms_per_step"] * 4 / 1000.0), rel=0.02)
 
 
+def test_bench_dump_outputs_and_steps_dry_run(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's arrays as float32 .npy files that are
+    identical from run to run (seeded inputs), `--steps` sets how many steps ran (the
+    placeholder's result depends on it), the line carries ms_per_step, and `--full` is
+    accepted."""
+    import json
+
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+
+    def run(out, steps, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "1", "--dry-run", "--dump-outputs", str(out), *extra],
+                           capture_output=True, text=True, timeout=120, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        assert lines[0]["steps"] == steps and lines[0]["ms_per_step"] > 0
+        assert [f.name for f in out.iterdir()] == ["placeholder.npy"]
+        a = np.load(out / "placeholder.npy")
+        assert a.dtype == np.float32 and a.nbytes <= 64 << 20 and np.isfinite(a).all()
+        return a
+
+    a3 = run(tmp_path / "a", 3)
+    assert np.array_equal(a3, run(tmp_path / "b", 3, "--full"))
+    assert not np.array_equal(a3, run(tmp_path / "c", 2))
+
+
 def test_bench_launcher_fails_fast_when_a_rank_dies():
     """A rank that exits with an error takes the job down at once: the launcher polls its
     children and stops the sibling waiting in the barrier (instead of leaving it there until
