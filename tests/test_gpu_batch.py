@@ -367,7 +367,9 @@ def test_batch_32_streams_two_row_blocks(models, tiny_cfg):
     prefills all of them in stacked passes (32 prompts of 39 rows exceed one 1024-row pass, so
     the prompts go in groups) and takes their first token in the batched steps; every stream's
     ids equal its own oracle session, and streams in the second row block (rows 16-31) keep
-    the logit bar step by step."""
+    the logit bar step by step.  At TINY's 2 kv heads 32 slots give 64 (slot, kv head) blocks,
+    below the 256 the 1024-thread attention grid needs, so this test runs the 128-key split
+    grid; the 32-slot default grid (8 kv heads) is pinned by tests/test_gpu_batch_kv8.py."""
     import vox_hip
     import vox_oracle
     hm, om = models
