@@ -105,6 +105,24 @@ int vox_hip_model_ada_scale(vox_hip_model_t *m, float *out);
  * default f32 ring is the CPU reference's (voxtral_decoder.c:232-234).  head_dim 128 only
  * (Voxtral's); returns 0, or -1 (vox_hip_last_error) for another head_dim. */
 int vox_hip_model_set_kv_fp16(vox_hip_model_t *m, int on);
+/* wpack13 (no reference counterpart): at creation every bf16 matrix of the single-stream
+ * decode step (Q|K|V, wo, W1|W3, W2 per decoder layer, and the LM head) whose nonzero
+ * exponents span at most 30 binades also gets a 13-bit-per-weight copy that the M = 1 GEMV
+ * streams instead (0.8125 of the bytes, decoded without loss: same bits out).  The others,
+ * and every tensor when VOX_HIP_WPACK=0 is set at creation or the model is Q8, stay raw. */
+typedef struct {
+    int packed_tensors;         /* tensors the decode GEMV streams from wpack13 planes */
+    int raw_tensors;            /* bf16 tensors of the same set that stayed raw */
+    long long packed_bytes;     /* bytes of the planes (main + side) */
+    long long packed_raw_bytes; /* bf16 bytes of the packed tensors (the raw copies kept) */
+    long long raw_bytes;        /* bf16 bytes of the tensors that stayed raw */
+    double pack_ms;             /* host time spent scanning, packing and uploading the planes */
+} vox_hip_wpack_stats_t;
+int vox_hip_model_wpack_stats(const vox_hip_model_t *m, vox_hip_wpack_stats_t *out);
+/* Test entry: y[rows] = W x for one bf16 matrix W [rows, K] (host pointers) through the
+ * M = 1 GEMV, from wpack13 planes (packed = 1) or from the raw rows.  Returns 1 when the
+ * packed kernel ran, 0 when the raw one did (packed = 0 or W outside the window), -1 on error. */
+int vox_hip_gemv_wpack(int rows, int K, const uint16_t *W, const float *x, float *y, int packed);
 /* Arithmetic of the M > 1 GEMMs (encoder, adapter, prefill; no reference counterpart: the
  * CPU path's cblas_sgemm, voxtral_kernels.c:197-240, is f32): every f32 activation is split
  * into bf16 planes that multiply the exact bf16 weights on MFMA.  planes = 3 (hi + mid + lo,

@@ -3,6 +3,7 @@
 // launches on one stream).  Build: make -C tools; run: tools/kbench [iters]
 // Shapes: Voxtral-4B decoder (voxtral.h:37-48).
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,6 +11,7 @@
 
 #include "../voxtral.c_amd/csrc/vox_hip_internal.h"
 #include "../voxtral.c_amd/csrc/vox_hip_dev.h"
+#include "../voxtral.c_amd/csrc/vox_wpack.h"
 
 using namespace vox;
 namespace vox { extern int g_skf_r, g_skf_nw, g_skf_d, g_skl_nw, g_gemv_rb, g_attn_lw, g_attn_blocks, g_attn_short, g_gemmf_rb, g_gemmf_minu, g_gemmf_wr, g_gemmf_order, g_mel_fpb, g_skf2_r, g_attn_kvfast, g_attn_bsplit, g_gemv_maxb; }
@@ -311,6 +313,96 @@ int main(int argc, char** argv) {
                 fflush(stdout);
             }
         g_mel_fpb = 0;
+        return 0;
+    }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "wpack")) {
+        // wpack13 planes (vox_wpack.h, 13 bits per weight) against the raw bf16 rows: the five
+        // decode GEMV shapes, cold weights (a buffer per layer), raw and packed alternating in
+        // one run so that the spread between repeats of one format is on the same page.
+        // First, per shape, a seeded random matrix is packed on the host and the two kernels'
+        // outputs are compared bit for bit (the LM head at 65536 rows).
+        // VOX_KB_WPACK_SHAPES=w13 (or any list of qkv,wo,w13,w2,lm) limits the shapes.
+        struct S { const char* n; int pro, epi, K, rows, crows; std::vector<uint16_t*>* w; };
+        const char* only = getenv("VOX_KB_WPACK_SHAPES");
+        CK(hipMemset(state, 0, 16));
+        std::vector<uint16_t*> lm1(1, emb);
+        for (S o : {S{"w13", PRO_NORM_ADA, EPI_SWIGLU, D, 2 * DH, 2 * DH, &w13}, S{"w2", PRO_NONE, EPI_RESID, DH, D, D, &w2},
+                    S{"qkv", PRO_NORM, EPI_QKV, D, DQ + 2 * DKV, DQ + 2 * DKV, &wqkv}, S{"wo", PRO_NONE, EPI_RESID, DQ, D, D, &wo},
+                    S{"lm", PRO_NORM, EPI_LOGITS, D, V, 65536, &lm1}}) {
+            if (only && !strstr(only, o.n)) continue;
+            const int rb = gemv_rowgroup(o.rows), sw = vox_wpack13_side_words(o.K, rb), swiglu = o.epi == EPI_SWIGLU;
+            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sideb = (size_t)o.rows / rb * 256 * sw * 4;
+            auto run = [&](const uint16_t* W, const void* pm, const void* ps, int d, int rows, float* out) {
+                GemvArgs a;
+                memset(&a, 0, sizeof a);
+                a.x = x; a.K = o.K; a.W = W; a.wp_main = pm; a.wp_side = ps; a.wp_d = d; a.rows = rows; a.norm_w = normw;
+                a.ada = ada; a.eps = 1e-5f; a.y = out; a.qd = DQ; a.kvd = DKV; a.hd = HD; a.rope = rope; a.state = state;
+                a.Kc = Kc; a.Vc = Vc; a.cap = cap; a.part_val = pv; a.part_idx = pi;
+                CK(launch_gemv(o.pro, o.epi, a, st));
+            };
+            int d = 0;
+            {   // bit check on seeded random weights (uniform, std 1/sqrt(3072)) and a random x
+                const int rows = o.crows;
+                if (gemv_rowgroup(rows) != rb) { printf("%s: check rows use another row group\n", o.n); return 1; }
+                std::vector<uint16_t> hw((size_t)rows * o.K);
+                uint64_t z = 0x9E3779B97F4A7C15ull ^ (uint64_t)o.K * 131 ^ (uint64_t)o.rows;
+                auto rnd = [&] { z = z * 6364136223846793005ull + 1442695040888963407ull; return (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f; };
+                for (auto& v : hw) {
+                    const float f = 0.03125f * rnd();
+                    uint32_t u;
+                    memcpy(&u, &f, 4);
+                    v = (uint16_t)(u >> 16);
+                }
+                std::vector<float> hx(DH);
+                for (auto& v : hx) v = rnd();
+                CK(hipMemcpy(x, hx.data(), DH * 4, hipMemcpyHostToDevice));
+                int emin, emax;
+                if (!vox_wpack13_scan_(hw.data(), hw.size(), &emin, &emax, &d)) { printf("%s: not packable\n", o.n); return 1; }
+                std::vector<uint32_t> hm((size_t)rows * o.K / 8 * 3), hs((size_t)rows / rb * 256 * sw);
+                std::vector<uint8_t> hb((size_t)rows * o.K / 8);
+                vox_wpack13_pack_(hw.data(), rows, o.K, d, hm.data(), hb.data());
+                vox_wpack13_side_layout_(hb.data(), rows, o.K, rb, swiglu, hs.data());
+                uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
+                uint32_t* dm = (uint32_t*)dmalloc(hm.size() * 4, 0);
+                uint32_t* ds = (uint32_t*)dmalloc(hs.size() * 4, 0);
+                CK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+                CK(hipMemcpy(dm, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+                CK(hipMemcpy(ds, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+                const int ny = swiglu ? rows / 2 : rows;
+                float* y2 = (float*)dmalloc((size_t)V * 4, 0);
+                std::vector<float> y0(ny), y1(ny);
+                CK(hipMemset(y, 0, (size_t)ny * 4));
+                run(dw, nullptr, nullptr, 0, rows, y);
+                run(dw, dm, ds, d, rows, y2);
+                CK(hipStreamSynchronize(st));
+                CK(hipMemcpy(y0.data(), y, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                CK(hipMemcpy(y1.data(), y2, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                double sum = 0;
+                for (float v : y0) sum += fabs((double)v);
+                printf("wpack %-4s check: exponents %d..%d D %d, %d outputs, mean |y| %.4g: %s\n", o.n, emin, emax, d, ny,
+                       sum / ny, memcmp(y0.data(), y1.data(), (size_t)ny * 4) ? "BITS DIFFER" : "same bits");
+                fflush(stdout);
+                CK(hipFree(dw)); CK(hipFree(dm)); CK(hipFree(ds)); CK(hipFree(y2));
+                CK(hipMemsetD32(x, 0x3c003c01u, DH));
+            }
+            // timing: constant planes (values do not matter), one pair of planes per layer
+            const int nl = (int)o.w->size();
+            std::vector<void*> pm(nl), ps(nl);
+            for (int l = 0; l < nl; l++) {
+                pm[l] = dmalloc(mainb, 1);
+                ps[l] = dmalloc(sideb, 0);
+            }
+            const int it = nl == 1 ? iters / 10 + 1 : iters;
+            for (int r = 0; r < 5; r++) {
+                char nm[96];
+                snprintf(nm, sizeof nm, "wpack %-4s raw    run %d", o.n, r);
+                add(nm, timeit([&] { run((*o.w)[layer++ % nl], nullptr, nullptr, 0, o.rows, y); }, it, st), (double)o.rows * o.K * 2);
+                snprintf(nm, sizeof nm, "wpack %-4s packed run %d", o.n, r);
+                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], pm[l], ps[l], d, o.rows, y); }, it, st),
+                    (double)mainb + sideb);
+            }
+            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); }
+        }
         return 0;
     }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gpe")) {

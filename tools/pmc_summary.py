@@ -14,6 +14,7 @@ import os
 import sys
 
 W13 = "k_gemv<2, 4, 4, 2, 0>"   # PRO_NORM_ADA, EPI_SWIGLU, RB 4, KQ 2, bf16
+W13_P13 = "k_gemv<2, 4, 4, 2, 2>"  # the same from wpack13 planes (the default for bf16 models)
 W13_Q8 = "k_gemv<2, 4, 4, 1, 1>"  # the same, Q8 rows (int8 + f32 row scales)
 ALGO = {  # algorithmic bytes per launch (weights + activation vectors), DESIGN.md section 5
     "k_gemv<2, 4, 4, 2, 0>": 2 * 9216 * 3072 * 2 + 3072 * 4 * 3 + 9216 * 4,
@@ -21,6 +22,13 @@ ALGO = {  # algorithmic bytes per launch (weights + activation vectors), DESIGN.
     "k_gemv<1, 5, 4, 2, 0>": 6144 * 3072 * 2 + 3072 * 8 + 6144 * 4,
     "k_gemv<0, 1, 2, 2, 0>": 3072 * 4096 * 2 + 4096 * 4 + 3072 * 8,
     "k_gemv<1, 6, 8, 2, 0>": 131072 * 3072 * 2 + 3072 * 8 + 131072 * 4,
+    # wpack13 planes (csrc/vox_wpack.h): 12 B per 8 weights, and a side record of
+    # ceil(KQ * RB / 4) dwords per thread of each row group
+    "k_gemv<2, 4, 4, 2, 2>": 2 * 9216 * 3072 * 3 // 2 + 2 * 9216 // 4 * 256 * 8 + 3072 * 4 * 3 + 9216 * 4,
+    "k_gemv<0, 1, 2, 5, 2>": 3072 * 9216 * 3 // 2 + 3072 // 2 * 256 * 12 + 9216 * 4 + 3072 * 8,
+    "k_gemv<1, 5, 4, 2, 2>": 6144 * 3072 * 3 // 2 + 6144 // 4 * 256 * 8 + 3072 * 8 + 6144 * 4,
+    "k_gemv<0, 1, 2, 2, 2>": 3072 * 4096 * 3 // 2 + 3072 // 2 * 256 * 4 + 4096 * 4 + 3072 * 8,
+    "k_gemv<1, 6, 8, 2, 2>": 131072 * 3072 * 3 // 2 + 131072 // 8 * 256 * 16 + 3072 * 8 + 131072 * 4,
     # Q8 (config 5): int8 rows + f32 row scales
     "k_gemv<2, 4, 4, 1, 1>": 2 * 9216 * 3072 + 2 * 9216 * 4 + 3072 * 4 * 3 + 9216 * 4,
     "k_gemv<0, 1, 2, 3, 1>": 3072 * 9216 + 3072 * 4 + 9216 * 4 + 3072 * 8,
@@ -59,7 +67,7 @@ def main():
                     "algorithmic_bytes": ALGO.get(k), "ratio": round((rd + wr) / ALGO[k], 4) if k in ALGO else None}
         print(f"{k:40s} n={n[k]:6d} read {rd / 1e6:9.2f} MB write {wr / 1e6:7.3f} MB"
               + (f"  algo {ALGO[k] / 1e6:8.2f} MB  ratio {table[k]['ratio']}" if k in ALGO else ""))
-    key = W13 if W13 in table else W13_Q8
+    key = W13_P13 if W13_P13 in table else W13 if W13 in table else W13_Q8
     w = table[key]
     res = {"kernel": key + " (W1|W3: RMSNorm*(1+ada) -> GEMV -> SiLU*up)",
            "hbm_bytes_per_launch": w["read_bytes"] + w["write_bytes"],

@@ -7,6 +7,7 @@
 // of greedy steps never returns to the host (DESIGN.md "Decoder step").
 #include "../../include/voxtral_hip.h"
 #include "vox_hip_internal.h"
+#include "vox_wpack.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -18,8 +19,10 @@
 #include <stddef.h>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -141,10 +144,17 @@ struct EncLayerD {
     float *sqkv, *so, *s13, *s2;
     float *bqkv, *bo, *b2, *attn_norm, *ffn_norm;
 };
+// wpack13 copy of a bf16 matrix for the single-stream GEMV (vox_wpack.h): 13 bits per
+// weight, decoded without loss.  main == null: the tensor stays raw.
+struct WPackD {
+    uint8_t *main, *side;
+    int d;
+};
 struct DecLayerD {
     uint8_t *wqkv, *wo, *w13, *w2;
     float *sqkv, *so, *s13, *s2;
     float *attn_norm, *ffn_norm;
+    WPackD pqkv, po, p13, p2;
 };
 // the same matrices in MFMA fragment order for the batched step (k_skf; built on first use)
 struct DecFragD {
@@ -173,6 +183,9 @@ struct vox_hip_model {
     std::vector<DecFragD> efrag;   // fragment-major encoder matrices (empty until a short chunk)
     uint8_t* lm_frag;              // fragment-major LM head (tied embeddings)
     int kv16;                      // decoder KV rings of streams created from now on in IEEE half
+    WPackD plm;                    // wpack13 copy of the LM head
+    int wpack;                     // VOX_HIP_WPACK (default 1), read once at creation
+    vox_hip_wpack_stats_t wstats;
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -246,6 +259,59 @@ static int upload_w13(uint8_t** dst, float** dscale, const void* w1, const float
         CK(hipMemcpy2D((char*)*dscale + g4, 2 * g4, s3, g4, g4, hidden / 16, hipMemcpyHostToDevice));
     }
     return 0;
+}
+
+// f(lo, hi) over [0, n) on up to 16 host threads
+template <class F>
+static void par_range(long long n, F f) {
+    const long long nt = std::max(1LL, std::min<long long>({16, (long long)std::thread::hardware_concurrency(), n}));
+    std::vector<std::thread> th;
+    for (long long t = 1; t < nt; t++) th.emplace_back([=] { f(n * t / nt, n * (t + 1) / nt); });
+    f(0, n / nt);
+    for (auto& t : th) t.join();
+}
+
+// The wpack13 planes of a bf16 matrix whose rows are in device order (host copy), for
+// k_gemv's row groups of this shape.  A tensor outside the format's window (vox_wpack.h),
+// or of a shape launch_gemv does not take, stays raw: P->main stays null.
+static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const uint16_t* w, int rows, int K, int swiglu) {
+    P->main = P->side = nullptr;
+    P->d = 0;
+    const size_t n = (size_t)rows * K;
+    auto raw = [&] { S.raw_tensors++; S.raw_bytes += (long long)n * 2; return 0; };
+    if (!w) return set_err("null weight pointer");
+    if (!enabled || !gemv_ok(rows, K, 0)) return raw();
+    const auto t0 = std::chrono::steady_clock::now();
+    int lo = 256, hi = -1, bad = 0;
+    std::mutex mu;
+    par_range(rows, [&](long long r0, long long r1) {
+        int l = 256, h = -1, b = 0;
+        vox_wpack13_scan_range(w + r0 * K, (size_t)(r1 - r0) * K, &l, &h, &b);
+        std::lock_guard<std::mutex> g(mu);
+        lo = std::min(lo, l); hi = std::max(hi, h); bad |= b;
+    });
+    int d;
+    if (!vox_wpack13_choose(lo, hi, bad, &d)) return raw();
+    const int rb = gemv_rowgroup(rows), sw = vox_wpack13_side_words(K, rb);
+    const size_t mainw = n / 8 * 3, sidew = (size_t)rows / rb * 256 * sw;
+    std::vector<uint32_t> hm(mainw), hs(sidew);
+    std::vector<uint8_t> hb(n / 8);
+    par_range(rows, [&](long long r0, long long r1) { vox_wpack13_pack_rows(w, r0, r1, K, d, hm.data(), hb.data()); });
+    par_range(rows / rb, [&](long long g0, long long g1) { vox_wpack13_side_groups(hb.data(), g0, g1, K, rb, swiglu, hs.data()); });
+    CK(dalloc(&P->main, mainw * 4));
+    CK(dalloc(&P->side, sidew * 4));
+    if (upload(P->main, hm.data(), mainw * 4) || upload(P->side, hs.data(), sidew * 4)) return -1;
+    P->d = d;
+    S.packed_tensors++;
+    S.packed_bytes += (long long)(mainw + sidew) * 4;
+    S.packed_raw_bytes += (long long)n * 2;
+    S.pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+static void wpack_args(GemvArgs& a, const WPackD& P) {
+    a.wp_main = P.main;
+    a.wp_side = P.side;
+    a.wp_d = P.d;
 }
 
 static int model_update_ada(vox_hip_model_t* m) {
@@ -336,6 +402,13 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     m->ad0_s = m->ad1_s = m->tok_emb_s = nullptr;
     m->conv0_b = m->conv1_b = m->enc_norm = m->dec_norm = m->ada_scale = nullptr;
     m->rope_enc = m->rope_dec = nullptr;
+    memset(&m->plm, 0, sizeof m->plm);
+    memset(&m->wstats, 0, sizeof m->wstats);
+    {
+        // VOX_HIP_WPACK=0: every GEMV weight stays raw bf16 (same-machine A/B runs)
+        const char* e = getenv("VOX_HIP_WPACK");
+        m->wpack = (e && atoi(e) == 0) ? 0 : 1;
+    }
     const vox_hip_config_t& c = *cfg;
     const int ED = c.enc_dim, EQ = c.enc_heads * c.enc_head_dim, EKV = c.enc_kv_heads * c.enc_head_dim;
     const int EH = c.enc_hidden;
@@ -383,6 +456,10 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     TRY(upload_mat(&m->ad1, &m->ad1_s, w->ad1, w->ad1_s, DD, DD));
     // decoder
     TRY(upload_mat(&m->tok_emb, &m->tok_emb_s, w->tok_emb, w->tok_emb_s, c.vocab, DD));
+    // wpack13 copies of the bf16 matrices the single-stream decode step streams (made here,
+    // not in the first step); the raw copies stay for every other path
+    if (!w->tok_emb_s) TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)w->tok_emb, c.vocab, DD, 0));
+    std::vector<uint16_t> hrows;  // a matrix in device row order (merged Q|K|V, interleaved W1|W3)
     m->dec.resize(c.dec_layers);
     m->ada_down.resize(c.dec_layers);
     m->ada_up.resize(c.dec_layers);
@@ -394,6 +471,24 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         TRY(upload_mat(&L.wo, &L.so, w->dec_wo[l], SCL(dec_wo_s, l), DD, DQ));
         TRY(upload_w13(&L.w13, &L.s13, w->dec_w1[l], SCL(dec_w1_s, l), w->dec_w3[l], SCL(dec_w3_s, l), DH, DD));
         TRY(upload_mat(&L.w2, &L.s2, w->dec_w2[l], SCL(dec_w2_s, l), DD, DH));
+        if (!L.sqkv) {
+            hrows.resize((size_t)(DQ + 2 * DKV) * DD);
+            memcpy(hrows.data(), w->dec_wq[l], (size_t)DQ * DD * 2);
+            memcpy(hrows.data() + (size_t)DQ * DD, w->dec_wk[l], (size_t)DKV * DD * 2);
+            memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, w->dec_wv[l], (size_t)DKV * DD * 2);
+            TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
+        }
+        if (!L.so) TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)w->dec_wo[l], DD, DQ, 0));
+        if (!L.s13) {
+            hrows.resize((size_t)2 * DH * DD);
+            const size_t grp = (size_t)16 * DD;
+            for (int g = 0; g < DH / 16; g++) {
+                memcpy(hrows.data() + 2 * g * grp, (const uint16_t*)w->dec_w1[l] + g * grp, grp * 2);
+                memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)w->dec_w3[l] + g * grp, grp * 2);
+            }
+            TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1));
+        }
+        if (!L.s2) TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)w->dec_w2[l], DD, DH, 0));
         TRYH(dalloc(&L.attn_norm, DD));
         TRY(upload(L.attn_norm, w->dec_attn_norm[l], DD * 4));
         TRYH(dalloc(&L.ffn_norm, DD));
@@ -425,7 +520,9 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
         dfree(L.wqkv); dfree(L.wo); dfree(L.w13); dfree(L.w2);
         dfree(L.sqkv); dfree(L.so); dfree(L.s13); dfree(L.s2);
         dfree(L.attn_norm); dfree(L.ffn_norm);
+        for (WPackD* P : {&L.pqkv, &L.po, &L.p13, &L.p2}) { dfree(P->main); dfree(P->side); }
     }
+    dfree(m->plm.main); dfree(m->plm.side);
     for (auto& F : m->dfrag) {
         dfree(F.wqkv); dfree(F.wo); dfree(F.w13); dfree(F.w2);
     }
@@ -437,6 +534,12 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
     dfree(m->ad0_s); dfree(m->ad1_s); dfree(m->tok_emb_s);
     dfree(m->ada_scale); dfree(m->rope_enc); dfree(m->rope_dec);
     delete m;
+}
+
+extern "C" int vox_hip_model_wpack_stats(const vox_hip_model_t* m, vox_hip_wpack_stats_t* out) {
+    if (!m || !out) return set_err("wpack_stats: null argument");
+    *out = m->wstats;
+    return 0;
 }
 
 extern "C" int vox_hip_model_set_delay(vox_hip_model_t* m, int delay_tokens) {
@@ -1928,6 +2031,7 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         a.state = state; a.pos = pos;
         a.rope = state ? m->rope_dec : rope_row - (size_t)pos * hd;
         a.Kc = Kc; a.Vc = Vc; a.cap = s->dcap; a.kv16 = s->kv16;
+        wpack_args(a, L.pqkv);
         CK(launch_gemv(PRO_NORM, EPI_QKV, a, st));
         // attention over the last min(pos+1, window) keys (decoder.c:724-733)
         CK(launch_attn_decode(hd, s->qd_, Kc, Vc, s->dcap, state, pos, c.dec_window, scale, H, KVH,
@@ -1935,11 +2039,13 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         // wo + residual (decoder.c:735-740)
         memset(&a, 0, sizeof a);
         a.x = s->attd; a.K = DQ; a.W = L.wo; a.wscale = L.so; a.rows = DD; a.y = s->xd;
+        wpack_args(a, L.po);
         CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up (decoder.c:742-758)
         memset(&a, 0, sizeof a);
         a.x = s->xd; a.K = DD; a.W = L.w13; a.wscale = L.s13; a.rows = 2 * DH; a.norm_w = L.ffn_norm;
         a.ada = m->ada_scale + (size_t)l * DD; a.eps = c.dec_eps; a.y = s->gated;
+        wpack_args(a, L.p13);
         // profiling: HIP events recorded by the W1|W3 launch's own dispatch (eager steps)
         const bool gprof = s->profiling && state && !s->capturing && (int)s->pev.size() == 2 * c.dec_layers;
         if (gprof) CK(launch_gemv_timed(PRO_NORM_ADA, EPI_SWIGLU, a, s->pev[2 * l], s->pev[2 * l + 1], st));
@@ -1947,6 +2053,7 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         // W2 + residual (decoder.c:758-760)
         memset(&a, 0, sizeof a);
         a.x = s->gated; a.K = DH; a.W = L.w2; a.wscale = L.s2; a.rows = DD; a.y = s->xd;
+        wpack_args(a, L.p2);
         CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
     }
     return enqueue_lm_head(s, state);
@@ -1962,6 +2069,7 @@ static int enqueue_lm_head(vox_hip_stream_t* s, const int* state) {
     a.x = s->xd; a.K = c.dec_dim; a.W = m->tok_emb; a.wscale = m->tok_emb_s; a.rows = c.vocab; a.norm_w = m->dec_norm;
     a.eps = c.dec_eps; a.y = s->logits; a.part_val = s->pval; a.part_idx = s->pidx;
     a.part_alt = s->part_alt;
+    wpack_args(a, m->plm);
     CK(launch_gemv(PRO_NORM, (state && s->n_alt > 1) ? EPI_LOGITS_ALT : EPI_LOGITS, a, st));
     return 0;
 }
@@ -2376,6 +2484,40 @@ static int twin_sgemm(int M, int N, int K, const float* A, const void* B, const 
         return -1;
     CK(hipStreamSynchronize(g_twin_st));
     return 0;
+}
+
+// Test entry: y = W x for one bf16 matrix [rows, K] through k_gemv's STORE instance, from the
+// wpack13 planes (packed = 1) or from the raw rows.  Returns 1 when the packed instance ran,
+// 0 when the raw one did (packed = 0, or W outside the format's window), -1 on error.
+extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const float* x, float* y, int packed) {
+    std::lock_guard<std::mutex> lk(g_twin_mu);
+    if (!W || !x || !y) return set_err("gemv_wpack: null argument");
+    if (!gemv_ok(rows, K, 0)) return set_err("gemv_wpack: shape %d x %d is not a GEMV shape", rows, K);
+    if (twin_init()) return -1;
+    uint8_t* dW = nullptr;
+    float *dx = nullptr, *dy = nullptr;
+    WPackD P = {nullptr, nullptr, 0};
+    vox_hip_wpack_stats_t S;
+    memset(&S, 0, sizeof S);
+    auto run = [&]() -> int {
+        CK(dalloc(&dW, (size_t)rows * K * 2));
+        CK(dalloc(&dx, (size_t)K));
+        CK(dalloc(&dy, (size_t)rows));
+        if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)K * 4)) return -1;
+        if (wpack_make(packed, S, &P, W, rows, K, 0)) return -1;
+        GemvArgs a;
+        memset(&a, 0, sizeof a);
+        a.x = dx; a.K = K; a.W = dW; a.rows = rows; a.y = dy;
+        wpack_args(a, P);
+        CK(launch_gemv(PRO_NONE, EPI_STORE, a, g_twin_st));
+        CK(hipStreamSynchronize(g_twin_st));
+        CK(hipMemcpy(y, dy, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    const int was_packed = P.main != nullptr;
+    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side);
+    return rc ? -1 : was_packed;
 }
 
 extern "C" void vox_hip_sgemm_bf16(int M, int N, int K, const float* A, const uint16_t* B, float* C) {

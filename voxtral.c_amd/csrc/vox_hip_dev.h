@@ -163,6 +163,29 @@ __device__ __forceinline__ float dot8(uint4 w, float4 a, float4 b, float acc) {
     return acc;
 }
 
+// dot of 8 wpack13 weights (vox_wpack.h: three dwords of half pairs whose spare low bits,
+// with the chunk's two side nibbles, hold the fourth pair) with 8 f32 activations already
+// scaled by 2^D.  Same k order as dot8; the halves enter the f32 FMA as they are
+// (v_fma_mix_f32), and half * (x * 2^D) is the real number w * x, so every FMA rounds as
+// dot8's does.  sd: the side dword of this chunk's slot, q: the slot's index in it.
+__device__ __forceinline__ float hlo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float hhi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+__device__ __forceinline__ float dot8h(uint4 w, uint32_t sd, int q, float4 a, float4 b, float acc) {
+    const uint32_t HM = 0xfff8fff8u, SM = 0x00070007u;
+    const uint32_t t = (w.x & SM) | ((w.y & SM) << 3) | ((w.z & SM) << 6);
+    const uint32_t p3 = (t << 3) | ((sd << (4 * q)) & 0xf000f000u);
+    const uint32_t p0 = w.x & HM, p1 = w.y & HM, p2 = w.z & HM;
+    acc = fmaf(hlo(p0), a.x, acc);
+    acc = fmaf(hhi(p0), a.y, acc);
+    acc = fmaf(hlo(p1), a.z, acc);
+    acc = fmaf(hhi(p1), a.w, acc);
+    acc = fmaf(hlo(p2), b.x, acc);
+    acc = fmaf(hhi(p2), b.y, acc);
+    acc = fmaf(hlo(p3), b.z, acc);
+    acc = fmaf(hhi(p3), b.w, acc);
+    return acc;
+}
+
 // dot of 16 int8 weights (one uint4, Q8 rows) with 16 f32 activations: each byte is
 // sign-extended and converted exactly (q8_matvec_fused, voxtral_kernels.c:277-318)
 __device__ __forceinline__ float i8f(uint32_t w, int b) { return (float)((int32_t)(w << (24 - 8 * b)) >> 24); }

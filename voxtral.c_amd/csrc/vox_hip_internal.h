@@ -13,6 +13,8 @@ constexpr int ALT_TEXT_MIN = 1000;   // TOKEN_TEXT_MIN (voxtral.c:399)
 constexpr int ALT_PART = 10;         // per-block alt partial: m, s, 4 values, 4 ids
 constexpr int ALT_REC = 8;           // per-step alt record: p_best, (id, p) x 3, pad
 enum { PRO_NONE = 0, PRO_NORM = 1, PRO_NORM_ADA = 2 };
+// k_gemv weight formats: bf16 rows, Q8 rows + row scales, wpack13 planes (vox_wpack.h)
+enum { WF_BF16 = 0, WF_Q8 = 1, WF_P13 = 2 };
 
 constexpr int GEMV_MAX_BLOCKS = 1024;  // 4 blocks of 256 threads per CU on 256 CUs
 
@@ -21,6 +23,11 @@ struct GemvArgs {
     int K;
     const void* W;         // bf16 [rows, K], or int8 [rows, K] when wscale is set
     const float* wscale;   // Q8 per-row scales (null: bf16 weights)
+    // wpack13 copy of W (vox_wpack.h; null: stream W itself): main plane, the side plane
+    // laid out for this launch's row groups, and the tensor's exponent offset D
+    const void* wp_main = nullptr;
+    const void* wp_side = nullptr;
+    int wp_d = 0;
     int rows;              // output rows streamed (2*hidden for SWIGLU)
     const float* norm_w;   // PRO_NORM*: RMSNorm weight [K]
     const float* ada;      // PRO_NORM_ADA: ada_scale row [K]
@@ -94,6 +101,7 @@ struct AttnFuse {
 constexpr int ARGB = 64;                // argmax partial blocks per row
 
 int gemv_grid(int rows);
+int gemv_rowgroup(int rows);  // rows per k_gemv group (the wpack13 side plane is laid out for it)
 bool gemv_ok(int rows, int K, int q8);  // shapes launch_gemv accepts (rows, K multiple of the chunk)
 int attn_maxch(int window);      // decode-attention partials per head (64-key blocks)
 int attn_maxsplits(int window);  // 256-key spans of a window (graph buckets)

@@ -754,13 +754,19 @@ __device__ __forceinline__ void gemv_rows(int g, int (&rows)[RB]) {
 // 64-bit address per (row, round) -- the register count sets how many blocks stay resident.
 // Non-temporal (aux = 2: nt): every weight byte is read once per step.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-template <int RB, int KQ>
+typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
+template <int RB, int KQ, bool WP = false>
 __device__ __forceinline__ void gemv_load(__amdgpu_buffer_rsrc_t W, int rowbytes, const int (&rows)[RB],
                                           const int (&voff)[KQ], uint4 (&wv)[KQ][RB]) {
 #pragma unroll
     for (int j = 0; j < KQ; j++)
 #pragma unroll
         for (int i = 0; i < RB; i++) {
+            if constexpr (WP) {  // wpack13: 12-B chunks
+                const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(W, voff[j], rows[i] * rowbytes, 2);
+                wv[j][i] = make_uint4(v.x, v.y, v.z, 0u);
+                continue;
+            }
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(W, voff[j], rows[i] * rowbytes, 2);
             wv[j][i] = make_uint4(v.x, v.y, v.z, v.w);
         }
@@ -779,9 +785,42 @@ __device__ unsigned long long* g_gemv_stamps;
 #define GEMV_STAMP(k) do {} while (0)
 #endif
 
-template <int PRO, int EPI, int RB, int KQ, int WQ8>
+// wpack13 rows (WF_P13, vox_wpack.h): 12-B chunks of 8 weights as IEEE halves plus one side
+// dword record per (group, thread), fetched with the group's weights by one load; x is
+// scaled by 2^D once per block after the prologue.  ldexpf is exact for 0 and for |x| in
+// [2^(-126-D), 2^(127-D)); |D| <= 40 (VOX_WPACK_MAX_D) puts those bounds at 2^-86 and 2^87
+// or beyond, past anything an RMSNorm output, an attention output or a SwiGLU product of
+// this model reaches.  Every output is then bit-identical to the bf16 instance's.
+template <int SW>
+__device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int voff, int soff, uint32_t (&sd)[SW]) {
+    if constexpr (SW == 1) {
+        sd[0] = __builtin_amdgcn_raw_buffer_load_b32(S, voff, soff, 2);
+    } else if constexpr (SW == 2) {
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(S, voff, soff, 2);
+        sd[0] = v.x; sd[1] = v.y;
+    } else if constexpr (SW == 3) {
+        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(S, voff, soff, 2);
+        sd[0] = v.x; sd[1] = v.y; sd[2] = v.z;
+    } else {
+        static_assert(SW % 4 != 3, "side record size");
+#pragma unroll
+        for (int o = 0; o + 4 <= SW; o += 4) {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(S, voff + o * 4, soff, 2);
+            sd[o] = v.x; sd[o + 1] = v.y; sd[o + 2] = v.z; sd[o + 3] = v.w;
+        }
+        if constexpr (SW % 4 == 1) sd[SW - 1] = __builtin_amdgcn_raw_buffer_load_b32(S, voff + (SW - 1) * 4, soff, 2);
+        if constexpr (SW % 4 == 2) {
+            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(S, voff + (SW - 2) * 4, soff, 2);
+            sd[SW - 2] = v.x; sd[SW - 1] = v.y;
+        }
+    }
+}
+
+template <int PRO, int EPI, int RB, int KQ, int WF>
 __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
+    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13;
     constexpr int XPC = WQ8 ? 4 : 2;  // float4 of x per 16-B chunk
+    constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
     __shared__ float red[2][4][RB];
     __shared__ float sred[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -796,10 +835,14 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
     float wsc[RB];
     GEMV_STAMP(0);
     bool first_group = true;
-    const int rowbytes = K * (WQ8 ? 1 : 2);
-    const __amdgpu_buffer_rsrc_t wrs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, a.rows * rowbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, 0, 0x00020000);
+    const int rowbytes = WP ? KC * 12 : K * (WQ8 ? 1 : 2);
+    void* const wbase = const_cast<void*>(WP ? a.wp_main : a.W);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, a.rows * rowbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
+    void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
+    uint32_t sd[SW];
     // chunk offsets per K round; chunks past K (K not a multiple of 16 B * 256) re-load
     // chunk 0 and meet x = 0: every load is unconditional, so hipcc issues them all before
     // the first wait (a guarded load makes it wait vmcnt(0) at each branch join)
@@ -807,11 +850,12 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 #pragma unroll
     for (int j = 0; j < KQ; j++) {
         const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * 16;
+        voff[j] = (c0 < KC ? c0 : 0) * (WP ? 12 : 16);
     }
     // first group's weights are independent of x: issue them before the prologue
     gemv_rows<EPI, RB>(g, rows);
-    gemv_load<RB, KQ>(wrs, rowbytes, rows, voff, wv);
+    if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);  // first: every chunk needs it
+    gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
     if ((EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT) && WQ8 && wave == 0) {
 #pragma unroll
         for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
@@ -883,6 +927,18 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
         }
     }
 
+    if (WP) {
+#pragma unroll
+        for (int j = 0; j < KQ; j++)
+#pragma unroll
+            for (int h = 0; h < XPC; h++) {
+                float4 v = xr[j][h];
+                v.x = ldexpf(v.x, a.wp_d); v.y = ldexpf(v.y, a.wp_d);
+                v.z = ldexpf(v.z, a.wp_d); v.w = ldexpf(v.w, a.wp_d);
+                xr[j][h] = v;
+            }
+    }
+
     constexpr bool QKVE = (EPI == EPI_QKV || EPI == EPI_QKV_BIAS);
     int lp = 0;
     if (QKVE) lp = a.state ? a.state[0] : a.pos;
@@ -940,6 +996,7 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 #pragma unroll
             for (int i = 0; i < RB; i++) {
                 if (WQ8) acc[i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[j]), acc[i]);
+                else if (WP) acc[i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[j][0], xr[j][1], acc[i]);
                 else acc[i] = dot8(wv[j][i], xr[j][0], xr[j][XPC - 1], acc[i]);
             }
         if (first_group) {
@@ -963,7 +1020,8 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
         {
             const bool more = g < ngroups;
             gemv_rows<EPI, RB>(more ? g : 0, rows);
-            gemv_load<RB, KQ>(more ? wrs : wnone, rowbytes, rows, voff, wv);
+            if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
+            gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
             if (LOGIT && WQ8 && wave == 0) {
 #pragma unroll
                 for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
@@ -3266,6 +3324,8 @@ static int gemv_rb(int rows) {
     return 2;
 }
 
+int gemv_rowgroup(int rows) { return gemv_rb(rows); }
+
 VOX_KB_KNOB(g_gemv_maxb, 0);  // tools/kbench knob: grid cap other than GEMV_MAX_BLOCKS (no LM head)
 int gemv_grid(int rows) {
     // the largest divisor of the group count that fits 4 blocks per CU: every block then
@@ -3299,7 +3359,7 @@ int gemv_occupancy(const void* fn) {
 
 template <int P, int E, int RB, int Q8>
 static hipError_t gemv_k(const GemvArgs& a, int grid, hipStream_t st) {
-    const int kq = ((Q8 ? a.K >> 4 : a.K >> 3) + 255) / 256;
+    const int kq = ((Q8 == WF_Q8 ? a.K >> 4 : a.K >> 3) + 255) / 256;
     switch (kq) {
 #define KQ_CASE(Q) case Q: hipLaunchKernelGGL((k_gemv<P, E, RB, Q, Q8>), dim3(grid), dim3(256), 0, st, a); break;
         KQ_CASE(1) KQ_CASE(2) KQ_CASE(3) KQ_CASE(4) KQ_CASE(5)
@@ -3310,25 +3370,46 @@ static hipError_t gemv_k(const GemvArgs& a, int grid, hipStream_t st) {
     return hipSuccess;
 }
 
+// the wpack13 instances: the decoder step's GEMVs (and STORE for a single packed GEMV);
+// the encoder's single-row chunks stay bf16
+template <int P, int E>
+constexpr bool gemv_p13 = (P == PRO_NONE && (E == EPI_STORE || E == EPI_RESID)) || (P == PRO_NORM && E == EPI_QKV) ||
+                          (P == PRO_NORM_ADA && E == EPI_SWIGLU) ||
+                          (P == PRO_NORM && (E == EPI_LOGITS || E == EPI_LOGITS_ALT));
+
+template <int P, int E, int RB>
+static hipError_t gemv_q(const GemvArgs& a, int grid, hipStream_t st) {
+    if (a.wscale) return gemv_k<P, E, RB, WF_Q8>(a, grid, st);
+    if constexpr (gemv_p13<P, E>) {
+        if (a.wp_main) return gemv_k<P, E, RB, WF_P13>(a, grid, st);
+    } else if (a.wp_main) {
+        return hipErrorInvalidValue;
+    }
+    return gemv_k<P, E, RB, WF_BF16>(a, grid, st);
+}
+template <int P, int E, int RB>
+static const void* gemv_fn_q(const GemvArgs& a, int kq) {
+    if (a.wscale) return gemv_fn<P, E, RB, WF_Q8>(kq);
+    if constexpr (gemv_p13<P, E>) {
+        if (a.wp_main) return gemv_fn<P, E, RB, WF_P13>(kq);
+    } else if (a.wp_main) {
+        return nullptr;
+    }
+    return gemv_fn<P, E, RB, WF_BF16>(kq);
+}
+
 // kernel instance launch_gemv would use (tools, occupancy queries)
 const void* gemv_kernel(int pro, int epi, const GemvArgs& a) {
     const int rb = gemv_rb(a.rows);
     const int kq = ((a.wscale ? a.K >> 4 : a.K >> 3) + 255) / 256;
-#define GEMV_FN(P, E)                                                                     \
-    if (pro == P && epi == E)                                                             \
-        return rb == 8 ? (a.wscale ? gemv_fn<P, E, 8, 1>(kq) : gemv_fn<P, E, 8, 0>(kq))   \
-             : rb == 2 ? (a.wscale ? gemv_fn<P, E, 2, 1>(kq) : gemv_fn<P, E, 2, 0>(kq))   \
-                       : (a.wscale ? gemv_fn<P, E, 4, 1>(kq) : gemv_fn<P, E, 4, 0>(kq));
+#define GEMV_FN(P, E)         \
+    if (pro == P && epi == E) \
+        return rb == 8 ? gemv_fn_q<P, E, 8>(a, kq) : rb == 2 ? gemv_fn_q<P, E, 2>(a, kq) : gemv_fn_q<P, E, 4>(a, kq);
     GEMV_FN(PRO_NONE, EPI_STORE) GEMV_FN(PRO_NONE, EPI_RESID) GEMV_FN(PRO_NORM, EPI_QKV)
     GEMV_FN(PRO_NORM_ADA, EPI_SWIGLU) GEMV_FN(PRO_NORM, EPI_LOGITS) GEMV_FN(PRO_NORM, EPI_LOGITS_ALT)
     GEMV_FN(PRO_NORM, EPI_QKV_BIAS) GEMV_FN(PRO_NORM, EPI_SWIGLU)
 #undef GEMV_FN
     return nullptr;
-}
-
-template <int P, int E, int RB>
-static hipError_t gemv_q(const GemvArgs& a, int grid, hipStream_t st) {
-    return a.wscale ? gemv_k<P, E, RB, 1>(a, grid, st) : gemv_k<P, E, RB, 0>(a, grid, st);
 }
 
 // The same launch with HIP events recorded by the kernel's own dispatch packet

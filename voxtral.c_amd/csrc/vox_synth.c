@@ -12,6 +12,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "vox_wpack.h"
+
 static inline uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -96,4 +98,20 @@ void vox_dequant_q8(float *out, const int8_t *q, const float *scales, long long 
 #pragma omp parallel for schedule(static)
     for (long long r = 0; r < rows; r++)
         for (long long c = 0; c < cols; c++) out[r * cols + c] = (float)q[r * cols + c] * scales[r];
+}
+
+/* wpack13 (vox_wpack.h): the pure pack / unpack functions the engine's loader uses, exported
+ * for the CPU tests. */
+int vox_wpack13_scan(const uint16_t *w, size_t n, int *emin, int *emax, int *D) {
+    return vox_wpack13_scan_(w, n, emin, emax, D);
+}
+void vox_wpack13_pack(const uint16_t *w, long long rows, long long K, int D, uint32_t *main, uint8_t *side) {
+    vox_wpack13_pack_(w, rows, K, D, main, side);
+}
+void vox_wpack13_unpack(const uint32_t *main, const uint8_t *side, long long rows, long long K, int D, uint16_t *w) {
+    vox_wpack13_unpack_(main, side, rows, K, D, w);
+}
+int vox_wpack13_side_words_of(long long K, int rb) { return vox_wpack13_side_words(K, rb); }
+void vox_wpack13_side_layout(const uint8_t *side, long long rows, long long K, int rb, int swiglu, uint32_t *out) {
+    vox_wpack13_side_layout_(side, rows, K, rb, swiglu, out);
 }

@@ -32,12 +32,35 @@ OFFLINE_STREAMING_BUFFER_TOKENS = 10      # voxtral.c:401
 ConfigC = config_struct_class()
 WeightsC = weights_struct_class()
 
+class WPackStatsC(ctypes.Structure):
+    """vox_hip_wpack_stats_t"""
+    _fields_ = [("packed_tensors", ctypes.c_int), ("raw_tensors", ctypes.c_int),
+                ("packed_bytes", ctypes.c_longlong), ("packed_raw_bytes", ctypes.c_longlong),
+                ("raw_bytes", ctypes.c_longlong), ("pack_ms", ctypes.c_double)]
+
+
+def gemv_wpack(W_bf16, x, packed: bool):
+    """Test entry: (y, ran_packed) of y = W x for one bf16 matrix [rows, K] through the M = 1
+    GEMV, from wpack13 planes or from the raw rows"""
+    init()
+    W = np.ascontiguousarray(W_bf16, np.uint16)
+    xv = np.ascontiguousarray(x, np.float32)
+    rows, K = W.shape
+    assert xv.shape == (K,)
+    y = np.empty(rows, np.float32)
+    rc = lib().vox_hip_gemv_wpack(rows, K, W.ctypes.data, fptr(xv), fptr(y), int(packed))
+    if rc < 0:
+        _err("gemv_wpack")
+    return y, bool(rc)
+
+
 # exported symbols, as declared in include/voxtral_hip.h
 EXPORTS = [
     "vox_hip_init", "vox_hip_available", "vox_hip_shutdown", "vox_hip_memory_used",
     "vox_hip_last_error", "vox_hip_clear_error", "vox_hip_set_device", "vox_hip_config_voxtral_4b",
     "vox_hip_model_create", "vox_hip_model_free", "vox_hip_model_set_delay",
     "vox_hip_model_ada_scale", "vox_hip_model_set_kv_fp16", "vox_hip_stream_kv_fp16",
+    "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -77,6 +100,8 @@ def lib():
         "vox_hip_model_create": (P, [P, P, I]), "vox_hip_model_free": (None, [P]),
         "vox_hip_model_set_delay": (I, [P, I]), "vox_hip_model_ada_scale": (I, [P, fp]),
         "vox_hip_model_set_kv_fp16": (I, [P, I]), "vox_hip_stream_kv_fp16": (I, [P]),
+        "vox_hip_model_wpack_stats": (I, [P, P]),
+        "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -183,6 +208,14 @@ class Model:
         decoder K/V rings in IEEE half"""
         if lib().vox_hip_model_set_kv_fp16(self.h, int(on)) != 0:
             _err("set_kv_fp16")
+
+    def wpack_stats(self) -> dict:
+        """What the single-stream decode GEMV streams as wpack13 planes (13 bits per bf16
+        weight, lossless) and what stayed raw: tensor counts, bytes, host packing time"""
+        st = WPackStatsC()
+        if lib().vox_hip_model_wpack_stats(self.h, ctypes.byref(st)) != 0:
+            _err("wpack_stats")
+        return {name: getattr(st, name) for name, _ in WPackStatsC._fields_}
 
     def ada_scale(self):
         c = self.cfg
