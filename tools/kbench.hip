@@ -1285,7 +1285,7 @@ int main(int argc, char** argv) {
         CK(gemv_set_stamps(nullptr));
     }
 #endif
-    add("argmax+embed", timeit([&] { CK(launch_argmax_final(pv, pi, 1024, state, nullptr, 0, (float*)emb, 1024, emb, nullptr, D, x, nullptr, nullptr, st)); }, iters, st), 1.0);
+    add("argmax+embed", timeit([&] { CK(launch_argmax_final(pv, pi, 1024, state, nullptr, 0, (float*)emb, 1024, emb, nullptr, D, x, nullptr, nullptr, 131072, st)); }, iters, st), 1.0);
     add("empty-ish (embed step)", timeit([&] { CK(launch_embed_step((float*)emb, emb, nullptr, state, D, x, st)); }, iters, st), 1.0);
     // whole-layer sequence (no graph)
     int st4[4] = {186, 0, 0, 0};

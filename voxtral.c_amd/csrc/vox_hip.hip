@@ -2092,7 +2092,7 @@ static int enqueue_graph_step(vox_hip_stream_t* s, int splits) {
     if (enqueue_step_layers(s, s->state, 0, nullptr, splits)) return -1;
     CK(launch_argmax_final(s->pval, s->pidx, gemv_grid(c.vocab), s->state, s->tokens, s->tokens_cap,
                            s->adapter, s->adapter_cap, s->m->tok_emb, s->m->tok_emb_s, c.dec_dim, s->xd,
-                           s->part_alt, s->n_alt > 1 ? s->alts : nullptr, s->st));
+                           s->part_alt, s->n_alt > 1 ? s->alts : nullptr, c.vocab, s->st));
     return 0;
 }
 
@@ -2693,7 +2693,7 @@ extern "C" int vox_hip_decoder_full_step(vox_hip_stream_t* s, const float* rope_
     int st4[4] = {0, 0, 0, 0};
     CK(hipMemcpyAsync(tmp_state, st4, sizeof st4, hipMemcpyHostToDevice, s->st));
     CK(launch_argmax_final(s->pval, s->pidx, gemv_grid(c.vocab), tmp_state, nullptr, 0, nullptr, 0,
-                           nullptr, nullptr, c.dec_dim, nullptr, nullptr, nullptr, s->st));
+                           nullptr, nullptr, c.dec_dim, nullptr, nullptr, nullptr, c.vocab, s->st));
     CK(hipMemcpyAsync(st4, tmp_state, sizeof st4, hipMemcpyDeviceToHost, s->st));
     if (logits) CK(hipMemcpyAsync(logits, s->logits, (size_t)c.vocab * 4, hipMemcpyDeviceToHost, s->st));
     CK(hipStreamSynchronize(s->st));

@@ -167,7 +167,7 @@ hipError_t launch_embed_rows(const float* adapter, const void* emb, const float*
 hipError_t launch_argmax_final(const float* pv, const int* pi, int n, int* state, int* tokens,
                                int cap, const float* adapter, int adapter_rows,
                                const void* emb, const float* esc, int D, float* x,
-                               const float* part_alt, float* alts, hipStream_t st);
+                               const float* part_alt, float* alts, int V, hipStream_t st);
 // batched step: x_i = adapter_i[state[1]] + tok_emb[state[2]] for every live slot, 0 otherwise
 hipError_t launch_embed_batch(const BatchSlot* slots, int nb, const void* emb, const float* esc, int D, float* x,
                               hipStream_t st);

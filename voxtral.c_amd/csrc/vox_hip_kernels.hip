@@ -1717,7 +1717,8 @@ __global__ __launch_bounds__(256) void k_embed_rows(const float* __restrict__ ad
 
 // stream_fill_alts candidates (voxtral.c:955-1010) from the LM head's per-block partials:
 // the softmax denominator S = sum_b s_b exp(m_b - M) and the 3 largest logits with id >=
-// TOKEN_TEXT_MIN other than the chosen token (ties: lower id).  Writes the step's record
+// TOKEN_TEXT_MIN other than the chosen token (ties: lower id; a candidate whose probability
+// underflows to 0 gives way to the lowest unused text id, see alt_merge).  Writes the step's record
 // {p_best, id1, p1, id2, p2, id3, p3, 0}, p = exp(l - M) * (1 / S); the host applies n_alt
 // and the cutoff.  Called by all 256 threads of k_argmax_final after its barrier.
 __device__ __forceinline__ bool alt_before(float va, int ia, float vb, int ib) {
@@ -1781,7 +1782,7 @@ __device__ void alt_tree(float& m, float& su, float (&tv)[4], int (&ti)[4]) {
 }
 
 __device__ void alt_merge(const float* __restrict__ pa, int n, int best, float bestv, int step,
-                          float* __restrict__ alts) {
+                          float* __restrict__ alts, int V) {
     const int t = threadIdx.x;
     float m = -INFINITY, su = 0.f, tv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int ti[4] = {-1, -1, -1, -1};
@@ -1813,10 +1814,26 @@ __device__ void alt_merge(const float* __restrict__ pa, int n, int best, float b
         const float inv = 1.0f / su;
         float* r = alts + (size_t)step * ALT_REC;
         r[0] = expf(bestv - m) * inv;
+        int used[3];
         for (int k = 0; k < 3; k++) {
-            const int id = ti[k];
+            int id = ti[k];
+            float p = id >= 0 ? expf(tv[k] - m) * inv : 0.f;
+            if (!(p > 0.f)) {
+                // The reference ranks probabilities, not logits.  Once the largest one left has
+                // underflowed to 0 every unused text id ties at 0, and its ascending scan with a
+                // strict '>' (from -1) takes the lowest of them, whatever their logits.
+                id = ALT_TEXT_MIN;
+                for (bool moved = true; moved;) {
+                    moved = id == best;
+                    for (int j = 0; j < k; j++) moved |= used[j] == id;
+                    id += moved;
+                }
+                if (id >= V) id = -1;
+                p = 0.f;
+            }
+            used[k] = id;
             r[1 + 2 * k] = __int_as_float(id);
-            r[2 + 2 * k] = id >= 0 ? expf(tv[k] - m) * inv : 0.f;
+            r[2 + 2 * k] = p;
         }
         r[7] = 0.f;
     }
@@ -1836,7 +1853,7 @@ __global__ __launch_bounds__(256) void k_argmax_final(const float* __restrict__ 
                                                       const float* __restrict__ esc, int D,
                                                       float* __restrict__ x,
                                                       const float* __restrict__ part_alt,
-                                                      float* __restrict__ alts) {
+                                                      float* __restrict__ alts, int V) {
     constexpr int XPT = 16;  // next-input elements per thread (D <= 4096)
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -1889,7 +1906,7 @@ __global__ __launch_bounds__(256) void k_argmax_final(const float* __restrict__ 
         for (int j = 0; j < XPT; j++)
             if (tid + 256 * j < D) x[tid + 256 * j] = av[j] + emb_at(emb, esc, tok, D, tid + 256 * j);
     }
-    if (alts) alt_merge(part_alt, n, tok, best, step % tokens_cap, alts);
+    if (alts) alt_merge(part_alt, n, tok, best, step % tokens_cap, alts, V);
 }
 
 // ============================================================================
@@ -1973,7 +1990,7 @@ __global__ __launch_bounds__(256) void k_argmax_batch_final(const float* __restr
                                                             const float* __restrict__ palt, BatchSlot* __restrict__ slots,
                                                             int tokens_cap, int* __restrict__ toklog,
                                                             const void* __restrict__ emb, const float* __restrict__ esc,
-                                                            int D, float* __restrict__ x) {
+                                                            int D, float* __restrict__ x, int V) {
     __shared__ int stok, srow, slive, sstep;
     __shared__ float sbest;
     const int i = blockIdx.x;
@@ -2020,7 +2037,7 @@ __global__ __launch_bounds__(256) void k_argmax_batch_final(const float* __restr
     __syncthreads();
     const float* a = sl->adapter + (size_t)srow * D;
     for (int j = threadIdx.x; j < D; j += 256) xr[j] = slive ? a[j] + emb_at(emb, esc, stok, D, j) : 0.f;
-    if (sl->alts) alt_merge(palt + (size_t)i * ARGB * ALT_PART, ARGB, stok, sbest, sstep % tokens_cap, sl->alts);
+    if (sl->alts) alt_merge(palt + (size_t)i * ARGB * ALT_PART, ARGB, stok, sbest, sstep % tokens_cap, sl->alts, V);
 }
 
 // ============================================================================
@@ -3627,10 +3644,10 @@ hipError_t launch_embed_rows(const float* adapter, const void* emb, const float*
 hipError_t launch_argmax_final(const float* pv, const int* pi, int n, int* state, int* tokens,
                                int cap, const float* adapter, int adapter_rows,
                                const void* emb, const float* esc, int D, float* x,
-                               const float* part_alt, float* alts, hipStream_t st) {
+                               const float* part_alt, float* alts, int V, hipStream_t st) {
     if (adapter && D > 16 * 256) return hipErrorInvalidValue;  // k_argmax_final: 16 next-input elements per thread
     hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, st, pv, pi, n, state, tokens, cap,
-                       adapter, adapter_rows, emb, esc, D, x, part_alt, alts);
+                       adapter, adapter_rows, emb, esc, D, x, part_alt, alts, V);
     LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -3650,7 +3667,7 @@ hipError_t launch_argmax_batch(const float* logits, int nb, int V, float* pval, 
     hipLaunchKernelGGL(k_argmax_rows, dim3(ARGB, nb), dim3(256), 0, st, logits, V, pval, pidx, slots, palt);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_argmax_batch_final, dim3(nb), dim3(256), 0, st, pval, pidx, palt, slots, tokens_cap, toklog,
-                       emb, esc, D, x);
+                       emb, esc, D, x, V);
     LAUNCH_CHECK();
     return hipSuccess;
 }
