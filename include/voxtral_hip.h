@@ -264,6 +264,24 @@ int vox_hip_batch_read_logits(vox_hip_batch_t *b, vox_hip_stream_t *s, float *ou
 /* Counters since creation: [0] calls, [1] step replays, [2] live rows over those steps,
  * [3] step-graph captures, [4] batched prefill passes, [5] prefilled streams. */
 int vox_hip_batch_stats(const vox_hip_batch_t *b, long long *out6);
+/* Opt-in step for small batches: the R-row GEMV (k_gemvr) streams each weight matrix once per
+ * step for the whole bucket -- bf16 rows or the model's wpack13 planes, as the single-stream
+ * step does -- in five launches per layer, instead of the skinny MFMA GEMMs over the
+ * fragment-major copies.
+ * Steps whose slot bucket is <= max_rows (0 = off, the default; 1, 2, 4 or 8) take the R-row
+ * GEMV path; larger buckets keep the MFMA step.  Tokens, logits (to f32 summation order),
+ * alternatives, rings and stream state are those of the MFMA step, and the mode may change
+ * between calls.  VOX_HIP_BATCH_GEMV=<0|1|2|4|8> sets the initial value at
+ * vox_hip_batch_create (ignored for a Q8 model).  Returns 0; -1 (vox_hip_last_error) for
+ * another value, for a Q8 model, or between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
+/* [0] max_rows in effect, [1] step replays on the GEMV path, [2] live rows over those,
+ * [3] GEMV step-graph captures.  ([1]..[3] are also counted in vox_hip_batch_stats.) */
+int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
+/* Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
+ * bucket >= R (unused rows zero).  Returns flags: bit 0 the packed instance ran, bit 1 the
+ * per-row summation order is the single-row GEMV's; -1 on error. */
+int vox_hip_gemv_rows(int rows, int K, const uint16_t *W, const float *x, int R, float *y, int packed);
 /* Decoder state snapshot: [0]=kv logical length, [1]=next adapter row, [2]=prev token,
  * [3]=started, [4]=eos_seen, [5]=tokens generated. */
 int vox_hip_stream_state(vox_hip_stream_t *s, int *out6);

@@ -405,6 +405,72 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemvr")) {
+        // k_gemvr (the R-row GEMV of the small batched step): each full-size projection and the
+        // LM head at R = 1, 2, 4, 8, raw and packed, cold weights (a buffer per layer), with
+        // k_gemv on the same shape in the same process.  us, bytes streamed once, fraction of
+        // 8 TB/s.  VOX_KB_GEMVR_SHAPES=w2 (or any list of qkv,wo,w13,w2,lm) limits the shapes.
+        struct S { const char* n; int pro, epi, epi1, K, rows; std::vector<uint16_t*>* w; };
+        const char* only = getenv("VOX_KB_GEMVR_SHAPES");
+        CK(hipMemset(state, 0, 16));
+        std::vector<uint16_t*> lm1(1, emb);
+        const int RM = GEMVR_MAX_ROWS;
+        float* xr = (float*)dmalloc((size_t)RM * DH * 4, 1);
+        float* yr = (float*)dmalloc((size_t)RM * V * 4, 0);
+        // slot s: live, position 0, its own 1024 ring rows of the K / V buffers
+        BatchSlot hs[RM];
+        memset(hs, 0, sizeof hs);
+        for (int s = 0; s < RM; s++) {
+            hs[s].Kc = (char*)(Kc + (size_t)s * 1024 * DKV);
+            hs[s].Vc = (char*)(Vc + (size_t)s * 1024 * DKV);
+            hs[s].live = 1;
+        }
+        BatchSlot* slots = (BatchSlot*)dmalloc(sizeof hs, 0);
+        CK(hipMemcpy(slots, hs, sizeof hs, hipMemcpyHostToDevice));
+        for (S o : {S{"qkv", PRO_NORM, EPI_QKV, EPI_QKV, D, DQ + 2 * DKV, &wqkv}, S{"wo", PRO_NONE, EPI_RESID, EPI_RESID, DQ, D, &wo},
+                    S{"w13", PRO_NORM_ADA, EPI_SWIGLU, EPI_SWIGLU, D, 2 * DH, &w13}, S{"w2", PRO_NONE, EPI_RESID, EPI_RESID, DH, D, &w2},
+                    S{"lm", PRO_NORM, EPI_STORE, EPI_LOGITS, D, V, &lm1}}) {
+            if (only && !strstr(only, o.n)) continue;
+            const int rb = gemv_rowgroup(o.rows), sw = vox_wpack13_side_words(o.K, rb);
+            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sideb = (size_t)o.rows / rb * 256 * sw * 4;
+            const int nl = (int)o.w->size();
+            std::vector<void*> pm(nl), ps(nl);
+            for (int l = 0; l < nl; l++) {
+                pm[l] = dmalloc(mainb, 1);
+                ps[l] = dmalloc(sideb, 0);
+            }
+            const int ldy = o.epi == EPI_QKV ? DQ : o.epi == EPI_SWIGLU ? DH : o.rows;
+            auto args = [&](int l, int packed) {
+                GemvRArgs a;
+                memset(&a, 0, sizeof a);
+                a.g.x = xr; a.ldx = o.K; a.g.K = o.K; a.g.W = (*o.w)[l]; a.g.rows = o.rows; a.g.norm_w = normw; a.g.ada = ada;
+                a.g.eps = 1e-5f; a.g.y = yr; a.ldy = ldy; a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = HD; a.g.rope = rope;
+                a.g.state = state; a.g.Kc = Kc; a.g.Vc = Vc; a.g.cap = 1024; a.g.part_val = pv; a.g.part_idx = pi;
+                a.slots = slots;
+                if (packed) { a.g.wp_main = pm[l]; a.g.wp_side = ps[l]; }
+                return a;
+            };
+            const int it = nl == 1 ? iters / 10 + 1 : iters;
+            for (int packed = 0; packed < 2; packed++) {
+                const double bytes = packed ? (double)mainb + sideb : (double)o.rows * o.K * 2;
+                char nm[96];
+                snprintf(nm, sizeof nm, "gemvr %-4s %s k_gemv", o.n, packed ? "packed" : "raw   ");
+                const double us1 = timeit([&] { GemvRArgs a = args(layer++ % nl, packed); CK(launch_gemv(o.pro, o.epi1, a.g, st)); }, it, st);
+                printf("%-30s %9.2f us  %6.1f MB  %5.1f %% of 8 TB/s\n", nm, us1, bytes / 1e6, bytes / us1 / 8e6 * 100);
+                for (int R : {1, 2, 4, 8}) {
+                    GemvRArgs a0 = args(0, packed);
+                    const int occ = gemv_occupancy(gemvr_kernel(o.pro, o.epi, R, a0));
+                    snprintf(nm, sizeof nm, "gemvr %-4s %s R = %d", o.n, packed ? "packed" : "raw   ", R);
+                    const double us = timeit([&] { GemvRArgs a = args(layer++ % nl, packed); CK(launch_gemvr(o.pro, o.epi, R, a, st)); }, it, st);
+                    printf("%-30s %9.2f us  %6.1f MB  %5.1f %% of 8 TB/s  %d blocks/CU  %.2fx k_gemv\n", nm, us, bytes / 1e6,
+                           bytes / us / 8e6 * 100, occ, us / us1);
+                    fflush(stdout);
+                }
+            }
+            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); }
+        }
+        return 0;
+    }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gpe")) {
         // where the fused prologue / epilogue cost of the W1|W3 and QKV GEMVs sits: each
         // prologue x epilogue combination of the same weights, bf16 and Q8

@@ -2520,6 +2520,45 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
     return rc ? -1 : was_packed;
 }
 
+// Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
+// bucket >= R (the bucket's unused rows are zero), from the wpack13 planes (packed = 1) or
+// from the raw rows.  Returns flags: bit 0 the packed instance ran, bit 1 the per-row
+// summation order is k_gemv's (every shape: k_gemvr never splits K); -1 on error.
+extern "C" int vox_hip_gemv_rows(int rows, int K, const uint16_t* W, const float* x, int R, float* y, int packed) {
+    std::lock_guard<std::mutex> lk(g_twin_mu);
+    if (!W || !x || !y) return set_err("gemv_rows: null argument");
+    if (R < 1 || R > GEMVR_MAX_ROWS) return set_err("gemv_rows: %d rows (1..%d)", R, GEMVR_MAX_ROWS);
+    if (!gemvr_ok(PRO_NONE, EPI_STORE, rows, K)) return set_err("gemv_rows: no k_gemvr instance for %d x %d", rows, K);
+    if (twin_init()) return -1;
+    int Rb = 1;
+    while (Rb < R) Rb *= 2;
+    uint8_t* dW = nullptr;
+    float *dx = nullptr, *dy = nullptr;
+    WPackD P = {nullptr, nullptr, 0};
+    vox_hip_wpack_stats_t S;
+    memset(&S, 0, sizeof S);
+    auto run = [&]() -> int {
+        CK(dalloc(&dW, (size_t)rows * K * 2));
+        CK(dalloc(&dx, (size_t)Rb * K));
+        CK(dalloc(&dy, (size_t)Rb * rows));
+        CK(hipMemset(dx, 0, (size_t)Rb * K * 4));
+        if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)R * K * 4)) return -1;
+        if (wpack_make(packed, S, &P, W, rows, K, 0)) return -1;
+        GemvRArgs a;
+        memset(&a, 0, sizeof a);
+        a.g.x = dx; a.ldx = K; a.g.K = K; a.g.W = dW; a.g.rows = rows; a.g.y = dy; a.ldy = rows;
+        wpack_args(a.g, P);
+        CK(launch_gemvr(PRO_NONE, EPI_STORE, Rb, a, g_twin_st));
+        CK(hipStreamSynchronize(g_twin_st));
+        CK(hipMemcpy(y, dy, (size_t)R * rows * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    const int was_packed = P.main != nullptr;
+    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side);
+    return rc ? -1 : (was_packed | 2);
+}
+
 extern "C" void vox_hip_sgemm_bf16(int M, int N, int K, const float* A, const uint16_t* B, float* C) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
     twin_sgemm(M, N, K, A, B, nullptr, C);
@@ -2740,6 +2779,13 @@ struct vox_hip_batch {
     // streams come and go; captured again only when the model's rope table moves
     hipGraphExec_t gexec[2][6][STEP_GRAPHS];
     int grope_gen;
+    // the R-row GEMV step (batch_step_gemv): steps whose slot bucket is <= gemv_rows take it
+    // (0: off).  Its graphs [kv16][bucket 1, 2, 4, 8][splits bucket] have keys of their own, so
+    // the mode changes between calls without a capture being dropped.
+    int gemv_rows;
+    float* hid;      // SwiGLU rows [GEMVR_MAX_ROWS][dec_hidden] (allocated when the mode is first set)
+    hipGraphExec_t gvexec[2][4][STEP_GRAPHS];
+    long long n_gemv_replays, n_gemv_rows, n_gemv_captures;
     // rows of the last call (b->logits row i = stream luid[i], from its last step when llive[i])
     unsigned long long luid[VOX_MAX_BATCH];
     int llive[VOX_MAX_BATCH];
@@ -2755,6 +2801,7 @@ struct vox_hip_batch {
     // vox_hip_batch_finish): its streams, outputs and the steps left after the chunk in flight
     struct {
         int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kv16, done, k;
+        int gemv;  // the call's steps take the GEMV path
         vox_hip_stream_t* streams[VOX_MAX_BATCH];
         int* tokens_out;
         int* counts_out;
@@ -2810,6 +2857,13 @@ static void batch_drop_graphs(vox_hip_batch_t* b) {
                     hipGraphExecDestroy(e);
                     e = nullptr;
                 }
+    for (auto& k : b->gvexec)
+        for (auto& g : k)
+            for (auto& e : g)
+                if (e) {
+                    hipGraphExecDestroy(e);
+                    e = nullptr;
+                }
 }
 
 extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
@@ -2817,13 +2871,15 @@ extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
     if (b->st) hipStreamSynchronize(b->st);
     dfree(b->x); dfree(b->part); dfree(b->ssq); dfree(b->ticket); dfree(b->q); dfree(b->att);
     dfree(b->logits); dfree(b->pval); dfree(b->pidx); dfree(b->palt); dfree(b->apart);
-    dfree(b->xp_d); dfree(b->xp_q); dfree(b->xp_h); dfree(b->pgws); dfree(b->gflags);
+    dfree(b->xp_d); dfree(b->xp_q); dfree(b->xp_h); dfree(b->pgws); dfree(b->gflags); dfree(b->hid);
     if (b->slots) hipFree(b->slots);
     if (b->hslots) hipHostFree(b->hslots);
     batch_drop_graphs(b);
     if (b->st) hipStreamDestroy(b->st);
     delete b;
 }
+
+static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows);
 
 extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_streams) {
     if (!m || max_streams < 1 || max_streams > VOX_MAX_BATCH) {
@@ -2876,6 +2932,12 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
     TRYH(dalloc(&b->xp_q, (size_t)3 * S * c.dec_heads * c.dec_head_dim));
     TRYH(dalloc(&b->xp_h, (size_t)3 * S * c.dec_hidden));
 #undef TRYH
+    // VOX_HIP_BATCH_GEMV=<0|1|2|4|8>: the initial max_rows of the R-row GEMV step (unset: 0;
+    // a Q8 model keeps 0)
+    if (const char* e = getenv("VOX_HIP_BATCH_GEMV")) {
+        const int r = atoi(e);
+        if (r && !(m->tok_emb_s || m->dec[0].sqkv) && batch_set_gemv_rows(b, r)) return fail();
+    }
     return b;
 }
 
@@ -2960,6 +3022,108 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16) {
     return 0;
 }
 
+// The same step for a bucket of nb <= 8 slots on the R-row GEMV (k_gemvr): the
+// single-stream step's five launches per layer with every weight byte (bf16 rows, or the
+// model's wpack13 planes) read once for the nb rows, and no planes, slabs or tickets.  Between
+// the launches the rows live in b->x (residual stream, updated in place), b->q, b->att and
+// b->hid; attention is the slot-table kernel of the single-stream step.  b->x is complete
+// before and after either step, so the two may alternate from one call to the next.
+static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kv16) {
+    vox_hip_model_t* m = b->m;
+    const vox_hip_config_t& c = m->c;
+    const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
+    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int cap = c.dec_window + DEC_SLACK;
+    const size_t ring_layer = (size_t)cap * DKV * (kv16 ? 2 : 4);
+    hipStream_t st = b->st;
+    AttnPtrs ap;
+    memset(&ap, 0, sizeof ap);
+    ap.slots = b->slots;
+    for (int i = 0; i < nb; i++) {
+        ap.q[i] = b->q + (size_t)i * DQ;
+        ap.part[i] = b->apart + (size_t)i * b->apart_n;
+        ap.out[i] = b->att + (size_t)i * DQ;
+    }
+    GemvRArgs a;
+    for (int l = 0; l < c.dec_layers; l++) {
+        const DecLayerD& L = m->dec[l];
+        ap.ring_off = (size_t)l * ring_layer;
+        // norm -> QKV -> RoPE -> KV append of every live slot
+        memset(&a, 0, sizeof a);
+        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.wqkv; a.g.rows = DQ + 2 * DKV;
+        a.g.norm_w = L.attn_norm; a.g.eps = c.dec_eps; a.g.y = b->q; a.ldy = DQ;
+        a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kv16 = kv16;
+        a.slots = b->slots; a.ring_off = ap.ring_off;
+        wpack_args(a.g, L.pqkv);
+        CK(launch_gemvr(PRO_NORM, EPI_QKV, nb, a, st));
+        CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kv16));
+        // wo + residual
+        memset(&a, 0, sizeof a);
+        a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
+        wpack_args(a.g, L.po);
+        CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
+        // norm * (1 + ada) -> W1|W3 -> silu * up
+        memset(&a, 0, sizeof a);
+        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.w13; a.g.rows = 2 * DH; a.g.norm_w = L.ffn_norm;
+        a.g.ada = m->ada_scale + (size_t)l * DD; a.g.eps = c.dec_eps; a.g.y = b->hid; a.ldy = DH;
+        wpack_args(a.g, L.p13);
+        CK(launch_gemvr(PRO_NORM_ADA, EPI_SWIGLU, nb, a, st));
+        // W2 + residual
+        memset(&a, 0, sizeof a);
+        a.g.x = b->hid; a.ldx = DH; a.g.K = DH; a.g.W = L.w2; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
+        wpack_args(a.g, L.p2);
+        CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
+    }
+    // final norm + LM head rows, then the batched step's own end (argmax, alternatives, token
+    // log, state, next inputs)
+    memset(&a, 0, sizeof a);
+    a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = m->tok_emb; a.g.rows = c.vocab; a.g.norm_w = m->dec_norm;
+    a.g.eps = c.dec_eps; a.g.y = b->logits; a.ldy = c.vocab;
+    wpack_args(a.g, m->plm);
+    CK(launch_gemvr(PRO_NORM, EPI_STORE, nb, a, st));
+    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots),
+                           m->tok_emb, m->tok_emb_s, DD, b->x, st));
+    return 0;
+}
+
+// the shapes of the model all have k_gemvr instances
+static bool model_gemvr_ok(const vox_hip_model_t* m) {
+    const vox_hip_config_t& c = m->c;
+    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
+    return gemvr_ok(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DQ) &&
+           gemvr_ok(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DH) &&
+           gemvr_ok(PRO_NORM, EPI_STORE, c.vocab, DD);
+}
+
+static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
+    if (max_rows != 0 && max_rows != 1 && max_rows != 2 && max_rows != 4 && max_rows != 8)
+        return set_err("batch_set_gemv_rows: max_rows %d is not 0, 1, 2, 4 or 8", max_rows);
+    if (b->call.active) return set_err("batch_set_gemv_rows: a begun call was not finished");
+    if (max_rows) {
+        const vox_hip_model_t* m = b->m;
+        if (m->tok_emb_s || m->dec[0].sqkv) return set_err("batch_set_gemv_rows: the GEMV step takes bf16 weights, not Q8");
+        if (!model_gemvr_ok(m)) return set_err("batch_set_gemv_rows: no k_gemvr instance for this model's shapes");
+        if (!b->hid) CK(dalloc(&b->hid, (size_t)GEMVR_MAX_ROWS * m->c.dec_hidden));
+    }
+    b->gemv_rows = max_rows;
+    return 0;
+}
+
+extern "C" int vox_hip_batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
+    if (!b) return set_err("batch_set_gemv_rows: null batch");
+    return batch_set_gemv_rows(b, max_rows);
+}
+
+extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out4) {
+    if (!b || !out4) return set_err("batch_gemv_stats: null argument");
+    out4[0] = b->gemv_rows;
+    out4[1] = b->n_gemv_replays;
+    out4[2] = b->n_gemv_rows;
+    out4[3] = b->n_gemv_captures;
+    return 0;
+}
+
 // slot bucket of n streams: 1, 2, 4, 8, 16 or 32 slots (graph g of the bucket)
 static int slot_bucket(int n, int* g) {
     int k = 0;
@@ -2970,10 +3134,12 @@ static int slot_bucket(int n, int* g) {
 
 // `steps` batched steps over slots 0..nb-1: replays of the bucket's step graph (captured the
 // first time, and again only when the rope table moved), or eager launches
-static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kv16, int steps) {
+static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kv16, int steps, int gemv) {
+    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kv16) : batch_step(b, nb, splits, kv16); };
+    if (gemv) b->n_gemv_replays += steps;
     if (!use_graphs()) {
         for (int k = 0; k < steps; k++)
-            if (batch_step(b, nb, splits, kv16)) return -1;
+            if (step()) return -1;
         b->n_replays += steps;
         return 0;
     }
@@ -2981,11 +3147,11 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = b->gexec[kv16][gb][gi];
+    hipGraphExec_t& ge = gemv ? b->gvexec[kv16][gb][gi] : b->gexec[kv16][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
-        const int rc = batch_step(b, nb, splits, kv16);
+        const int rc = step();
         hipError_t e = hipStreamEndCapture(b->st, &g);
         if (rc || e != hipSuccess) {
             if (g) hipGraphDestroy(g);
@@ -2998,6 +3164,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
             return set_err("batch graph instantiate failed: %s", hipGetErrorString(e));
         }
         b->n_captures++;
+        if (gemv) b->n_gemv_captures++;
     }
     for (int k = 0; k < steps; k++) CK(hipGraphLaunch(ge, b->st));
     b->n_replays += steps;
@@ -3203,10 +3370,13 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     //    table + token log comes back; the call ends when no slot is live.  The first chunk
     //    goes out here, the rest in batch_finish.
     const int k = std::min(STEP_BATCH, K);
-    if (batch_run(b, nb, gb, gi, splits, kv16, k)) return -1;
+    // buckets of up to gemv_rows slots take the R-row GEMV step (vox_hip_batch_set_gemv_rows)
+    const int gemv = b->gemv_rows && nb <= b->gemv_rows;
+    if (batch_run(b, nb, gb, gi, splits, kv16, k, gemv)) return -1;
     CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
     auto& cl = b->call;
     cl.active = 1;
+    cl.gemv = gemv;
     cl.n = n;
     for (int i = 0; i < n; i++) cl.streams[i] = streams[i];
     cl.max_steps = max_steps;
@@ -3255,7 +3425,7 @@ static int batch_finish(vox_hip_batch_t* b) {
         }
         if (!any || done >= K) break;
         k = std::min(STEP_BATCH, K - done);
-        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kv16, k)) return -1;
+        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kv16, k, cl.gemv)) return -1;
         CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
     }
     // 4. host mirrors
@@ -3275,6 +3445,7 @@ static int batch_finish(vox_hip_batch_t* b) {
     }
     b->lnb = n;
     b->n_rows += total;
+    if (cl.gemv) b->n_gemv_rows += total;
     return total;
 }
 

@@ -71,7 +71,18 @@ struct BatchSlot {
     int produced;           // steps taken in this call (index into the batch's token log)
 };
 static_assert(sizeof(BatchSlot) == 72, "BatchSlot layout");
-constexpr int BATCH_TOKLOG = 64;     // per-slot token log entries (>= the steps between reads)
+// k_gemvr: k_gemv over R <= 8 input rows (a small batched decode step).  g describes row 0
+// (x, y) and everything the rows share; Q8 weights and biases are not taken.
+constexpr int GEMVR_MAX_ROWS = 8;
+struct GemvRArgs {
+    GemvArgs g;
+    int ldx, ldy;            // floats between consecutive rows of x / y
+    // EPI_QKV: row r takes position, liveness and rings (layer-0 base + ring_off bytes) from
+    // slots[r]; g.state / g.pos / g.Kc / g.Vc are not used
+    const BatchSlot* slots;
+    size_t ring_off;
+};
+constexpr int BATCH_TOKLOG = 64;    // per-slot token log entries (>= the steps between reads)
 
 // per-stream operands of one decode-attention launch (blockIdx.z = stream of a batch)
 struct AttnPtrs {
@@ -126,6 +137,12 @@ const void* gemv_kernel(int pro, int epi, const GemvArgs& a);
 hipError_t launch_gemv_timed(int pro, int epi, const GemvArgs& a, hipEvent_t start, hipEvent_t stop,
                              hipStream_t st);
 int gemv_occupancy(const void* fn);
+// R = 1, 2, 4 or 8 rows; (pro, epi) in {NORM/QKV, NONE/RESID, NORM_ADA/SWIGLU, NORM/STORE (the
+// LM head), NONE/STORE}.  gemvr_ok: the launch has an instance (K rounds <= 2 where the input
+// is a dec_dim row or the group is 8 rows, <= 5 otherwise)
+bool gemvr_ok(int pro, int epi, int rows, int K);
+hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st);
+const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a);
 // part: H * attn_maxch(window) * (hd + 2) floats of partials, then KVH ints (zeroed before
 // the first launch) that count the split blocks' arrivals
 hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const float* Vc, int cap,

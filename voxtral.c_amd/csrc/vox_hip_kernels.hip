@@ -1100,6 +1100,249 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 }
 
 // ============================================================================
+// R-row weight-streaming GEMV (R = 1, 2, 4, 8: the slot buckets of a small batched decode
+// step): y[r] = W x[r].  k_gemv's block, row groups, grid, chunk mapping, non-temporal buffer
+// loads, early next-group loads and zero-length descriptor, so the P13 instance streams the
+// model's own wpack13 planes; every weight register feeds R FMA chains.  The x rows of a pass
+// live in registers (R * KQ * 8 floats per thread).  More than 160 floats (R * KQ > 20: W2 of
+// the full model at 8 rows would take 320) do not fit beside the weights: such an instance
+// runs two passes of R / 2 rows over the block's groups and reads its weights twice
+// (DESIGN.md 18.3).
+//
+// Each row's arithmetic is k_gemv's, in k_gemv's order, in registers of its own: chunks in j
+// order, the wave sum, the four waves added ((0 + 1) + 2) + 3, and the RMSNorm prologue per
+// row.  So the bits of y[r] depend on W and x[r] alone -- not on R, on r or on the other
+// rows -- and equal k_gemv's for every shape.
+//
+// Epilogues per row r: STORE / RESID on row r of y (stride ldy), SWIGLU into row r of the
+// hidden buffer, QKV with RoPE at slots[r].pos, q into row r of y and K/V into the slot's own
+// rings (a slot that is not live appends nothing; its q row is never read).
+// ============================================================================
+template <int PRO, int EPI, int RB, int KQ, int WF, int R>
+__global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
+    static_assert(WF == WF_BF16 || WF == WF_P13, "k_gemvr streams bf16 rows or wpack13 planes");
+    constexpr bool WP = WF == WF_P13;
+    constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
+    constexpr int RP = R * KQ > 20 ? R / 2 : R;     // rows per pass
+    constexpr bool QKVE = EPI == EPI_QKV;
+    constexpr bool PAIRED = QKVE || EPI == EPI_SWIGLU;
+    constexpr int NL = PAIRED ? RB / 2 : RB;        // epilogue lanes per row
+    static_assert(RP * NL <= 64, "the epilogue owners are lanes of wave 0");
+    __shared__ float red[2][4][RP][RB];
+    __shared__ float sred[4][RP];
+    const GemvArgs& a = ra.g;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K, KC = K >> 3;
+    const int ngroups = a.rows / RB;
+    const int G = gridDim.x;
+    const int rowbytes = WP ? KC * 12 : K * 2;
+    void* const wbase = const_cast<void*>(WP ? a.wp_main : a.W);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, a.rows * rowbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
+    void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
+    // chunk offsets per K round, as k_gemv: chunks past K re-load chunk 0 and meet x = 0
+    int voff[KQ];
+#pragma unroll
+    for (int j = 0; j < KQ; j++) {
+        const int c0 = (j * 4 + wave) * 64 + lane;
+        voff[j] = (c0 < KC ? c0 : 0) * (WP ? 12 : 16);
+    }
+    // epilogue ownership: thread orow * NL + ol of wave 0 finishes row (or row pair) ol of the
+    // group for input row orow of the pass
+    const bool owner = tid < RP * NL;
+    const int orow = owner ? tid / NL : 0, ol = tid % NL;
+    const int i0 = PAIRED ? 2 * ol : ol;
+    int buf = 0;
+#pragma unroll 1
+    for (int r0 = 0; r0 < R; r0 += RP) {
+        int g = blockIdx.x;
+        int rows[RB];
+        uint4 wv[KQ][RB];
+        uint32_t sd[SW];
+        // first group's weights are independent of x: issue them before the prologue
+        gemv_rows<EPI, RB>(g, rows);
+        if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);
+        gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
+
+        float4 xr[RP][KQ][2];
+        float4 nwr[KQ][2], adr[KQ][2];
+        float ss[RP];
+#pragma unroll
+        for (int r = 0; r < RP; r++) ss[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < KQ; j++) {
+            const int c = (j * 4 + wave) * 64 + lane;
+            const int cc = c < KC ? c : 0;
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int r = 0; r < RP; r++) {
+                const float4* xp = reinterpret_cast<const float4*>(a.x + (size_t)(r0 + r) * ra.ldx) + 2 * cc;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const float4 xv = xp[h];
+                    xr[r][j][h] = c < KC ? xv : z;
+                }
+            }
+            if (PRO != PRO_NONE) {
+                // the norm weights (and the ada row) are shared by the rows
+                const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + 2 * cc;
+                const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + 2 * cc;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    nwr[j][h] = wp[h];
+                    if (PRO == PRO_NORM_ADA) adr[j][h] = ap[h];
+                }
+#pragma unroll
+                for (int r = 0; r < RP; r++)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const float4 v = xr[r][j][h];
+                        ss[r] = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss[r]))));
+                    }
+            }
+        }
+        if (PRO != PRO_NONE) {
+            // RMSNorm prologue, per row (k_gemv's arithmetic)
+#pragma unroll
+            for (int r = 0; r < RP; r++) {
+                ss[r] = wave_sum(ss[r]);
+                if (lane == 0) sred[wave][r] = ss[r];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < RP; r++) {
+                const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
+                const float inv = 1.0f / sqrtf(tot / (float)K + a.eps);
+#pragma unroll
+                for (int j = 0; j < KQ; j++)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        float4 v = xr[r][j][h];
+                        const float4 nw = nwr[j][h];
+                        v.x = v.x * inv * nw.x; v.y = v.y * inv * nw.y;
+                        v.z = v.z * inv * nw.z; v.w = v.w * inv * nw.w;
+                        if (PRO == PRO_NORM_ADA) {
+                            const float4 ad = adr[j][h];
+                            v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
+                            v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
+                        }
+                        xr[r][j][h] = v;
+                    }
+            }
+        }
+        if (WP) {
+#pragma unroll
+            for (int r = 0; r < RP; r++)
+#pragma unroll
+                for (int j = 0; j < KQ; j++)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        float4 v = xr[r][j][h];
+                        v.x = ldexpf(v.x, a.wp_d); v.y = ldexpf(v.y, a.wp_d);
+                        v.z = ldexpf(v.z, a.wp_d); v.w = ldexpf(v.w, a.wp_d);
+                        xr[r][j][h] = v;
+                    }
+        }
+
+        // the owner's row of this pass: output row, and for QKV the slot's position and rings
+        float* const yrow = a.y + (size_t)(r0 + orow) * ra.ldy;
+        int lp = 0, live = 0;
+        float *Kc = nullptr, *Vc = nullptr;
+        if (QKVE && owner) {
+            const BatchSlot* sl = ra.slots + (r0 + orow);
+            live = sl->live;
+            lp = live ? sl->pos : 0;
+            Kc = reinterpret_cast<float*>(sl->Kc + ra.ring_off);
+            Vc = reinterpret_cast<float*>(sl->Vc + ra.ring_off);
+        }
+        for (;;) {
+            const int gcur = g;
+            // epilogue inputs of this group (independent of the dot products)
+            int er0 = 0, er1 = 0;
+            float ein0 = 0.f, ein1 = 0.f;
+            if (owner) {
+                int rr[RB];
+                gemv_rows<EPI, RB>(gcur, rr);
+#pragma unroll
+                for (int i = 0; i < RB; i++) {
+                    if (i == i0) er0 = rr[i];
+                    if (i == i0 + 1) er1 = rr[i];
+                }
+                if (EPI == EPI_RESID) ein0 = yrow[er0];
+                if (QKVE && er0 < a.qd + a.kvd) {
+                    const int col = er0 < a.qd ? er0 : er0 - a.qd;
+                    const float* rp = a.rope + (size_t)lp * a.hd + ((col % a.hd) & ~1);
+                    ein0 = rp[0];
+                    ein1 = rp[1];
+                }
+            }
+            float acc[RP][RB];
+#pragma unroll
+            for (int r = 0; r < RP; r++)
+#pragma unroll
+                for (int i = 0; i < RB; i++) acc[r][i] = 0.f;
+#pragma unroll
+            for (int j = 0; j < KQ; j++)
+#pragma unroll
+                for (int i = 0; i < RB; i++)
+#pragma unroll
+                    for (int r = 0; r < RP; r++) {
+                        if (WP) acc[r][i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[r][j][0], xr[r][j][1], acc[r][i]);
+                        else acc[r][i] = dot8(wv[j][i], xr[r][j][0], xr[r][j][1], acc[r][i]);
+                    }
+            g += G;
+            // the next group's loads before this group's reduction, unconditionally; past the
+            // last group through the zero-length descriptor (k_gemv)
+            {
+                const bool more = g < ngroups;
+                gemv_rows<EPI, RB>(more ? g : 0, rows);
+                if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
+                gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
+            }
+#pragma unroll
+            for (int r = 0; r < RP; r++)
+#pragma unroll
+                for (int i = 0; i < RB; i++) acc[r][i] = wave_sum(acc[r][i]);
+            if (lane == 0) {
+#pragma unroll
+                for (int r = 0; r < RP; r++)
+#pragma unroll
+                    for (int i = 0; i < RB; i++) red[buf][wave][r][i] = acc[r][i];
+            }
+            __syncthreads();
+            if (owner) {
+                const float v0 = ((red[buf][0][orow][i0] + red[buf][1][orow][i0]) + red[buf][2][orow][i0]) + red[buf][3][orow][i0];
+                float v1 = 0.f;
+                if (PAIRED)
+                    v1 = ((red[buf][0][orow][i0 + 1] + red[buf][1][orow][i0 + 1]) + red[buf][2][orow][i0 + 1]) +
+                         red[buf][3][orow][i0 + 1];
+                if (EPI == EPI_STORE || EPI == EPI_RESID) {
+                    yrow[er0] = ein0 + v0;
+                } else if (EPI == EPI_SWIGLU) {
+                    yrow[gcur * (RB / 2) + ol] = silu(v0) * v1;
+                } else if (QKVE) {
+                    if (er0 < a.qd + a.kvd) {
+                        const float o0 = v0 * ein0 - v1 * ein1, o1 = v0 * ein1 + v1 * ein0;
+                        if (er0 < a.qd) {
+                            yrow[er0] = o0;
+                            yrow[er1] = o1;
+                        } else if (live) {
+                            kv_st2_rt(Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kv16);
+                        }
+                    } else if (live) {
+                        kv_st2_rt(Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kv16);
+                    }
+                }
+            }
+            buf ^= 1;
+            if (g >= ngroups) break;
+        }
+    }
+}
+
+// ============================================================================
 // Decode attention (one query per head, GQA group of <= 4 heads per kv head).
 // Keys: the last min(lp+1, window) logical positions (voxtral_decoder.c:731-733 after
 // compaction; voxtral_kernels.c:554-560).  A block owns up to 256 consecutive keys and HPB
@@ -3462,6 +3705,70 @@ hipError_t launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t st) {
     GEMV_CASE(PRO_NORM, EPI_QKV_BIAS) GEMV_CASE(PRO_NORM, EPI_SWIGLU)
 #undef GEMV_CASE
     return hipErrorInvalidValue;
+}
+
+// k_gemvr instances: 8-row groups only where the LM head has them (STORE), and more than two
+// K rounds only where the input is not a dec_dim row (wo and W2: PRO_NONE) and the group is
+// not the LM head's
+template <int P, int E, int RB, int KQ>
+constexpr bool gemvr_inst = (RB < 8 || E == EPI_STORE) && (KQ <= 2 || (P == PRO_NONE && RB < 8));
+
+template <int P, int E, int RB, int KQ, int WF>
+static const void* gemvr_fn_r(int R) {
+    if constexpr (gemvr_inst<P, E, RB, KQ>) {
+        switch (R) {
+            case 1: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 1>);
+            case 2: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 2>);
+            case 4: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 4>);
+            case 8: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 8>);
+        }
+    }
+    return nullptr;
+}
+template <int P, int E, int RB, int WF>
+static const void* gemvr_fn_kq(int kq, int R) {
+    switch (kq) {
+        case 1: return gemvr_fn_r<P, E, RB, 1, WF>(R);
+        case 2: return gemvr_fn_r<P, E, RB, 2, WF>(R);
+        case 3: return gemvr_fn_r<P, E, RB, 3, WF>(R);
+        case 4: return gemvr_fn_r<P, E, RB, 4, WF>(R);
+        case 5: return gemvr_fn_r<P, E, RB, 5, WF>(R);
+        default: return nullptr;
+    }
+}
+template <int P, int E>
+static const void* gemvr_fn(int rb, int kq, bool packed, int R) {
+#define GEMVR_RB(RB) \
+    if (rb == RB) return packed ? gemvr_fn_kq<P, E, RB, WF_P13>(kq, R) : gemvr_fn_kq<P, E, RB, WF_BF16>(kq, R);
+    GEMVR_RB(2) GEMVR_RB(4) GEMVR_RB(8)
+#undef GEMVR_RB
+    return nullptr;
+}
+static const void* gemvr_pick(int pro, int epi, int rows, int K, bool packed, int R) {
+    if (!gemv_ok(rows, K, 0)) return nullptr;
+    const int rb = gemv_rb(rows), kq = ((K >> 3) + 255) / 256;
+#define GEMVR_FN(P, E) \
+    if (pro == P && epi == E) return gemvr_fn<P, E>(rb, kq, packed, R);
+    GEMVR_FN(PRO_NORM, EPI_QKV) GEMVR_FN(PRO_NONE, EPI_RESID) GEMVR_FN(PRO_NORM_ADA, EPI_SWIGLU)
+    GEMVR_FN(PRO_NORM, EPI_STORE) GEMVR_FN(PRO_NONE, EPI_STORE)
+#undef GEMVR_FN
+    return nullptr;
+}
+
+bool gemvr_ok(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, false, 1) != nullptr; }
+
+// kernel instance launch_gemvr would use (tools, occupancy queries)
+const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a) {
+    return gemvr_pick(pro, epi, a.g.rows, a.g.K, a.g.wp_main != nullptr, R);
+}
+
+hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st) {
+    if (a.g.wscale || a.g.bias || (epi == EPI_QKV && !a.slots)) return hipErrorInvalidValue;
+    const void* fn = gemvr_kernel(pro, epi, R, a);
+    if (!fn) return hipErrorInvalidValue;
+    GemvRArgs args = a;
+    void* kargs[] = {&args};
+    return hipLaunchKernel(fn, dim3(gemv_grid(a.g.rows)), dim3(256), kargs, 0, st);
 }
 
 // partial slots per head (at least 4)

@@ -54,6 +54,23 @@ def gemv_wpack(W_bf16, x, packed: bool):
     return y, bool(rc)
 
 
+def gemv_rows(W_bf16, x, packed: bool):
+    """Test entry: (y [R, rows], flags) of y[r] = W x[r] for R <= 8 rows through the R-row GEMV
+    (vox_hip_gemv_rows); flags bit 0: the packed instance ran, bit 1: the per-row summation
+    order is the single-row GEMV's"""
+    init()
+    W = np.ascontiguousarray(W_bf16, np.uint16)
+    xv = np.ascontiguousarray(x, np.float32)
+    rows, K = W.shape
+    assert xv.ndim == 2 and xv.shape[1] == K
+    R = xv.shape[0]
+    y = np.empty((R, rows), np.float32)
+    rc = lib().vox_hip_gemv_rows(rows, K, W.ctypes.data, fptr(xv), R, fptr(y), int(packed))
+    if rc < 0:
+        _err("gemv_rows")
+    return y, rc
+
+
 # exported symbols, as declared in include/voxtral_hip.h
 EXPORTS = [
     "vox_hip_init", "vox_hip_available", "vox_hip_shutdown", "vox_hip_memory_used",
@@ -68,7 +85,7 @@ EXPORTS = [
     "vox_hip_batch_create", "vox_hip_batch_free", "vox_hip_batch_decode", "vox_hip_batch_decode_rows",
     "vox_hip_batch_begin_rows", "vox_hip_batch_finish",
     "vox_hip_batch_read_logits",
-    "vox_hip_batch_stats",
+    "vox_hip_batch_stats", "vox_hip_batch_set_gemv_rows", "vox_hip_batch_gemv_stats", "vox_hip_gemv_rows",
     "vox_hip_stream_state", "vox_hip_stream_set_alt", "vox_hip_stream_read_alts", "vox_hip_sgemm_bf16", "vox_hip_sgemm_q8", "vox_hip_fused_qkv_bf16",
     "vox_hip_fused_ffn_bf16", "vox_hip_encoder_attention", "vox_hip_encoder_full_step",
     "vox_hip_decoder_prefill_step", "vox_hip_decoder_start", "vox_hip_decoder_end",
@@ -118,6 +135,9 @@ def lib():
         "vox_hip_batch_finish": (I, [P]),
         "vox_hip_batch_read_logits": (I, [P, P, fp]),
         "vox_hip_batch_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_batch_set_gemv_rows": (I, [P, I]),
+        "vox_hip_batch_gemv_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_gemv_rows": (I, [I, I, P, fp, I, fp, I]),
         "vox_hip_stream_set_alt": (I, [P, I, F]),
         "vox_hip_stream_read_alts": (I, [P, I, I, ip, fp]),
         "vox_hip_sgemm_bf16": (None, [I, I, I, fp, P, fp]),
@@ -599,6 +619,19 @@ class Batch:
             _err("vox_hip_batch_stats")
         keys = ("calls", "replays", "rows", "captures", "prefill_passes", "prefilled")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def set_gemv_rows(self, max_rows: int) -> int:
+        """vox_hip_batch_set_gemv_rows: steps of up to max_rows slots (0, 1, 2, 4, 8) take the
+        R-row GEMV step.  Returns 0, or -1 with last_error() set (another value, a Q8 model, a
+        begun call)."""
+        return lib().vox_hip_batch_set_gemv_rows(self.h, int(max_rows))
+
+    def gemv_stats(self) -> tuple:
+        """vox_hip_batch_gemv_stats: (max_rows, GEMV step replays, live rows, GEMV captures)"""
+        out = (ctypes.c_longlong * 4)()
+        if lib().vox_hip_batch_gemv_stats(self.h, out) != 0:
+            _err("vox_hip_batch_gemv_stats")
+        return tuple(int(v) for v in out)
 
     def close(self):
         if self.h:
