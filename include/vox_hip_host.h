@@ -92,6 +92,10 @@ void vh_stream_stats(const vh_stream_t *s, vh_stats_t *out);
  * rows still pending */
 int vh_stream_pending(vh_stream_t *s);
 
+/* The model behind a context (for the model-level calls of voxtral_hip.h, such as
+ * vox_hip_model_wmx4_stats); the context keeps owning it. */
+vox_hip_model_t *vh_model(const vh_ctx_t *ctx);
+
 /* Wrap a model the caller created with vox_hip_model_create (Python mirror, servers that
  * load once and share): vh_free on the result leaves the model alone. */
 vh_ctx_t *vh_ctx_wrap(vox_hip_model_t *model, const vox_hip_config_t *cfg, int delay_tokens);

@@ -120,9 +120,54 @@ typedef struct {
 } vox_hip_wpack_stats_t;
 int vox_hip_model_wpack_stats(const vox_hip_model_t *m, vox_hip_wpack_stats_t *out);
 /* Test entry: y[rows] = W x for one bf16 matrix W [rows, K] (host pointers) through the
- * M = 1 GEMV, from wpack13 planes (packed = 1) or from the raw rows.  Returns 1 when the
- * packed kernel ran, 0 when the raw one did (packed = 0 or W outside the window), -1 on error. */
+ * M = 1 GEMV, from wpack13 planes (packed = 1), from the wmx4 plane (packed = 2) or from the
+ * raw rows.  Returns 1 when the wpack13 kernel ran, 2 when the wmx4 kernel ran, 0 when the raw
+ * one did (packed = 0, W outside the wpack13 window, or W refused by the wmx4 scan), -1 on
+ * error. */
 int vox_hip_gemv_wpack(int rows, int K, const uint16_t *W, const float *x, float *y, int packed);
+/* wmx4 (no reference counterpart; opt-in): MXFP4 weight streaming for the single-stream decode
+ * GEMVs, 5 stored bits per weight.
+ *
+ * Format.  A block is 32 consecutive k of one row: 32 e2m1 values ({0, 0.5, 1, 1.5, 2, 3, 4, 6}
+ * with a sign) times one scale 2^e, e = floor(log2(amax)) - 2 for the block's largest
+ * magnitude amax, stored as the e8m0 byte e + 127 (127 for an all-zero block).  Every such
+ * weight is exactly a bf16, so an MXFP4-valued model is an ordinary bf16 model: the kernel
+ * rebuilds the same f32 weight (v_cvt_scalef32_pk_f32_fp4) and runs the bf16 kernel's FMAs in
+ * the same order -- bit-identical outputs on the same (rounded) weights.
+ * Rounding rule (the only lossy step; on the host, never in a kernel): v / 2^e to the nearest
+ * e2m1 value, ties to the even mantissa, saturating at +-6; the sign of zero is kept;
+ * idempotent.  What this rounding does to transcription quality has not been evaluated.
+ * Exponent window: a tensor is streamed as wmx4 only when K % 32 == 0, it holds no Inf, NaN
+ * or subnormal, every block is representable under its own e, and every |e| <= 64: scales
+ * and weights are then normal f32 in [2^-65, 1.5 * 2^66] (csrc/vox_wmx4.h).
+ *
+ * Mode (process-wide, read at vox_hip_model_create; VOX_HIP_WMX4 gives the initial value):
+ *   0 (default)  nothing changes: no scan, no planes, every path and statistic as without it.
+ *   1 (detect)   each bf16 matrix of the single-stream decode step (Q|K|V, wo, W1|W3, W2 per
+ *                decoder layer, and the LM head) that passes the scan also gets a wmx4 plane,
+ *                which the M = 1 GEMV streams in preference to wpack13 or raw.  A tensor that
+ *                fails the scan is treated exactly as in mode 0.
+ *   2 (round)    the host first rounds those matrices (tok_emb included, as LM head and as
+ *                embedding table) by the rule above; the rounded values feed every upload
+ *                (raw rows, fragment-major copies, wpack13, wmx4), so prefill, the batched
+ *                steps and the single-stream step see one model.  Then as mode 1.
+ * Q8 tensors ignore the mode; VOX_HIP_WPACK=0 still streams raw bf16 everywhere.  The wpack13
+ * or raw copies are kept for the paths that need them, so vox_hip_model_wpack_stats reports
+ * what it reports in mode 0 (on the same weights).
+ * vox_hip_set_wmx4 returns 0, or -1 for another mode. */
+int vox_hip_set_wmx4(int mode);
+int vox_hip_wmx4(void);
+typedef struct {
+    int wmx4_tensors;        /* tensors the decode GEMV streams from wmx4 planes */
+    int refused_tensors;     /* tensors scanned and refused (not MXFP4-valued, window, shape) */
+    long long plane_bytes;   /* bytes of the wmx4 planes */
+    long long bf16_bytes;    /* bf16 bytes of the tensors they stand for */
+    double bits_per_weight;  /* plane_bytes * 8 / weights (0 when there are none) */
+    double scan_ms;          /* host time: scanning, */
+    double round_ms;         /* rounding (mode 2), */
+    double pack_ms;          /* packing, laying out and uploading the planes */
+} vox_hip_wmx4_stats_t;
+int vox_hip_model_wmx4_stats(const vox_hip_model_t *m, vox_hip_wmx4_stats_t *out);
 /* Arithmetic of the M > 1 GEMMs (encoder, adapter, prefill; no reference counterpart: the
  * CPU path's cblas_sgemm, voxtral_kernels.c:197-240, is f32): every f32 activation is split
  * into bf16 planes that multiply the exact bf16 weights on MFMA.  planes = 3 (hi + mid + lo,

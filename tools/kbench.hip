@@ -11,6 +11,7 @@
 
 #include "../voxtral.c_amd/csrc/vox_hip_internal.h"
 #include "../voxtral.c_amd/csrc/vox_hip_dev.h"
+#include "../voxtral.c_amd/csrc/vox_wmx4.h"
 #include "../voxtral.c_amd/csrc/vox_wpack.h"
 
 using namespace vox;
@@ -402,6 +403,102 @@ int main(int argc, char** argv) {
                     (double)mainb + sideb);
             }
             for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); }
+        }
+        return 0;
+    }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "wmx4")) {
+        // wmx4 plane (vox_wmx4.h, MXFP4, 5 stored bits per weight) beside the wpack13 planes and
+        // the raw bf16 rows: the five decode GEMV shapes, cold weights (a buffer per layer), the
+        // three formats alternating in one run.  First, per shape, a seeded random matrix is
+        // rounded and packed on the host and the wmx4 and raw kernels' outputs are compared bit
+        // for bit (the LM head at 65536 rows).  VOX_KB_WMX4_SHAPES=w13 (or any list of
+        // qkv,wo,w13,w2,lm) limits the shapes.
+        struct S { const char* n; int pro, epi, K, rows, crows; std::vector<uint16_t*>* w; };
+        const char* only = getenv("VOX_KB_WMX4_SHAPES");
+        CK(hipMemset(state, 0, 16));
+        std::vector<uint16_t*> lm1(1, emb);
+        for (S o : {S{"w13", PRO_NORM_ADA, EPI_SWIGLU, D, 2 * DH, 2 * DH, &w13}, S{"w2", PRO_NONE, EPI_RESID, DH, D, D, &w2},
+                    S{"qkv", PRO_NORM, EPI_QKV, D, DQ + 2 * DKV, DQ + 2 * DKV, &wqkv}, S{"wo", PRO_NONE, EPI_RESID, DQ, D, D, &wo},
+                    S{"lm", PRO_NORM, EPI_LOGITS, D, V, 65536, &lm1}}) {
+            if (only && !strstr(only, o.n)) continue;
+            const int rb = gemv_rowgroup(o.rows), sw = vox_wpack13_side_words(o.K, rb), swiglu = o.epi == EPI_SWIGLU;
+            const int rbm = gemv_rowgroup_mx4(o.rows);
+            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sideb = (size_t)o.rows / rb * 256 * sw * 4;
+            const size_t mxb = (size_t)vox_wmx4_plane_words(o.rows, o.K, rbm) * 4;
+            if (!gemv_ok_mx4(o.rows, o.K)) { printf("%s: not a wmx4 shape\n", o.n); return 1; }
+            auto run = [&](const uint16_t* W, const void* pm, const void* ps, const void* mx, int rows, float* out) {
+                GemvArgs a;
+                memset(&a, 0, sizeof a);
+                a.x = x; a.K = o.K; a.W = W; a.wp_main = pm; a.wp_side = ps; a.wm_plane = mx; a.rows = rows; a.norm_w = normw;
+                a.ada = ada; a.eps = 1e-5f; a.y = out; a.qd = DQ; a.kvd = DKV; a.hd = HD; a.rope = rope; a.state = state;
+                a.Kc = Kc; a.Vc = Vc; a.cap = cap; a.part_val = pv; a.part_idx = pi;
+                CK(launch_gemv(o.pro, o.epi, a, st));
+            };
+            {   // bit check on seeded random weights (uniform, std 1/sqrt(3072)), rounded, and a random x
+                const int rows = o.crows;
+                if (gemv_rowgroup_mx4(rows) != rbm) { printf("%s: check rows use another row group\n", o.n); return 1; }
+                std::vector<uint16_t> hw((size_t)rows * o.K);
+                uint64_t z = 0x9E3779B97F4A7C15ull ^ (uint64_t)o.K * 131 ^ (uint64_t)o.rows;
+                auto rnd = [&] { z = z * 6364136223846793005ull + 1442695040888963407ull; return (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f; };
+                for (auto& v : hw) {
+                    const float f = 0.03125f * rnd();
+                    uint32_t u;
+                    memcpy(&u, &f, 4);
+                    v = (uint16_t)(u >> 16);
+                }
+                vox_wmx4_round_(hw.data(), rows, o.K, hw.data());
+                if (!vox_wmx4_scan_(hw.data(), rows, o.K)) { printf("%s: rounded weights fail the scan\n", o.n); return 1; }
+                std::vector<float> hx(DH);
+                for (auto& v : hx) v = rnd();
+                CK(hipMemcpy(x, hx.data(), DH * 4, hipMemcpyHostToDevice));
+                std::vector<uint32_t> nib((size_t)rows * o.K / 8), pl((size_t)vox_wmx4_plane_words(rows, o.K, rbm));
+                std::vector<uint8_t> scl((size_t)rows * o.K / 32);
+                vox_wmx4_pack_(hw.data(), rows, o.K, nib.data(), scl.data());
+                vox_wmx4_plane_layout_(nib.data(), scl.data(), rows, o.K, rbm, swiglu, pl.data());
+                uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
+                uint32_t* dp = (uint32_t*)dmalloc(pl.size() * 4, 0);
+                CK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+                CK(hipMemcpy(dp, pl.data(), pl.size() * 4, hipMemcpyHostToDevice));
+                const int ny = swiglu ? rows / 2 : rows;
+                float* y2 = (float*)dmalloc((size_t)V * 4, 0);
+                std::vector<float> y0(ny), y1(ny);
+                CK(hipMemset(y, 0, (size_t)ny * 4));
+                run(dw, nullptr, nullptr, nullptr, rows, y);
+                run(dw, nullptr, nullptr, dp, rows, y2);
+                CK(hipStreamSynchronize(st));
+                CK(hipMemcpy(y0.data(), y, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                CK(hipMemcpy(y1.data(), y2, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                double sum = 0;
+                for (float v : y0) sum += fabs((double)v);
+                printf("wmx4 %-4s check: %d-row groups (bf16 %d), %d outputs, mean |y| %.4g: %s\n", o.n, rbm, rb, ny, sum / ny,
+                       memcmp(y0.data(), y1.data(), (size_t)ny * 4) ? "BITS DIFFER" : "same bits");
+                fflush(stdout);
+                CK(hipFree(dw)); CK(hipFree(dp)); CK(hipFree(y2));
+                CK(hipMemsetD32(x, 0x3c003c01u, DH));
+            }
+            // timing: constant planes (values do not matter; every byte 0x78 is a valid scale
+            // and a valid nibble pair), one set of planes per layer
+            const int nl = (int)o.w->size();
+            std::vector<void*> pm(nl), ps(nl), mx(nl);
+            for (int l = 0; l < nl; l++) {
+                pm[l] = dmalloc(mainb, 1);
+                ps[l] = dmalloc(sideb, 0);
+                mx[l] = dmalloc(mxb, 0);
+                CK(hipMemsetD32(mx[l], 0x78787878u, mxb / 4));
+            }
+            const int it = nl == 1 ? iters / 10 + 1 : iters;
+            for (int r = 0; r < 3; r++) {
+                char nm[96];
+                snprintf(nm, sizeof nm, "wmx4 %-4s raw     run %d", o.n, r);
+                add(nm, timeit([&] { run((*o.w)[layer++ % nl], nullptr, nullptr, nullptr, o.rows, y); }, it, st), (double)o.rows * o.K * 2);
+                snprintf(nm, sizeof nm, "wmx4 %-4s wpack13 run %d", o.n, r);
+                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], pm[l], ps[l], nullptr, o.rows, y); }, it, st),
+                    (double)mainb + sideb);
+                snprintf(nm, sizeof nm, "wmx4 %-4s wmx4    run %d", o.n, r);
+                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], nullptr, nullptr, mx[l], o.rows, y); }, it, st),
+                    (double)mxb);
+            }
+            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); CK(hipFree(mx[l])); }
         }
         return 0;
     }

@@ -7,6 +7,7 @@
 // of greedy steps never returns to the host (DESIGN.md "Decoder step").
 #include "../../include/voxtral_hip.h"
 #include "vox_hip_internal.h"
+#include "vox_wmx4.h"
 #include "vox_wpack.h"
 
 #include <hip/hip_runtime.h>
@@ -150,11 +151,17 @@ struct WPackD {
     uint8_t *main, *side;
     int d;
 };
+// wmx4 plane of a bf16 matrix that is MXFP4-valued (vox_wmx4.h), for the single-stream GEMV:
+// 5 bits per weight, decoded without loss.  null: none (the tensor streams as wpack13 or raw).
+struct WMx4D {
+    uint8_t* plane;
+};
 struct DecLayerD {
     uint8_t *wqkv, *wo, *w13, *w2;
     float *sqkv, *so, *s13, *s2;
     float *attn_norm, *ffn_norm;
     WPackD pqkv, po, p13, p2;
+    WMx4D mqkv, mo, m13, m2;
 };
 // the same matrices in MFMA fragment order for the batched step (k_skf; built on first use)
 struct DecFragD {
@@ -186,6 +193,9 @@ struct vox_hip_model {
     WPackD plm;                    // wpack13 copy of the LM head
     int wpack;                     // VOX_HIP_WPACK (default 1), read once at creation
     vox_hip_wpack_stats_t wstats;
+    WMx4D mlm;                     // wmx4 plane of the LM head
+    int wmx4;                      // vox_hip_wmx4() at creation (0 off, 1 detect, 2 round)
+    vox_hip_wmx4_stats_t mstats;
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -314,6 +324,84 @@ static void wpack_args(GemvArgs& a, const WPackD& P) {
     a.wp_d = P.d;
 }
 
+// wmx4 mode of models created from now on (include/voxtral_hip.h); VOX_HIP_WMX4 gives the
+// initial value
+static int g_wmx4 = -1;
+static int wmx4_mode() {
+    if (g_wmx4 < 0) {
+        const char* e = getenv("VOX_HIP_WMX4");
+        const int v = e ? atoi(e) : 0;
+        g_wmx4 = v == 1 || v == 2 ? v : 0;
+    }
+    return g_wmx4;
+}
+extern "C" int vox_hip_set_wmx4(int mode) {
+    if (mode < 0 || mode > 2) return set_err("wmx4 mode: 0, 1 or 2 (got %d)", mode);
+    g_wmx4 = mode;
+    return 0;
+}
+extern "C" int vox_hip_wmx4(void) { return wmx4_mode(); }
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Mode 2: the MXFP4 rounding of a host bf16 matrix (vox_wmx4_round), into `out`
+static void wmx4_round_host(vox_hip_wmx4_stats_t& S, const void* w, int rows, int K, std::vector<uint16_t>& out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    out.resize((size_t)rows * K);
+    const uint16_t* in = (const uint16_t*)w;
+    par_range(rows, [&](long long r0, long long r1) { vox_wmx4_round_rows(in, r0, r1, K, out.data()); });
+    S.round_ms += ms_since(t0);
+}
+
+// The wmx4 plane of a bf16 matrix whose rows are in device order (host copy), for the wmx4
+// row groups of this shape.  A tensor that fails vox_wmx4_scan, or of a shape the wmx4
+// instances do not take, gets none: M->plane stays null and the tensor streams as before.
+static int wmx4_make(int enabled, vox_hip_wmx4_stats_t& S, WMx4D* M, const uint16_t* w, int rows, int K, int swiglu) {
+    M->plane = nullptr;
+    if (!enabled) return 0;
+    if (!w) return set_err("null weight pointer");
+    const size_t n = (size_t)rows * K;
+    auto t0 = std::chrono::steady_clock::now();
+    std::atomic<int> ok{gemv_ok_mx4(rows, K) ? 1 : 0};
+    if (ok) {
+        // every thread starts at the head of its range and stops at its first failing block
+        par_range(rows, [&](long long r0, long long r1) {
+            for (long long r = r0; r < r1 && ok.load(std::memory_order_relaxed); r++)
+                if (!vox_wmx4_scan_rows(w, r, r + 1, K)) ok = 0;
+        });
+    }
+    S.scan_ms += ms_since(t0);
+    if (!ok) {
+        S.refused_tensors++;
+        return 0;
+    }
+    t0 = std::chrono::steady_clock::now();
+    const int rb = gemv_rowgroup_mx4(rows);
+    const size_t words = (size_t)vox_wmx4_plane_words(rows, K, rb);
+    std::vector<uint32_t> nib(n / 8), plane(words);
+    std::vector<uint8_t> scl(n / VOX_WMX4_BLOCK);
+    par_range(rows, [&](long long r0, long long r1) { vox_wmx4_pack_rows(w, r0, r1, K, nib.data(), scl.data()); });
+    par_range(rows / rb, [&](long long g0, long long g1) {
+        vox_wmx4_plane_groups(nib.data(), scl.data(), g0, g1, K, rb, swiglu, plane.data());
+    });
+    CK(dalloc(&M->plane, words * 4));
+    if (upload(M->plane, plane.data(), words * 4)) return -1;
+    S.wmx4_tensors++;
+    S.plane_bytes += (long long)words * 4;
+    S.bf16_bytes += (long long)n * 2;
+    S.bits_per_weight = S.plane_bytes * 8.0 / (S.bf16_bytes / 2);
+    S.pack_ms += ms_since(t0);
+    return 0;
+}
+// (VOX_HIP_WPACK=0 streams raw rows everywhere: such a model builds no plane)
+static void wmx4_args(GemvArgs& a, const WMx4D& M) { a.wm_plane = M.plane; }
+// blocks of the single-stream LM head launch (its argmax partials)
+static int lm_head_grid(const vox_hip_model* m) {
+    return m->mlm.plane ? gemv_grid_mx4(m->c.vocab) : gemv_grid(m->c.vocab);
+}
+
 static int model_update_ada(vox_hip_model_t* m) {
     // vox_update_time_conditioning (voxtral.c:31-80)
     const vox_hip_config_t& c = m->c;
@@ -404,6 +492,9 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     m->rope_enc = m->rope_dec = nullptr;
     memset(&m->plm, 0, sizeof m->plm);
     memset(&m->wstats, 0, sizeof m->wstats);
+    memset(&m->mlm, 0, sizeof m->mlm);
+    memset(&m->mstats, 0, sizeof m->mstats);
+    m->wmx4 = wmx4_mode();
     {
         // VOX_HIP_WPACK=0: every GEMV weight stays raw bf16 (same-machine A/B runs)
         const char* e = getenv("VOX_HIP_WPACK");
@@ -455,10 +546,24 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     TRY(upload_mat(&m->ad0, &m->ad0_s, w->ad0, w->ad0_s, DD, (size_t)ED * c.downsample));
     TRY(upload_mat(&m->ad1, &m->ad1_s, w->ad1, w->ad1_s, DD, DD));
     // decoder
-    TRY(upload_mat(&m->tok_emb, &m->tok_emb_s, w->tok_emb, w->tok_emb_s, c.vocab, DD));
+    // wmx4 mode 2: the bf16 matrices of the decode step are rounded to MXFP4 values here, on
+    // the host, before anything is uploaded: raw rows, fragment-major copies, wpack13 and wmx4
+    // planes all hold the one rounded model (Q8 tensors are left alone)
+    std::vector<uint16_t> rnd[7];
+    auto rounded = [&](int slot, const void* src, const float* scale, int rows, int K) -> const void* {
+        if (m->wmx4 != 2 || scale || !src) return src;
+        wmx4_round_host(m->mstats, src, rows, K, rnd[slot]);
+        return rnd[slot].data();
+    };
+    const void* h_tok = rounded(0, w->tok_emb, w->tok_emb_s, c.vocab, DD);
+    TRY(upload_mat(&m->tok_emb, &m->tok_emb_s, h_tok, w->tok_emb_s, c.vocab, DD));
     // wpack13 copies of the bf16 matrices the single-stream decode step streams (made here,
     // not in the first step); the raw copies stay for every other path
-    if (!w->tok_emb_s) TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)w->tok_emb, c.vocab, DD, 0));
+    if (!w->tok_emb_s) {
+        TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0));
+        TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &m->mlm, (const uint16_t*)h_tok, c.vocab, DD, 0));
+    }
+    rnd[0] = std::vector<uint16_t>();
     std::vector<uint16_t> hrows;  // a matrix in device row order (merged Q|K|V, interleaved W1|W3)
     m->dec.resize(c.dec_layers);
     m->ada_down.resize(c.dec_layers);
@@ -466,29 +571,45 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     for (int l = 0; l < c.dec_layers; l++) {
         DecLayerD& L = m->dec[l];
         memset(&L, 0, sizeof L);
-        TRY(upload_qkv(&L.wqkv, &L.sqkv, w->dec_wq[l], SCL(dec_wq_s, l), w->dec_wk[l], SCL(dec_wk_s, l),
-                       w->dec_wv[l], SCL(dec_wv_s, l), DQ, DKV, DD));
-        TRY(upload_mat(&L.wo, &L.so, w->dec_wo[l], SCL(dec_wo_s, l), DD, DQ));
-        TRY(upload_w13(&L.w13, &L.s13, w->dec_w1[l], SCL(dec_w1_s, l), w->dec_w3[l], SCL(dec_w3_s, l), DH, DD));
-        TRY(upload_mat(&L.w2, &L.s2, w->dec_w2[l], SCL(dec_w2_s, l), DD, DH));
+        // blocks lie within a row, so rounding wq, wk, wv (w1, w3) one by one rounds Q|K|V (W1|W3)
+        const void* h_wq = rounded(0, w->dec_wq[l], SCL(dec_wq_s, l), DQ, DD);
+        const void* h_wk = rounded(1, w->dec_wk[l], SCL(dec_wk_s, l), DKV, DD);
+        const void* h_wv = rounded(2, w->dec_wv[l], SCL(dec_wv_s, l), DKV, DD);
+        const void* h_wo = rounded(3, w->dec_wo[l], SCL(dec_wo_s, l), DD, DQ);
+        const void* h_w1 = rounded(4, w->dec_w1[l], SCL(dec_w1_s, l), DH, DD);
+        const void* h_w3 = rounded(5, w->dec_w3[l], SCL(dec_w3_s, l), DH, DD);
+        const void* h_w2 = rounded(6, w->dec_w2[l], SCL(dec_w2_s, l), DD, DH);
+        TRY(upload_qkv(&L.wqkv, &L.sqkv, h_wq, SCL(dec_wq_s, l), h_wk, SCL(dec_wk_s, l), h_wv, SCL(dec_wv_s, l), DQ,
+                       DKV, DD));
+        TRY(upload_mat(&L.wo, &L.so, h_wo, SCL(dec_wo_s, l), DD, DQ));
+        TRY(upload_w13(&L.w13, &L.s13, h_w1, SCL(dec_w1_s, l), h_w3, SCL(dec_w3_s, l), DH, DD));
+        TRY(upload_mat(&L.w2, &L.s2, h_w2, SCL(dec_w2_s, l), DD, DH));
         if (!L.sqkv) {
             hrows.resize((size_t)(DQ + 2 * DKV) * DD);
-            memcpy(hrows.data(), w->dec_wq[l], (size_t)DQ * DD * 2);
-            memcpy(hrows.data() + (size_t)DQ * DD, w->dec_wk[l], (size_t)DKV * DD * 2);
-            memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, w->dec_wv[l], (size_t)DKV * DD * 2);
+            memcpy(hrows.data(), h_wq, (size_t)DQ * DD * 2);
+            memcpy(hrows.data() + (size_t)DQ * DD, h_wk, (size_t)DKV * DD * 2);
+            memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, h_wv, (size_t)DKV * DD * 2);
             TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
         }
-        if (!L.so) TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)w->dec_wo[l], DD, DQ, 0));
+        if (!L.so) {
+            TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mo, (const uint16_t*)h_wo, DD, DQ, 0));
+        }
         if (!L.s13) {
             hrows.resize((size_t)2 * DH * DD);
             const size_t grp = (size_t)16 * DD;
             for (int g = 0; g < DH / 16; g++) {
-                memcpy(hrows.data() + 2 * g * grp, (const uint16_t*)w->dec_w1[l] + g * grp, grp * 2);
-                memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)w->dec_w3[l] + g * grp, grp * 2);
+                memcpy(hrows.data() + 2 * g * grp, (const uint16_t*)h_w1 + g * grp, grp * 2);
+                memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)h_w3 + g * grp, grp * 2);
             }
             TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m13, hrows.data(), 2 * DH, DD, 1));
         }
-        if (!L.s2) TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)w->dec_w2[l], DD, DH, 0));
+        if (!L.s2) {
+            TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m2, (const uint16_t*)h_w2, DD, DH, 0));
+        }
         TRYH(dalloc(&L.attn_norm, DD));
         TRY(upload(L.attn_norm, w->dec_attn_norm[l], DD * 4));
         TRYH(dalloc(&L.ffn_norm, DD));
@@ -521,8 +642,9 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
         dfree(L.sqkv); dfree(L.so); dfree(L.s13); dfree(L.s2);
         dfree(L.attn_norm); dfree(L.ffn_norm);
         for (WPackD* P : {&L.pqkv, &L.po, &L.p13, &L.p2}) { dfree(P->main); dfree(P->side); }
+        for (WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) dfree(M->plane);
     }
-    dfree(m->plm.main); dfree(m->plm.side);
+    dfree(m->plm.main); dfree(m->plm.side); dfree(m->mlm.plane);
     for (auto& F : m->dfrag) {
         dfree(F.wqkv); dfree(F.wo); dfree(F.w13); dfree(F.w2);
     }
@@ -539,6 +661,12 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
 extern "C" int vox_hip_model_wpack_stats(const vox_hip_model_t* m, vox_hip_wpack_stats_t* out) {
     if (!m || !out) return set_err("wpack_stats: null argument");
     *out = m->wstats;
+    return 0;
+}
+
+extern "C" int vox_hip_model_wmx4_stats(const vox_hip_model_t* m, vox_hip_wmx4_stats_t* out) {
+    if (!m || !out) return set_err("wmx4_stats: null argument");
+    *out = m->mstats;
     return 0;
 }
 
@@ -2032,6 +2160,7 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         a.rope = state ? m->rope_dec : rope_row - (size_t)pos * hd;
         a.Kc = Kc; a.Vc = Vc; a.cap = s->dcap; a.kv16 = s->kv16;
         wpack_args(a, L.pqkv);
+        wmx4_args(a, L.mqkv);
         CK(launch_gemv(PRO_NORM, EPI_QKV, a, st));
         // attention over the last min(pos+1, window) keys (decoder.c:724-733)
         CK(launch_attn_decode(hd, s->qd_, Kc, Vc, s->dcap, state, pos, c.dec_window, scale, H, KVH,
@@ -2040,12 +2169,14 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         memset(&a, 0, sizeof a);
         a.x = s->attd; a.K = DQ; a.W = L.wo; a.wscale = L.so; a.rows = DD; a.y = s->xd;
         wpack_args(a, L.po);
+        wmx4_args(a, L.mo);
         CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up (decoder.c:742-758)
         memset(&a, 0, sizeof a);
         a.x = s->xd; a.K = DD; a.W = L.w13; a.wscale = L.s13; a.rows = 2 * DH; a.norm_w = L.ffn_norm;
         a.ada = m->ada_scale + (size_t)l * DD; a.eps = c.dec_eps; a.y = s->gated;
         wpack_args(a, L.p13);
+        wmx4_args(a, L.m13);
         // profiling: HIP events recorded by the W1|W3 launch's own dispatch (eager steps)
         const bool gprof = s->profiling && state && !s->capturing && (int)s->pev.size() == 2 * c.dec_layers;
         if (gprof) CK(launch_gemv_timed(PRO_NORM_ADA, EPI_SWIGLU, a, s->pev[2 * l], s->pev[2 * l + 1], st));
@@ -2054,6 +2185,7 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         memset(&a, 0, sizeof a);
         a.x = s->gated; a.K = DH; a.W = L.w2; a.wscale = L.s2; a.rows = DD; a.y = s->xd;
         wpack_args(a, L.p2);
+        wmx4_args(a, L.m2);
         CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
     }
     return enqueue_lm_head(s, state);
@@ -2070,6 +2202,7 @@ static int enqueue_lm_head(vox_hip_stream_t* s, const int* state) {
     a.eps = c.dec_eps; a.y = s->logits; a.part_val = s->pval; a.part_idx = s->pidx;
     a.part_alt = s->part_alt;
     wpack_args(a, m->plm);
+    wmx4_args(a, m->mlm);
     CK(launch_gemv(PRO_NORM, (state && s->n_alt > 1) ? EPI_LOGITS_ALT : EPI_LOGITS, a, st));
     return 0;
 }
@@ -2090,7 +2223,7 @@ static int graph_index(const vox_hip_stream_t* s, int ctx) {
 static int enqueue_graph_step(vox_hip_stream_t* s, int splits) {
     const vox_hip_config_t& c = s->m->c;
     if (enqueue_step_layers(s, s->state, 0, nullptr, splits)) return -1;
-    CK(launch_argmax_final(s->pval, s->pidx, gemv_grid(c.vocab), s->state, s->tokens, s->tokens_cap,
+    CK(launch_argmax_final(s->pval, s->pidx, lm_head_grid(s->m), s->state, s->tokens, s->tokens_cap,
                            s->adapter, s->adapter_cap, s->m->tok_emb, s->m->tok_emb_s, c.dec_dim, s->xd,
                            s->part_alt, s->n_alt > 1 ? s->alts : nullptr, c.vocab, s->st));
     return 0;
@@ -2487,8 +2620,9 @@ static int twin_sgemm(int M, int N, int K, const float* A, const void* B, const 
 }
 
 // Test entry: y = W x for one bf16 matrix [rows, K] through k_gemv's STORE instance, from the
-// wpack13 planes (packed = 1) or from the raw rows.  Returns 1 when the packed instance ran,
-// 0 when the raw one did (packed = 0, or W outside the format's window), -1 on error.
+// wpack13 planes (packed = 1), the wmx4 plane (packed = 2) or the raw rows.  Returns 1 when the
+// wpack13 instance ran, 2 when the wmx4 instance ran, 0 when the raw one did (packed = 0, or W
+// outside the format's window / not MXFP4-valued), -1 on error.
 extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const float* x, float* y, int packed) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
     if (!W || !x || !y) return set_err("gemv_wpack: null argument");
@@ -2496,28 +2630,34 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
     if (twin_init()) return -1;
     uint8_t* dW = nullptr;
     float *dx = nullptr, *dy = nullptr;
+    if (packed < 0 || packed > 2) return set_err("gemv_wpack: packed must be 0, 1 or 2 (got %d)", packed);
     WPackD P = {nullptr, nullptr, 0};
+    WMx4D M = {nullptr};
     vox_hip_wpack_stats_t S;
+    vox_hip_wmx4_stats_t MS;
     memset(&S, 0, sizeof S);
+    memset(&MS, 0, sizeof MS);
     auto run = [&]() -> int {
         CK(dalloc(&dW, (size_t)rows * K * 2));
         CK(dalloc(&dx, (size_t)K));
         CK(dalloc(&dy, (size_t)rows));
         if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)K * 4)) return -1;
-        if (wpack_make(packed, S, &P, W, rows, K, 0)) return -1;
+        if (wpack_make(packed == 1, S, &P, W, rows, K, 0)) return -1;
+        if (wmx4_make(packed == 2, MS, &M, W, rows, K, 0)) return -1;
         GemvArgs a;
         memset(&a, 0, sizeof a);
         a.x = dx; a.K = K; a.W = dW; a.rows = rows; a.y = dy;
         wpack_args(a, P);
+        a.wm_plane = M.plane;
         CK(launch_gemv(PRO_NONE, EPI_STORE, a, g_twin_st));
         CK(hipStreamSynchronize(g_twin_st));
         CK(hipMemcpy(y, dy, (size_t)rows * 4, hipMemcpyDeviceToHost));
         return 0;
     };
     const int rc = run();
-    const int was_packed = P.main != nullptr;
-    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side);
-    return rc ? -1 : was_packed;
+    const int ran = M.plane ? 2 : P.main ? 1 : 0;
+    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side); dfree(M.plane);
+    return rc ? -1 : ran;
 }
 
 // Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
@@ -2731,7 +2871,7 @@ extern "C" int vox_hip_decoder_full_step(vox_hip_stream_t* s, const float* rope_
     int* tmp_state = s->twin_state;
     int st4[4] = {0, 0, 0, 0};
     CK(hipMemcpyAsync(tmp_state, st4, sizeof st4, hipMemcpyHostToDevice, s->st));
-    CK(launch_argmax_final(s->pval, s->pidx, gemv_grid(c.vocab), tmp_state, nullptr, 0, nullptr, 0,
+    CK(launch_argmax_final(s->pval, s->pidx, lm_head_grid(s->m), tmp_state, nullptr, 0, nullptr, 0,
                            nullptr, nullptr, c.dec_dim, nullptr, nullptr, nullptr, c.vocab, s->st));
     CK(hipMemcpyAsync(st4, tmp_state, sizeof st4, hipMemcpyDeviceToHost, s->st));
     if (logits) CK(hipMemcpyAsync(logits, s->logits, (size_t)c.vocab * 4, hipMemcpyDeviceToHost, s->st));

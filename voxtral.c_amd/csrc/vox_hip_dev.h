@@ -186,6 +186,29 @@ __device__ __forceinline__ float dot8h(uint4 w, uint32_t sd, int q, float4 a, fl
     return acc;
 }
 
+// dot of 8 wmx4 weights (vox_wmx4.h: one dword of e2m1 nibbles, weight k in bits 4k .. 4k + 3,
+// and the block's e8m0 scale byte) with 8 f32 activations.  v_cvt_scalef32_pk_f32_fp4 turns
+// byte `sel` of the dword and the scale 2^(byte - 127), given as the f32 byte << 23, into the
+// two f32 weights e2m1 * scale: exact, and the f32 that the bf16 weight widens to, so every
+// FMA is dot8's, in dot8's order.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float dot8m4(uint32_t w, uint32_t scale_byte, float4 a, float4 b, float acc) {
+    const float sc = __uint_as_float(scale_byte << 23);
+    const f32x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 0);
+    const f32x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 1);
+    const f32x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 2);
+    const f32x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 3);
+    acc = fmaf(p0.x, a.x, acc);
+    acc = fmaf(p0.y, a.y, acc);
+    acc = fmaf(p1.x, a.z, acc);
+    acc = fmaf(p1.y, a.w, acc);
+    acc = fmaf(p2.x, b.x, acc);
+    acc = fmaf(p2.y, b.y, acc);
+    acc = fmaf(p3.x, b.z, acc);
+    acc = fmaf(p3.y, b.w, acc);
+    return acc;
+}
+
 // dot of 16 int8 weights (one uint4, Q8 rows) with 16 f32 activations: each byte is
 // sign-extended and converted exactly (q8_matvec_fused, voxtral_kernels.c:277-318)
 __device__ __forceinline__ float i8f(uint32_t w, int b) { return (float)((int32_t)(w << (24 - 8 * b)) >> 24); }

@@ -13,8 +13,9 @@ constexpr int ALT_TEXT_MIN = 1000;   // TOKEN_TEXT_MIN (voxtral.c:399)
 constexpr int ALT_PART = 10;         // per-block alt partial: m, s, 4 values, 4 ids
 constexpr int ALT_REC = 8;           // per-step alt record: p_best, (id, p) x 3, pad
 enum { PRO_NONE = 0, PRO_NORM = 1, PRO_NORM_ADA = 2 };
-// k_gemv weight formats: bf16 rows, Q8 rows + row scales, wpack13 planes (vox_wpack.h)
-enum { WF_BF16 = 0, WF_Q8 = 1, WF_P13 = 2 };
+// k_gemv weight formats: bf16 rows, Q8 rows + row scales, wpack13 planes (vox_wpack.h), wmx4
+// plane (vox_wmx4.h)
+enum { WF_BF16 = 0, WF_Q8 = 1, WF_P13 = 2, WF_MX4 = 3 };
 
 constexpr int GEMV_MAX_BLOCKS = 1024;  // 4 blocks of 256 threads per CU on 256 CUs
 
@@ -28,6 +29,9 @@ struct GemvArgs {
     const void* wp_main = nullptr;
     const void* wp_side = nullptr;
     int wp_d = 0;
+    // wmx4 copy of W (vox_wmx4.h; null: none), laid out for gemv_rowgroup_mx4(rows); streamed
+    // in preference to the wpack13 planes
+    const void* wm_plane = nullptr;
     int rows;              // output rows streamed (2*hidden for SWIGLU)
     const float* norm_w;   // PRO_NORM*: RMSNorm weight [K]
     const float* ada;      // PRO_NORM_ADA: ada_scale row [K]
@@ -113,6 +117,9 @@ constexpr int ARGB = 64;                // argmax partial blocks per row
 
 int gemv_grid(int rows);
 int gemv_rowgroup(int rows);  // rows per k_gemv group (the wpack13 side plane is laid out for it)
+int gemv_rowgroup_mx4(int rows);  // rows per group of the wmx4 instances (the wmx4 plane is laid out for it)
+int gemv_grid_mx4(int rows);      // blocks of a wmx4 launch (the LM head's argmax partials)
+bool gemv_ok_mx4(int rows, int K);  // shapes the wmx4 instances accept
 bool gemv_ok(int rows, int K, int q8);  // shapes launch_gemv accepts (rows, K multiple of the chunk)
 int attn_maxch(int window);      // decode-attention partials per head (64-key blocks)
 int attn_maxsplits(int window);  // 256-key spans of a window (graph buckets)

@@ -724,14 +724,21 @@ __device__ __forceinline__ void alt_row(float v, int r, float& am, float& as, fl
         as += expf(v - am);
     }
     if (r >= ALT_TEXT_MIN && v > tv[3]) {
-        int k = 3;
-        while (k > 0 && v > tv[k - 1]) {
-            tv[k] = tv[k - 1];
-            ti[k] = ti[k - 1];
-            k--;
+        // v replaces the smallest and rises past every strictly smaller entry; the entries
+        // above it are sorted, so no later pair swaps.  Static indices only: a run-time index
+        // into tv / ti put both arrays in scratch (48 B per lane).
+        tv[3] = v;
+        ti[3] = r;
+#pragma unroll
+        for (int k = 3; k > 0; k--) {
+            const bool up = tv[k] > tv[k - 1];
+            const float fv = tv[k];
+            const int fi = ti[k];
+            tv[k] = up ? tv[k - 1] : fv;
+            ti[k] = up ? ti[k - 1] : fi;
+            tv[k - 1] = up ? fv : tv[k - 1];
+            ti[k - 1] = up ? fi : ti[k - 1];
         }
-        tv[k] = v;
-        ti[k] = r;
     }
 }
 
@@ -816,11 +823,24 @@ __device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int vof
     }
 }
 
+// wmx4 plane (WF_MX4, vox_wmx4.h): one record of RW = RB + ceil(RB / 4) dwords per (group,
+// chunk): the RB rows' nibble dwords of that chunk and their blocks' e8m0 scale bytes, so the
+// thread that owns a chunk fetches a group's weights with one record load per K round (the
+// wave's 64 records are contiguous).  dot8m4 rebuilds each weight as the exact f32 of the bf16
+// weight and runs dot8's FMAs: every output is bit-identical to the bf16 instance's.
+template <int RW, int KQ>
+__device__ __forceinline__ void gemv_load_mx4(__amdgpu_buffer_rsrc_t W, int soff, const int (&voff)[KQ],
+                                              uint32_t (&mr)[KQ][RW]) {
+#pragma unroll
+    for (int j = 0; j < KQ; j++) gemv_load_side<RW>(W, voff[j], soff, mr[j]);
+}
+
 template <int PRO, int EPI, int RB, int KQ, int WF>
 __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
-    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13;
+    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13, WM = WF == WF_MX4;
     constexpr int XPC = WQ8 ? 4 : 2;  // float4 of x per 16-B chunk
     constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
+    constexpr int RW = RB + (RB + 3) / 4;           // wmx4 record dwords per (group, chunk)
     __shared__ float red[2][4][RB];
     __shared__ float sred[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -831,13 +851,16 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
     const int G = gridDim.x;
     int g = blockIdx.x;
     int rows[RB];
-    uint4 wv[KQ][RB];
+    uint4 wv[WM ? 1 : KQ][RB];
+    uint32_t mr[WM ? KQ : 1][RW];
     float wsc[RB];
     GEMV_STAMP(0);
     bool first_group = true;
-    const int rowbytes = WP ? KC * 12 : K * (WQ8 ? 1 : 2);
-    void* const wbase = const_cast<void*>(WP ? a.wp_main : a.W);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, a.rows * rowbytes, 0x00020000);
+    // wmx4: "rowbytes" is a group's bytes (KC records), the plane ngroups of them
+    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * (WQ8 ? 1 : 2);
+    void* const wbase = const_cast<void*>(WM ? a.wm_plane : WP ? a.wp_main : a.W);
+    const __amdgpu_buffer_rsrc_t wrs =
+        __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
     void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
@@ -850,12 +873,13 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 #pragma unroll
     for (int j = 0; j < KQ; j++) {
         const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * (WP ? 12 : 16);
+        voff[j] = (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
     }
     // first group's weights are independent of x: issue them before the prologue
     gemv_rows<EPI, RB>(g, rows);
     if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);  // first: every chunk needs it
-    gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
+    if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
+    else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
     if ((EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT) && WQ8 && wave == 0) {
 #pragma unroll
         for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
@@ -995,7 +1019,8 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
         for (int j = 0; j < KQ; j++)
 #pragma unroll
             for (int i = 0; i < RB; i++) {
-                if (WQ8) acc[i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[j]), acc[i]);
+                if constexpr (WM) acc[i] = dot8m4(mr[j][i], (mr[j][RB + (i >> 2)] >> (8 * (i & 3))) & 0xffu, xr[j][0], xr[j][1], acc[i]);
+                else if (WQ8) acc[i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[j]), acc[i]);
                 else if (WP) acc[i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[j][0], xr[j][1], acc[i]);
                 else acc[i] = dot8(wv[j][i], xr[j][0], xr[j][XPC - 1], acc[i]);
             }
@@ -1021,7 +1046,8 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
             const bool more = g < ngroups;
             gemv_rows<EPI, RB>(more ? g : 0, rows);
             if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
-            gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
+            if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
+            else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
             if (LOGIT && WQ8 && wave == 0) {
 #pragma unroll
                 for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
@@ -3585,19 +3611,29 @@ static int gemv_rb(int rows) {
 }
 
 int gemv_rowgroup(int rows) { return gemv_rb(rows); }
+// wmx4 instances: a 2-row group's record would carry half a dword of padding (6 bits per
+// weight instead of 5) and a quarter of a bf16 group's bytes, so they take at least 4 rows
+// where the row count allows it; each row's bits do not depend on the group size
+static int gemv_rb_mx4(int rows) {
+    const int rb = gemv_rb(rows);
+    return rb < 4 && rows % 4 == 0 ? 4 : rb;
+}
+int gemv_rowgroup_mx4(int rows) { return gemv_rb_mx4(rows); }
 
 VOX_KB_KNOB(g_gemv_maxb, 0);  // tools/kbench knob: grid cap other than GEMV_MAX_BLOCKS (no LM head)
-int gemv_grid(int rows) {
+static int gemv_grid_rb(int rows, int rb) {
     // the largest divisor of the group count that fits 4 blocks per CU: every block then
     // runs the same number of groups (no tail); tools/kbench VOX_KB_ONLY=grid: 1536-2304
     // blocks were slower on every decode shape, bf16 and Q8 (profiles/r3_kbench_gemv_grid.txt)
-    const int ng = rows / gemv_rb(rows), maxb = g_gemv_maxb ? g_gemv_maxb : GEMV_MAX_BLOCKS;
+    const int ng = rows / rb, maxb = g_gemv_maxb ? g_gemv_maxb : GEMV_MAX_BLOCKS;
     int best = 1;
     for (int gsz = 1; gsz <= maxb && gsz <= ng; gsz++)
         if (ng % gsz == 0) best = gsz;
     if (best < 256 && ng > maxb) best = maxb;  // no good divisor: accept a tail
     return best;
 }
+int gemv_grid(int rows) { return gemv_grid_rb(rows, gemv_rb(rows)); }
+int gemv_grid_mx4(int rows) { return gemv_grid_rb(rows, gemv_rb_mx4(rows)); }
 
 template <int P, int E, int RB, int Q8>
 static const void* gemv_fn(int kq) {
@@ -3641,8 +3677,9 @@ template <int P, int E, int RB>
 static hipError_t gemv_q(const GemvArgs& a, int grid, hipStream_t st) {
     if (a.wscale) return gemv_k<P, E, RB, WF_Q8>(a, grid, st);
     if constexpr (gemv_p13<P, E>) {
+        if (a.wm_plane) return gemv_k<P, E, RB, WF_MX4>(a, grid, st);
         if (a.wp_main) return gemv_k<P, E, RB, WF_P13>(a, grid, st);
-    } else if (a.wp_main) {
+    } else if (a.wp_main || a.wm_plane) {
         return hipErrorInvalidValue;
     }
     return gemv_k<P, E, RB, WF_BF16>(a, grid, st);
@@ -3651,16 +3688,22 @@ template <int P, int E, int RB>
 static const void* gemv_fn_q(const GemvArgs& a, int kq) {
     if (a.wscale) return gemv_fn<P, E, RB, WF_Q8>(kq);
     if constexpr (gemv_p13<P, E>) {
+        if (a.wm_plane) return gemv_fn<P, E, RB, WF_MX4>(kq);
         if (a.wp_main) return gemv_fn<P, E, RB, WF_P13>(kq);
-    } else if (a.wp_main) {
+    } else if (a.wp_main || a.wm_plane) {
         return nullptr;
     }
     return gemv_fn<P, E, RB, WF_BF16>(kq);
 }
 
 // kernel instance launch_gemv would use (tools, occupancy queries)
+// row group and grid of a launch: the wmx4 plane has its own group size
+static bool gemv_is_mx4(const GemvArgs& a) { return a.wm_plane && !a.wscale; }
+static int gemv_rb_of(const GemvArgs& a) { return gemv_is_mx4(a) ? gemv_rb_mx4(a.rows) : gemv_rb(a.rows); }
+static int gemv_grid_of(const GemvArgs& a) { return gemv_grid_rb(a.rows, gemv_rb_of(a)); }
+
 const void* gemv_kernel(int pro, int epi, const GemvArgs& a) {
-    const int rb = gemv_rb(a.rows);
+    const int rb = gemv_rb_of(a);
     const int kq = ((a.wscale ? a.K >> 4 : a.K >> 3) + 255) / 256;
 #define GEMV_FN(P, E)         \
     if (pro == P && epi == E) \
@@ -3681,7 +3724,7 @@ hipError_t launch_gemv_timed(int pro, int epi, const GemvArgs& a, hipEvent_t sta
     if (!fn) return hipErrorInvalidValue;
     GemvArgs args = a;
     void* kargs[] = {&args};
-    return hipExtLaunchKernel(fn, dim3(gemv_grid(a.rows)), dim3(256), kargs, 0, st, start, stop, 0);
+    return hipExtLaunchKernel(fn, dim3(gemv_grid_of(a)), dim3(256), kargs, 0, st, start, stop, 0);
 }
 
 // the shapes launch_gemv accepts: whole 16-B chunks per row, whole row groups, and at most
@@ -3691,11 +3734,20 @@ bool gemv_ok(int rows, int K, int q8) {
     return rows > 0 && K > 0 && K % (q8 ? 16 : 8) == 0 && rows % gemv_rb(rows) == 0 && (kc + 255) / 256 <= 5;
 }
 
+// the shapes the wmx4 instances accept: gemv_ok's, whole 32-weight blocks, whole wmx4 row
+// groups, and a plane that a 32-bit buffer offset reaches
+bool gemv_ok_mx4(int rows, int K) {
+    if (!gemv_ok(rows, K, 0) || K % 32 || rows % gemv_rb_mx4(rows)) return false;
+    const int rb = gemv_rb_mx4(rows);
+    return (long long)rows / rb * (K / 8) * (rb + (rb + 3) / 4) * 4 < (1LL << 31);
+}
+
 hipError_t launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t st) {
-    const int rb = gemv_rb(a.rows);
+    const int rb = gemv_rb_of(a);
     if (!gemv_ok(a.rows, a.K, a.wscale != nullptr)) return hipErrorInvalidValue;
+    if (gemv_is_mx4(a) && !gemv_ok_mx4(a.rows, a.K)) return hipErrorInvalidValue;
     if (epi == EPI_QKV_BIAS && !a.bias) return hipErrorInvalidValue;
-    const int grid = gemv_grid(a.rows);
+    const int grid = gemv_grid_of(a);
 #define GEMV_CASE(P, E) \
     if (pro == P && epi == E)                                                            \
         return rb == 8 ? gemv_q<P, E, 8>(a, grid, st) : rb == 2 ? gemv_q<P, E, 2>(a, grid, st) : gemv_q<P, E, 4>(a, grid, st);

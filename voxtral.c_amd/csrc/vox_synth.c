@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "vox_wmx4.h"
 #include "vox_wpack.h"
 
 static inline uint64_t splitmix64(uint64_t x) {
@@ -114,4 +115,20 @@ void vox_wpack13_unpack(const uint32_t *main, const uint8_t *side, long long row
 int vox_wpack13_side_words_of(long long K, int rb) { return vox_wpack13_side_words(K, rb); }
 void vox_wpack13_side_layout(const uint8_t *side, long long rows, long long K, int rb, int swiglu, uint32_t *out) {
     vox_wpack13_side_layout_(side, rows, K, rb, swiglu, out);
+}
+
+/* wmx4 (vox_wmx4.h): the rounding, scan, pack / unpack and plane layout the engine's loader
+ * uses, exported for vox_weights.quantize_mxfp4 and the CPU tests. */
+void vox_wmx4_round(const uint16_t *in, long long rows, long long K, uint16_t *out) { vox_wmx4_round_(in, rows, K, out); }
+int vox_wmx4_scan(const uint16_t *w, long long rows, long long K) { return vox_wmx4_scan_(w, rows, K); }
+void vox_wmx4_pack(const uint16_t *w, long long rows, long long K, uint32_t *nib, uint8_t *scl) {
+    vox_wmx4_pack_(w, rows, K, nib, scl);
+}
+void vox_wmx4_unpack(const uint32_t *nib, const uint8_t *scl, long long rows, long long K, uint16_t *w) {
+    vox_wmx4_unpack_(nib, scl, rows, K, w);
+}
+long long vox_wmx4_plane_words_of(long long rows, long long K, int rb) { return vox_wmx4_plane_words(rows, K, rb); }
+void vox_wmx4_plane_layout(const uint32_t *nib, const uint8_t *scl, long long rows, long long K, int rb, int swiglu,
+                           uint32_t *out) {
+    vox_wmx4_plane_layout_(nib, scl, rows, K, rb, swiglu, out);
 }

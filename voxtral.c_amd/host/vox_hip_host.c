@@ -455,6 +455,7 @@ vh_ctx_t *vh_ctx_wrap(vox_hip_model_t *model, const vox_hip_config_t *cfg, int d
 }
 
 const vox_hip_config_t *vh_config(const vh_ctx_t *ctx) { return &ctx->cfg; }
+vox_hip_model_t *vh_model(const vh_ctx_t *ctx) { return ctx->model; }
 
 #define NAMEBUF 200
 

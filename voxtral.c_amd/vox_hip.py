@@ -39,9 +39,19 @@ class WPackStatsC(ctypes.Structure):
                 ("raw_bytes", ctypes.c_longlong), ("pack_ms", ctypes.c_double)]
 
 
-def gemv_wpack(W_bf16, x, packed: bool):
+class WMx4StatsC(ctypes.Structure):
+    """vox_hip_wmx4_stats_t"""
+    _fields_ = [("wmx4_tensors", ctypes.c_int), ("refused_tensors", ctypes.c_int),
+                ("plane_bytes", ctypes.c_longlong), ("bf16_bytes", ctypes.c_longlong),
+                ("bits_per_weight", ctypes.c_double), ("scan_ms", ctypes.c_double),
+                ("round_ms", ctypes.c_double), ("pack_ms", ctypes.c_double)]
+
+
+def gemv_wpack(W_bf16, x, packed):
     """Test entry: (y, ran_packed) of y = W x for one bf16 matrix [rows, K] through the M = 1
-    GEMV, from wpack13 planes or from the raw rows"""
+    GEMV, from wpack13 planes (packed True / 1), from the wmx4 plane (packed=2) or from the raw
+    rows.  ran_packed is a bool for packed False / True, and for packed=2 the kernel that ran:
+    2 (wmx4) or 0 (raw: the matrix is not MXFP4-valued)"""
     init()
     W = np.ascontiguousarray(W_bf16, np.uint16)
     xv = np.ascontiguousarray(x, np.float32)
@@ -51,7 +61,7 @@ def gemv_wpack(W_bf16, x, packed: bool):
     rc = lib().vox_hip_gemv_wpack(rows, K, W.ctypes.data, fptr(xv), fptr(y), int(packed))
     if rc < 0:
         _err("gemv_wpack")
-    return y, bool(rc)
+    return y, (rc if int(packed) == 2 else bool(rc))
 
 
 def gemv_rows(W_bf16, x, packed: bool):
@@ -78,6 +88,7 @@ EXPORTS = [
     "vox_hip_model_create", "vox_hip_model_free", "vox_hip_model_set_delay",
     "vox_hip_model_ada_scale", "vox_hip_model_set_kv_fp16", "vox_hip_stream_kv_fp16",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
+    "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -119,6 +130,7 @@ def lib():
         "vox_hip_model_set_kv_fp16": (I, [P, I]), "vox_hip_stream_kv_fp16": (I, [P]),
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
+        "vox_hip_set_wmx4": (I, [I]), "vox_hip_wmx4": (I, []), "vox_hip_model_wmx4_stats": (I, [P, P]),
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -189,6 +201,17 @@ def gemm_planes() -> int:
     return lib().vox_hip_gemm_planes()
 
 
+def set_wmx4(mode: int):
+    """MXFP4 weight streaming of models created from now on: 0 off (default), 1 stream the
+    decode-step matrices that are already MXFP4-valued, 2 round them first (include/voxtral_hip.h)"""
+    if lib().vox_hip_set_wmx4(int(mode)) != 0:
+        _err("set_wmx4")
+
+
+def wmx4() -> int:
+    return lib().vox_hip_wmx4()
+
+
 def set_gemmf_wait(ticks: int) -> int:
     """the encoder GEMM owner's wait per partial tile (100 MHz ticks; < 0: always recompute);
     returns the previous value (a diagnostic knob for the tests)"""
@@ -236,6 +259,14 @@ class Model:
         if lib().vox_hip_model_wpack_stats(self.h, ctypes.byref(st)) != 0:
             _err("wpack_stats")
         return {name: getattr(st, name) for name, _ in WPackStatsC._fields_}
+
+    def wmx4_stats(self) -> dict:
+        """What the single-stream decode GEMV streams as wmx4 planes (MXFP4, 5 stored bits per
+        weight): tensors streamed and refused, bytes, bits per weight, host scan / round / pack ms"""
+        st = WMx4StatsC()
+        if lib().vox_hip_model_wmx4_stats(self.h, ctypes.byref(st)) != 0:
+            _err("wmx4_stats")
+        return {name: getattr(st, name) for name, _ in WMx4StatsC._fields_}
 
     def ada_scale(self):
         c = self.cfg

@@ -151,6 +151,15 @@ def synth_lib():
                                              ctypes.c_void_p, ctypes.c_void_p]
         lib.vox_dequant_q8.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_longlong, ctypes.c_longlong]
+        LL = ctypes.c_longlong
+        lib.vox_wmx4_round.argtypes = [ctypes.c_void_p, LL, LL, ctypes.c_void_p]
+        lib.vox_wmx4_scan.argtypes = [ctypes.c_void_p, LL, LL]
+        lib.vox_wmx4_pack.argtypes = [ctypes.c_void_p, LL, LL, ctypes.c_void_p, ctypes.c_void_p]
+        lib.vox_wmx4_unpack.argtypes = [ctypes.c_void_p, ctypes.c_void_p, LL, LL, ctypes.c_void_p]
+        lib.vox_wmx4_plane_words_of.argtypes = [LL, LL, ctypes.c_int]
+        lib.vox_wmx4_plane_words_of.restype = LL
+        lib.vox_wmx4_plane_layout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, LL, LL, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_void_p]
         _synth = lib
     return _synth
 
@@ -233,6 +242,37 @@ def quantize_q8(w: Weights) -> Weights:
         else:
             f32[name] = bf16_to_f32(a)
     return Weights(w.cfg, {}, q8=q8, f32=f32)
+
+
+def mxfp4_tensor_names(c: VoxConfig):
+    """The matrices of the single-stream decode step: wq, wk, wv, wo, w1, w2, w3 of every
+    decoder layer, and tok_embeddings (LM head and embedding table)"""
+    names = [f"{EMB}.tok_embeddings.weight"]
+    for i in range(c.dec_layers):
+        names += [f"layers.{i}.{s}.weight" for s in ("attention.wq", "attention.wk", "attention.wv", "attention.wo",
+                                                     "feed_forward.w1", "feed_forward.w2", "feed_forward.w3")]
+    return names
+
+
+def mxfp4_round(a: np.ndarray) -> np.ndarray:
+    """bf16 bits [rows, K] -> the nearest MXFP4-valued bf16 tensor (csrc/vox_wmx4.h)"""
+    a = np.ascontiguousarray(a, np.uint16)
+    out = np.empty_like(a)
+    synth_lib().vox_wmx4_round(a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data)
+    return out
+
+
+def quantize_mxfp4(w: Weights) -> Weights:
+    """A bf16 checkpoint whose decode-step matrices are rounded to MXFP4 values (32-weight
+    blocks, e2m1 times a power of two; csrc/vox_wmx4.h) and still stored as bf16: what
+    VOX_HIP_WMX4=2 makes of w at load, as a checkpoint that VOX_HIP_WMX4=1 detects.  Every
+    other tensor is shared with w."""
+    if w.is_q8:
+        raise ValueError("quantize_mxfp4 takes a bf16 checkpoint")
+    t = dict(w.t)
+    for name in mxfp4_tensor_names(w.cfg):
+        t[name] = mxfp4_round(t[name])
+    return Weights(w.cfg, t, keep=w._keep)
 
 
 def synth_elems(cfg: VoxConfig) -> int:
