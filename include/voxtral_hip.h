@@ -168,6 +168,33 @@ typedef struct {
     double pack_ms;          /* packing, laying out and uploading the planes */
 } vox_hip_wmx4_stats_t;
 int vox_hip_model_wmx4_stats(const vox_hip_model_t *m, vox_hip_wmx4_stats_t *out);
+/* wmx4 for the batched MFMA step (opt-in on top of wmx4 mode 1 or 2; process-wide, read at
+ * vox_hip_model_create; VOX_HIP_WMX4_BATCH=1 gives the initial value).  When on, every bf16
+ * decoder matrix that gets a wmx4 GEMV plane (Q|K|V, wo, W1|W3, W2 per layer, the LM head) also
+ * gets a wmx4 fragment plane (csrc/vox_wmx4.h: 4.5 stored bits per weight, in the MFMA A
+ * operand's order), built on the host from the same nibbles and scales.  The batched step's
+ * projections and LM head then stream that plane instead of the 16-bit fragment-major copy
+ * and form the very bf16 fragments in registers (v_cvt_scalef32_pk_bf16_fp4): same waves,
+ * splits, slabs and summation order, so the step's logits and ids are bit-identical to the
+ * step on the bf16 copies.  A tensor the scan refuses keeps only its bf16 copy; Q8 models and
+ * VOX_HIP_WPACK=0 build nothing; the bf16 fragment copies stay (prefill reads them).  Off
+ * (default), or wmx4 mode 0: nothing changes.  The R-row GEMV step, prefill, the encoder and
+ * the single-stream step are untouched.  What MXFP4 rounding does to transcription quality
+ * has not been evaluated.
+ * vox_hip_set_wmx4_batch returns 0. */
+int vox_hip_set_wmx4_batch(int on);
+int vox_hip_wmx4_batch(void);
+/* out4: [0] tensors with a fragment plane, [1] bytes of the planes, [2] bf16 bytes of the
+ * tensors they stand for, [3] host microseconds spent laying them out and uploading them. */
+int vox_hip_model_wmx4_batch_stats(const vox_hip_model_t *m, long long out4[4]);
+/* Test entry: nb (1..32) rows x [nb][K] against one bf16 matrix W [N][K] (host pointers)
+ * through the batched step's own launchers: the rows are split into planes by the step's plane
+ * writer; head = 0 runs the projection launcher (k_skl up to 16 rows, k_skl2 from 17) and sums
+ * its split-K slabs in slab order into y [nb][N]; head = 1 runs the LM-head launcher (k_skf)
+ * into y.  fmt = 0 streams the bf16 fragment-major copy, fmt = 1 the wmx4 fragment plane.
+ * Returns 0; -1 (vox_hip_last_error) on a bad shape, or with fmt = 1 for a matrix the wmx4 scan
+ * refuses. */
+int vox_hip_skinny_wmx4(int N, int K, const uint16_t *W, const float *x, int nb, float *y, int fmt, int head);
 /* Arithmetic of the M > 1 GEMMs (encoder, adapter, prefill; no reference counterpart: the
  * CPU path's cblas_sgemm, voxtral_kernels.c:197-240, is f32): every f32 activation is split
  * into bf16 planes that multiply the exact bf16 weights on MFMA.  planes = 3 (hi + mid + lo,
@@ -323,6 +350,14 @@ int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
 /* [0] max_rows in effect, [1] step replays on the GEMV path, [2] live rows over those,
  * [3] GEMV step-graph captures.  ([1]..[3] are also counted in vox_hip_batch_stats.) */
 int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
+/* The batched MFMA step's weight source: on = 1 streams the wmx4 fragment plane of every tensor
+ * that has one (the bf16 fragment copy of the others), on = 0 the bf16 fragment copies.  Both
+ * give the same bits.  A batch created on a model with fragment planes (vox_hip_set_wmx4_batch)
+ * starts with it on; otherwise it is off and cannot be turned on.  The two modes keep step
+ * graphs of their own, so the mode may change between calls.  Returns 0; -1
+ * (vox_hip_last_error) when the model has no fragment plane, or between
+ * vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+int vox_hip_batch_set_wmx4(vox_hip_batch_t *b, int on);
 /* Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
  * bucket >= R (unused rows zero).  Returns flags: bit 0 the packed instance ran, bit 1 the
  * per-row summation order is the single-row GEMV's; -1 on error. */

@@ -227,6 +227,21 @@ __global__ __launch_bounds__(256) void k_gemv_wave(const void* __restrict__ W, c
     }
 }
 
+// VOX_KB_ONLY=skmx4 convert probe: v_cvt_scalef32_pk_bf16_fp4 of byte value threadIdx.x (in every
+// byte position of the source dword, one op_sel each) under the scale byte sb[blockIdx.x]
+__global__ void k_mx4_probe(const uint8_t* sb, uint32_t* out) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+    const uint32_t w = threadIdx.x * 0x01010101u;
+    const float sc = __uint_as_float((uint32_t)sb[blockIdx.x] << 23);
+    const bf2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
+    const bf2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
+    uint32_t* o = out + (blockIdx.x * 256 + threadIdx.x) * 4;
+    o[0] = __builtin_bit_cast(uint32_t, p0);
+    o[1] = __builtin_bit_cast(uint32_t, p1);
+    o[2] = __builtin_bit_cast(uint32_t, p2);
+    o[3] = __builtin_bit_cast(uint32_t, p3);
+}
+
 int main(int argc, char** argv) {
     int iters = argc > 1 ? atoi(argv[1]) : 200;
     hipStream_t st;
@@ -499,6 +514,169 @@ int main(int argc, char** argv) {
                     (double)mxb);
             }
             for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); CK(hipFree(mx[l])); }
+        }
+        return 0;
+    }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "skmx4")) {
+        // wmx4 fragment planes (vox_wmx4.h, 4.5 stored bits per weight) against the bf16
+        // fragment-major copies in the batched step's own launches: QKV (k_skl / k_skl2 with the
+        // RMSNorm scale), wo and W2 (k_skl / k_skl2), W1|W3 (k_sklx with the SwiGLU epilogue)
+        // and the LM head (k_skf) at 8, 16 and 32 rows, cold weights (a buffer per layer; three
+        // LM-head planes, since one would fit the Infinity Cache), the two formats alternating.
+        // Before any timing: the convert's bits for every byte under every scale of the window,
+        // and per shape and row count the outputs of both formats on a seeded random rounded
+        // matrix, bit for bit.  VOX_KB_SKMX4_SHAPES=w13 (or any list of qkv,wo,w13,w2,lm) limits
+        // the shapes.
+        {
+            const int ns = 2 * VOX_WMX4_MAX_E + 1;
+            std::vector<uint8_t> hs(ns);
+            for (int i = 0; i < ns; i++) hs[i] = (uint8_t)(127 - VOX_WMX4_MAX_E + i);
+            uint8_t* ds = (uint8_t*)dmalloc(256, 0);
+            uint32_t* dout = (uint32_t*)dmalloc((size_t)ns * 256 * 16, 0);
+            CK(hipMemcpy(ds, hs.data(), ns, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_mx4_probe, dim3(ns), dim3(256), 0, st, ds, dout);
+            CK(hipStreamSynchronize(st));
+            std::vector<uint32_t> ho((size_t)ns * 256 * 4);
+            CK(hipMemcpy(ho.data(), dout, ho.size() * 4, hipMemcpyDeviceToHost));
+            long bad = 0;
+            for (int i = 0; i < ns; i++)
+                for (int b = 0; b < 256; b++) {
+                    const int e = (int)hs[i] - 127;
+                    const uint32_t want = vox_wmx4_decode(b & 15, e) | (uint32_t)vox_wmx4_decode(b >> 4, e) << 16;
+                    for (int q = 0; q < 4; q++) bad += ho[((size_t)i * 256 + b) * 4 + q] != want;
+                }
+            printf("skmx4 convert probe: 256 bytes x %d scales x 4 byte selects against vox_wmx4_decode (low nibble = even k, "
+                   "signed zeros kept): %s (%ld differ)\n", ns, bad ? "BITS DIFFER" : "same bits", bad);
+            fflush(stdout);
+            CK(hipFree(ds)); CK(hipFree(dout));
+            if (bad) return 1;
+        }
+        const char* only = getenv("VOX_KB_SKMX4_SHAPES");
+        const int Z = 2, NLM = 3;
+        uint16_t* xp = (uint16_t*)dmalloc((size_t)Z * 3 * 16 * DH * 2, 1);
+        uint16_t* xo = (uint16_t*)dmalloc((size_t)Z * 3 * 16 * DH * 2, 0);
+        float* xf = (float*)dmalloc((size_t)Z * 16 * DH * 4, 0);
+        float* sp = (float*)dmalloc((size_t)Z * 36 * 16 * 18432 * 4, 0);
+        float* Cs = (float*)dmalloc((size_t)Z * 16 * V * 4, 0);
+        float* ssq = (float*)dmalloc((size_t)Z * 12 * 16 * 4, 0);
+        int* tick = (int*)dmalloc((size_t)SKX_TICKETS * 4, 0);
+        {
+            std::vector<float> h((size_t)Z * 12 * 16);
+            for (size_t i = 0; i < h.size(); i++) h[i] = 200.f + (float)(i % 37);
+            CK(hipMemcpy(ssq, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+        }
+        struct S { const char* n; int N, K, kind; std::vector<uint16_t*>* w; int crows; };  // kind 0 skl, 1 skl + ssq, 2 sklx, 3 skf
+        std::vector<uint16_t*> lm1(1, emb);
+        struct T { char nm[64]; double us[2][3]; double bytes[2]; };
+        std::vector<T> table;
+        for (S o : {S{"qkv", DQ + 2 * DKV, D, 1, &wqkv, DQ + 2 * DKV}, S{"wo", D, DQ, 0, &wo, D}, S{"w13", 2 * DH, D, 2, &w13, 2 * DH},
+                    S{"w2", D, DH, 0, &w2, D}, S{"lm", V, D, 3, &lm1, 32768}}) {
+            if (only && !strstr(only, o.n)) continue;
+            const size_t fragb = (size_t)vox_wmx4_frag_words(o.N, o.K) * 4;
+            size_t outb = 0;   // bytes of the output compared
+            auto run = [&](const void* W, int mx4, int nb, int rows) {
+                if (o.kind == 3) {
+                    outb = (size_t)nb * rows * 4;
+                    if (nb > 16) CK(launch_gemm_skf2(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4));
+                    else CK(launch_gemm_skf(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4));
+                } else if (o.kind == 2) {
+                    SklFused f;
+                    f.ssq_in = ssq; f.nsl = 12; f.eps = 1e-5f; f.part = sp; f.ticket = tick; f.planes = xo;
+                    outb = (size_t)Z * 3 * 16 * (rows / 2) * 2;
+                    CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, xp, o.K, W, rows, nb, f, st, mx4));
+                } else {
+                    outb = (size_t)((nb + 15) / 16) * skl_splits(o.K, rows) * 16 * rows * 4;
+                    CK(launch_gemm_skl(xp, o.K, W, nullptr, rows, nb, sp, st, o.kind == 1 ? ssq : nullptr, o.kind == 1 ? 12 : 0, 1e-5f, 1, mx4));
+                }
+            };
+            {   // bit check on seeded random weights (uniform, std 1/sqrt(3072)), rounded, and random rows
+                const int rows = o.crows;
+                std::vector<uint16_t> hw((size_t)rows * o.K);
+                uint64_t z = 0x9E3779B97F4A7C15ull ^ (uint64_t)o.K * 131 ^ (uint64_t)o.N;
+                auto rnd = [&] { z = z * 6364136223846793005ull + 1442695040888963407ull; return (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f; };
+                for (auto& v : hw) {
+                    const float f = 0.03125f * rnd();
+                    uint32_t u;
+                    memcpy(&u, &f, 4);
+                    v = (uint16_t)(u >> 16);
+                }
+                vox_wmx4_round_(hw.data(), rows, o.K, hw.data());
+                if (!vox_wmx4_scan_(hw.data(), rows, o.K)) { printf("%s: rounded weights fail the scan\n", o.n); return 1; }
+                std::vector<float> hx((size_t)Z * 16 * o.K);
+                for (auto& v : hx) v = rnd();
+                CK(hipMemcpy(xf, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+                CK(launch_split_fplanes(xf, Z * 16, o.K, xp, st));
+                std::vector<uint32_t> nib((size_t)rows * o.K / 8), pl((size_t)vox_wmx4_frag_words(rows, o.K));
+                std::vector<uint8_t> scl((size_t)rows * o.K / 32);
+                vox_wmx4_pack_(hw.data(), rows, o.K, nib.data(), scl.data());
+                vox_wmx4_frag_layout_(nib.data(), scl.data(), rows, o.K, pl.data());
+                uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
+                uint16_t* df = (uint16_t*)dmalloc(hw.size() * 2, 0);
+                uint32_t* dp = (uint32_t*)dmalloc(pl.size() * 4, 0);
+                CK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+                CK(hipMemcpy(dp, pl.data(), pl.size() * 4, hipMemcpyHostToDevice));
+                CK(launch_frag_pack(dw, rows, o.K, 0, df, st));
+                for (int nb : {8, 16, 32}) {
+                    std::vector<uint8_t> o0, o1;
+                    for (int mx4 = 0; mx4 < 2; mx4++) {
+                        void* out = o.kind == 3 ? (void*)Cs : o.kind == 2 ? (void*)xo : (void*)sp;
+                        CK(hipMemsetAsync(out, 0, o.kind == 3 ? (size_t)nb * rows * 4 : o.kind == 2 ? (size_t)Z * 3 * 16 * DH * 2 : (size_t)Z * 36 * 16 * 18432 * 4, st));
+                        run(mx4 ? (const void*)dp : (const void*)df, mx4, nb, rows);
+                        CK(hipStreamSynchronize(st));
+                        std::vector<uint8_t>& h = mx4 ? o1 : o0;
+                        h.resize(outb);
+                        CK(hipMemcpy(h.data(), out, outb, hipMemcpyDeviceToHost));
+                    }
+                    double sum = 0;
+                    size_t cnt = 0;
+                    if (o.kind != 2)
+                        for (size_t i = 0; i < outb / 4; i++, cnt++) sum += fabs((double)((const float*)o0.data())[i]);
+                    size_t nz = 0;   // (W1|W3: the outputs are the SwiGLU planes, bf16 bits)
+                    for (size_t i = 0; i < outb; i++) nz += o0[i] != 0;
+                    printf("skmx4 %-4s check nb%-2d: %d x %d, %zu output bytes (%zu nonzero), mean |y| %.4g: %s\n", o.n, nb, rows, o.K,
+                           outb, nz, cnt ? sum / cnt : 0.0, memcmp(o0.data(), o1.data(), outb) ? "BITS DIFFER" : "same bits");
+                    fflush(stdout);
+                }
+                CK(hipFree(dw)); CK(hipFree(df)); CK(hipFree(dp));
+                CK(hipMemsetD32(xp, 0x3c003c01u, (size_t)Z * 3 * 16 * DH * 2 / 4));
+            }
+            // timing: constant planes (values do not matter; every byte 0x78 is a valid scale and a
+            // valid nibble pair); the bf16 launches read the per-layer buffers as fragment copies
+            const int nl = o.kind == 3 ? NLM : (int)o.w->size();
+            std::vector<void*> mx(nl);
+            for (int l = 0; l < nl; l++) {
+                mx[l] = dmalloc(fragb, 0);
+                CK(hipMemsetD32(mx[l], 0x78787878u, fragb / 4));
+            }
+            const int it = o.kind == 3 ? iters / 10 + 1 : iters;
+            for (int nb : {8, 16, 32}) {
+                T t;
+                snprintf(t.nm, sizeof t.nm, "%-4s nb%-2d", o.n, nb);
+                t.bytes[0] = (double)o.N * o.K * 2;
+                t.bytes[1] = (double)fragb;
+                for (int r = 0; r < 3; r++) {
+                    char nm[96];
+                    snprintf(nm, sizeof nm, "skmx4 %-4s nb%-2d bf16 run %d", o.n, nb, r);
+                    t.us[0][r] = timeit([&] { run((*o.w)[layer++ % (int)o.w->size()], 0, nb, o.N); }, it, st);
+                    add(nm, t.us[0][r], t.bytes[0]);
+                    snprintf(nm, sizeof nm, "skmx4 %-4s nb%-2d mx4  run %d", o.n, nb, r);
+                    t.us[1][r] = timeit([&] { run(mx[layer++ % nl], 1, nb, o.N); }, it, st);
+                    add(nm, t.us[1][r], t.bytes[1]);
+                }
+                table.push_back(t);
+            }
+            for (int l = 0; l < nl; l++) CK(hipFree(mx[l]));
+        }
+        printf("\nskmx4 medians of three: us per launch, MB streamed, fraction of 8 TB/s\n");
+        printf("%-10s %9s %8s %6s   %9s %8s %6s   %s\n", "", "bf16 us", "MB", "of 8T", "mx4 us", "MB", "of 8T", "mx4 / bf16");
+        for (T& t : table) {
+            double m[2];
+            for (int f = 0; f < 2; f++) {
+                std::sort(t.us[f], t.us[f] + 3);
+                m[f] = t.us[f][1];
+            }
+            printf("%-10s %9.2f %8.1f %6.3f   %9.2f %8.1f %6.3f   %.3f\n", t.nm, m[0], t.bytes[0] / 1e6, t.bytes[0] / m[0] / 8e6, m[1],
+                   t.bytes[1] / 1e6, t.bytes[1] / m[1] / 8e6, m[1] / m[0]);
         }
         return 0;
     }

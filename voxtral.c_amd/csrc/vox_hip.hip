@@ -153,8 +153,11 @@ struct WPackD {
 };
 // wmx4 plane of a bf16 matrix that is MXFP4-valued (vox_wmx4.h), for the single-stream GEMV:
 // 5 bits per weight, decoded without loss.  null: none (the tensor streams as wpack13 or raw).
+// frag: its wmx4 fragment plane for the batched MFMA step (vox_hip_set_wmx4_batch), 4.5 bits per
+// weight; null: the step reads the tensor's bf16 fragment-major copy.
 struct WMx4D {
     uint8_t* plane;
+    uint8_t* frag;
 };
 struct DecLayerD {
     uint8_t *wqkv, *wo, *w13, *w2;
@@ -196,6 +199,8 @@ struct vox_hip_model {
     WMx4D mlm;                     // wmx4 plane of the LM head
     int wmx4;                      // vox_hip_wmx4() at creation (0 off, 1 detect, 2 round)
     vox_hip_wmx4_stats_t mstats;
+    int wmx4_batch;                // vox_hip_wmx4_batch() at creation: fragment planes beside the GEMV planes
+    long long fstats[4];           // fragment planes: tensors, plane bytes, their bf16 bytes, host microseconds
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -341,6 +346,21 @@ extern "C" int vox_hip_set_wmx4(int mode) {
     return 0;
 }
 extern "C" int vox_hip_wmx4(void) { return wmx4_mode(); }
+// wmx4 fragment planes for the batched step, for models created from now on;
+// VOX_HIP_WMX4_BATCH gives the initial value
+static int g_wmx4_batch = -1;
+static int wmx4_batch_mode() {
+    if (g_wmx4_batch < 0) {
+        const char* e = getenv("VOX_HIP_WMX4_BATCH");
+        g_wmx4_batch = e && atoi(e) == 1 ? 1 : 0;
+    }
+    return g_wmx4_batch;
+}
+extern "C" int vox_hip_set_wmx4_batch(int on) {
+    g_wmx4_batch = on ? 1 : 0;
+    return 0;
+}
+extern "C" int vox_hip_wmx4_batch(void) { return wmx4_batch_mode(); }
 
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -358,8 +378,11 @@ static void wmx4_round_host(vox_hip_wmx4_stats_t& S, const void* w, int rows, in
 // The wmx4 plane of a bf16 matrix whose rows are in device order (host copy), for the wmx4
 // row groups of this shape.  A tensor that fails vox_wmx4_scan, or of a shape the wmx4
 // instances do not take, gets none: M->plane stays null and the tensor streams as before.
-static int wmx4_make(int enabled, vox_hip_wmx4_stats_t& S, WMx4D* M, const uint16_t* w, int rows, int K, int swiglu) {
-    M->plane = nullptr;
+// fstats != null (and rows % 16 == 0, K % 64 == 0): the tensor's fragment plane for the batched
+// step as well, from the same nibbles and scales.
+static int wmx4_make(int enabled, vox_hip_wmx4_stats_t& S, WMx4D* M, const uint16_t* w, int rows, int K, int swiglu,
+                     long long* fstats = nullptr) {
+    M->plane = M->frag = nullptr;
     if (!enabled) return 0;
     if (!w) return set_err("null weight pointer");
     const size_t n = (size_t)rows * K;
@@ -393,6 +416,19 @@ static int wmx4_make(int enabled, vox_hip_wmx4_stats_t& S, WMx4D* M, const uint1
     S.bf16_bytes += (long long)n * 2;
     S.bits_per_weight = S.plane_bytes * 8.0 / (S.bf16_bytes / 2);
     S.pack_ms += ms_since(t0);
+    const size_t fwords = fstats ? (size_t)vox_wmx4_frag_words(rows, K) : 0;
+    if (fwords) {
+        t0 = std::chrono::steady_clock::now();
+        std::vector<uint32_t>().swap(plane);
+        std::vector<uint32_t> fp(fwords);
+        par_range(rows / 16, [&](long long g0, long long g1) { vox_wmx4_frag_groups(nib.data(), scl.data(), g0, g1, K, fp.data()); });
+        CK(dalloc(&M->frag, fwords * 4));
+        if (upload(M->frag, fp.data(), fwords * 4)) return -1;
+        fstats[0]++;
+        fstats[1] += (long long)fwords * 4;
+        fstats[2] += (long long)n * 2;
+        fstats[3] += (long long)(ms_since(t0) * 1000.0);
+    }
     return 0;
 }
 // (VOX_HIP_WPACK=0 streams raw rows everywhere: such a model builds no plane)
@@ -495,6 +531,9 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     memset(&m->mlm, 0, sizeof m->mlm);
     memset(&m->mstats, 0, sizeof m->mstats);
     m->wmx4 = wmx4_mode();
+    m->wmx4_batch = m->wmx4 ? wmx4_batch_mode() : 0;
+    memset(m->fstats, 0, sizeof m->fstats);
+    long long* const fst = m->wmx4_batch ? m->fstats : nullptr;
     {
         // VOX_HIP_WPACK=0: every GEMV weight stays raw bf16 (same-machine A/B runs)
         const char* e = getenv("VOX_HIP_WPACK");
@@ -561,7 +600,7 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     // not in the first step); the raw copies stay for every other path
     if (!w->tok_emb_s) {
         TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0));
-        TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &m->mlm, (const uint16_t*)h_tok, c.vocab, DD, 0));
+        TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &m->mlm, (const uint16_t*)h_tok, c.vocab, DD, 0, fst));
     }
     rnd[0] = std::vector<uint16_t>();
     std::vector<uint16_t> hrows;  // a matrix in device row order (merged Q|K|V, interleaved W1|W3)
@@ -590,11 +629,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
             memcpy(hrows.data() + (size_t)DQ * DD, h_wk, (size_t)DKV * DD * 2);
             memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, h_wv, (size_t)DKV * DD * 2);
             TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
-            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mqkv, hrows.data(), DQ + 2 * DKV, DD, 0, fst));
         }
         if (!L.so) {
             TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0));
-            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mo, (const uint16_t*)h_wo, DD, DQ, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mo, (const uint16_t*)h_wo, DD, DQ, 0, fst));
         }
         if (!L.s13) {
             hrows.resize((size_t)2 * DH * DD);
@@ -604,11 +643,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
                 memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)h_w3 + g * grp, grp * 2);
             }
             TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1));
-            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m13, hrows.data(), 2 * DH, DD, 1));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m13, hrows.data(), 2 * DH, DD, 1, fst));
         }
         if (!L.s2) {
             TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0));
-            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m2, (const uint16_t*)h_w2, DD, DH, 0));
+            TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m2, (const uint16_t*)h_w2, DD, DH, 0, fst));
         }
         TRYH(dalloc(&L.attn_norm, DD));
         TRY(upload(L.attn_norm, w->dec_attn_norm[l], DD * 4));
@@ -642,9 +681,9 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
         dfree(L.sqkv); dfree(L.so); dfree(L.s13); dfree(L.s2);
         dfree(L.attn_norm); dfree(L.ffn_norm);
         for (WPackD* P : {&L.pqkv, &L.po, &L.p13, &L.p2}) { dfree(P->main); dfree(P->side); }
-        for (WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) dfree(M->plane);
+        for (WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) { dfree(M->plane); dfree(M->frag); }
     }
-    dfree(m->plm.main); dfree(m->plm.side); dfree(m->mlm.plane);
+    dfree(m->plm.main); dfree(m->plm.side); dfree(m->mlm.plane); dfree(m->mlm.frag);
     for (auto& F : m->dfrag) {
         dfree(F.wqkv); dfree(F.wo); dfree(F.w13); dfree(F.w2);
     }
@@ -667,6 +706,12 @@ extern "C" int vox_hip_model_wpack_stats(const vox_hip_model_t* m, vox_hip_wpack
 extern "C" int vox_hip_model_wmx4_stats(const vox_hip_model_t* m, vox_hip_wmx4_stats_t* out) {
     if (!m || !out) return set_err("wmx4_stats: null argument");
     *out = m->mstats;
+    return 0;
+}
+
+extern "C" int vox_hip_model_wmx4_batch_stats(const vox_hip_model_t* m, long long out4[4]) {
+    if (!m || !out4) return set_err("wmx4_batch_stats: null argument");
+    memcpy(out4, m->fstats, sizeof m->fstats);
     return 0;
 }
 
@@ -2632,7 +2677,7 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
     float *dx = nullptr, *dy = nullptr;
     if (packed < 0 || packed > 2) return set_err("gemv_wpack: packed must be 0, 1 or 2 (got %d)", packed);
     WPackD P = {nullptr, nullptr, 0};
-    WMx4D M = {nullptr};
+    WMx4D M = {nullptr, nullptr};
     vox_hip_wpack_stats_t S;
     vox_hip_wmx4_stats_t MS;
     memset(&S, 0, sizeof S);
@@ -2697,6 +2742,74 @@ extern "C" int vox_hip_gemv_rows(int rows, int K, const uint16_t* W, const float
     const int was_packed = P.main != nullptr;
     dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side);
     return rc ? -1 : (was_packed | 2);
+}
+
+// Test entry: nb rows x [nb][K] against one bf16 matrix W [N][K] through the batched step's own
+// launchers (include/voxtral_hip.h): planes by launch_split_fplanes, then launch_gemm_skl with
+// pair = 1 and its slabs summed in slab order on the host (head = 0), or launch_gemm_skf /
+// launch_gemm_skf2 (head = 1); fmt = 1 streams the wmx4 fragment plane.
+extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float* x, int nb, float* y, int fmt, int head) {
+    std::lock_guard<std::mutex> lk(g_twin_mu);
+    if (!W || !x || !y) return set_err("skinny_wmx4: null argument");
+    if (nb < 1 || nb > VOX_MAX_BATCH) return set_err("skinny_wmx4: %d rows (1..%d)", nb, VOX_MAX_BATCH);
+    if ((fmt != 0 && fmt != 1) || (head != 0 && head != 1)) return set_err("skinny_wmx4: fmt and head are 0 or 1");
+    if (N < 64 || N % 64 || K < 64 || K % 64 || (!head && !skl_splits(K, N)))
+        return set_err("skinny_wmx4: shape %d x %d is not a skinny GEMM shape", N, K);
+    if (fmt && !vox_wmx4_scan_(W, N, K))
+        return set_err("skinny_wmx4: the matrix is not MXFP4-valued inside the exponent window");
+    if (twin_init()) return -1;
+    const int S = head ? 1 : skl_splits(K, N), Z = 2;
+    uint8_t *dW = nullptr, *dF = nullptr;
+    float *dx = nullptr, *dout = nullptr;
+    uint16_t* dxs = nullptr;
+    const size_t nout = head ? (size_t)Z * SK_ROWS * N : (size_t)Z * S * SK_ROWS * N;
+    std::vector<float> out(nout);
+    auto run = [&]() -> int {
+        if (fmt) {
+            const size_t n = (size_t)N * K, words = (size_t)vox_wmx4_frag_words(N, K);
+            std::vector<uint32_t> nib(n / 8), fp(words);
+            std::vector<uint8_t> scl(n / VOX_WMX4_BLOCK);
+            par_range(N, [&](long long r0, long long r1) { vox_wmx4_pack_rows(W, r0, r1, K, nib.data(), scl.data()); });
+            par_range(N / 16, [&](long long g0, long long g1) { vox_wmx4_frag_groups(nib.data(), scl.data(), g0, g1, K, fp.data()); });
+            CK(dalloc(&dF, words * 4));
+            if (upload(dF, fp.data(), words * 4)) return -1;
+        } else {
+            CK(dalloc(&dW, (size_t)N * K * 2));
+            if (upload(dW, W, (size_t)N * K * 2) || frag_copy(&dF, dW, N, K, 0)) return -1;
+        }
+        CK(dalloc(&dx, (size_t)nb * K));
+        CK(dalloc(&dxs, (size_t)Z * 3 * SK_ROWS * K));
+        CK(dalloc(&dout, nout));
+        if (upload(dx, x, (size_t)nb * K * 4)) return -1;  // (dalloc zeroes: the planes of rows nb.. are 0)
+        CK(launch_split_fplanes(dx, nb, K, dxs, g_twin_st));
+        if (!head)
+            CK(launch_gemm_skl(dxs, K, dF, nullptr, N, nb, dout, g_twin_st, nullptr, 0, 0.f, 1, fmt));
+        else if (nb > SK_ROWS)
+            CK(launch_gemm_skf2(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt));
+        else
+            CK(launch_gemm_skf(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt));
+        CK(hipStreamSynchronize(g_twin_st));
+        CK(hipMemcpy(out.data(), dout, nout * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    dfree(dW); dfree(dF); dfree(dx); dfree(dxs); dfree(dout);
+    if (rc) return -1;
+    for (int j = 0; j < nb; j++) {
+        float* yr = y + (size_t)j * N;
+        if (head) {
+            memcpy(yr, out.data() + (size_t)j * N, (size_t)N * 4);
+            continue;
+        }
+        // slabs [row block][s][16][N], added in slab order (psum)
+        const float* p = out.data() + (size_t)(j >> 4) * S * SK_ROWS * N + (size_t)(j & 15) * N;
+        for (int n = 0; n < N; n++) {
+            float v = p[n];
+            for (int sp = 1; sp < S; sp++) v += p[(size_t)sp * SK_ROWS * N + n];
+            yr[n] = v;
+        }
+    }
+    return 0;
 }
 
 extern "C" void vox_hip_sgemm_bf16(int M, int N, int K, const float* A, const uint16_t* B, float* C) {
@@ -2917,8 +3030,12 @@ struct vox_hip_batch {
     // step graphs [kv16][slot bucket 1, 2, 4, 8, 16, 32][attention splits bucket]: their kernel
     // arguments point at the slot table and the batch's buffers only, so they stay valid as
     // streams come and go; captured again only when the model's rope table moves
-    hipGraphExec_t gexec[2][6][STEP_GRAPHS];
+    // (wmx4: [2 wmx4 + kv16], the two weight sources keep graphs of their own)
+    hipGraphExec_t gexec[4][6][STEP_GRAPHS];
     int grope_gen;
+    // the MFMA step streams the wmx4 fragment planes of the tensors that have one
+    // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
+    int wmx4;
     // the R-row GEMV step (batch_step_gemv): steps whose slot bucket is <= gemv_rows take it
     // (0: off).  Its graphs [kv16][bucket 1, 2, 4, 8][splits bucket] have keys of their own, so
     // the mode changes between calls without a capture being dropped.
@@ -3078,18 +3195,22 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
         const int r = atoi(e);
         if (r && !(m->tok_emb_s || m->dec[0].sqkv) && batch_set_gemv_rows(b, r)) return fail();
     }
+    b->wmx4 = m->fstats[0] ? 1 : 0;
     return b;
 }
 
 // the batched step's projections: k_skl, one burst of column groups per block
-static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* part,
-                             hipStream_t st, const float* ssq = nullptr, int nsl = 0, float eps = 0.f) {
-    return launch_gemm_skl(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps, 1);
+// mx: the tensor's wmx4 fragment plane when the step streams it (null: Wf, the 16-bit copy)
+static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const uint8_t* mx, const float* wscale, int N,
+                             int nb, float* part, hipStream_t st, const float* ssq = nullptr, int nsl = 0,
+                             float eps = 0.f) {
+    return launch_gemm_skl(xs, K, mx ? mx : Wf, wscale, N, nb, part, st, ssq, nsl, eps, 1, mx != nullptr);
 }
 
 // one batched step over slots 0..nb-1 of the slot table (their input rows already in b->x)
-static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16) {
+static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16, int wmx4) {
     vox_hip_model_t* m = b->m;
+    auto mx = [&](const WMx4D& M) -> const uint8_t* { return wmx4 ? M.frag : nullptr; };
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
@@ -3117,13 +3238,13 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16) {
         // inverse RMS applied by the projection
         CK(launch_resid_xw_fplanes(b->x, nb, DD, L.attn_norm, nullptr, b->xp_d, b->part, l ? Sres : 0, nullptr,
                                    b->ssq, st));
-        CK(batch_gemm(b->xp_d, DD, F.wqkv, L.sqkv, DQ + 2 * DKV, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
+        CK(batch_gemm(b->xp_d, DD, F.wqkv, mx(L.mqkv), L.sqkv, DQ + 2 * DKV, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
         // RoPE + KV append + attention of every live slot, output into the wo planes (one
         // launch; past 256 keys the last key-range block of a kv head merges the partials)
         AttnFuse af;
         af.qkv = b->part; af.S = skl_splits(DD, DQ + 2 * DKV); af.N = DQ + 2 * DKV; af.rope = m->rope_dec; af.xs = b->xp_q;
         CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kv16));
-        CK(batch_gemm(b->xp_q, DQ, F.wo, L.so, DD, nb, b->part, st));
+        CK(batch_gemm(b->xp_q, DQ, F.wo, mx(L.mo), L.so, DD, nb, b->part, st));
         CK(launch_resid_xw_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, b->xp_d, b->part,
                                    skl_splits(DQ, DD), nullptr, b->ssq, st));
         if (!L.s13) {
@@ -3133,13 +3254,14 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16) {
             f.ssq_in = b->ssq; f.nsl = DD / 256; f.eps = c.dec_eps;
             f.part = b->part; f.ticket = b->ticket;
             f.planes = b->xp_h;
-            CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, b->xp_d, DD, F.w13, 2 * DH, nb, f, st));
+            const uint8_t* m13 = mx(L.m13);
+            CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, b->xp_d, DD, m13 ? m13 : F.w13, 2 * DH, nb, f, st, m13 != nullptr));
         } else {
             // Q8: the int8 projection, then the SwiGLU rows
-            CK(batch_gemm(b->xp_d, DD, F.w13, L.s13, 2 * DH, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
+            CK(batch_gemm(b->xp_d, DD, F.w13, nullptr, L.s13, 2 * DH, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
             CK(launch_swiglu_fplanes(b->part, skl_splits(DD, 2 * DH), DH, nb, b->xp_h, st));
         }
-        CK(batch_gemm(b->xp_h, DH, F.w2, L.s2, DD, nb, b->part, st));
+        CK(batch_gemm(b->xp_h, DH, F.w2, mx(L.m2), L.s2, DD, nb, b->part, st));
     }
     // final norm (after the last w2 residual) + LM head (tied embeddings) + per-slot argmax,
     // state, token log and next inputs (decoder.c:762-779)
@@ -3151,12 +3273,14 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16) {
         const char* e = getenv("VOX_HIP_SKF2");
         skf2 = (e && atoi(e) == 0) ? 0 : 1;
     }
+    const uint8_t* mlm = mx(m->mlm);
+    const void* lmw = mlm ? mlm : m->lm_frag;
     if (skf2 && nb > SK_ROWS)
-        CK(launch_gemm_skf2(b->xp_d, DD, m->lm_frag, m->tok_emb_s, c.vocab, nb, b->logits, c.vocab, st));
+        CK(launch_gemm_skf2(b->xp_d, DD, lmw, m->tok_emb_s, c.vocab, nb, b->logits, c.vocab, st, mlm != nullptr));
     else
         for (int r0 = 0; r0 < nb; r0 += SK_ROWS)
-            CK(launch_gemm_skf(b->xp_d + (size_t)r0 * 3 * DD, DD, m->lm_frag, m->tok_emb_s, c.vocab,
-                               std::min(SK_ROWS, nb - r0), b->logits + (size_t)r0 * c.vocab, c.vocab, st));
+            CK(launch_gemm_skf(b->xp_d + (size_t)r0 * 3 * DD, DD, lmw, m->tok_emb_s, c.vocab,
+                               std::min(SK_ROWS, nb - r0), b->logits + (size_t)r0 * c.vocab, c.vocab, st, mlm != nullptr));
     CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
@@ -3255,6 +3379,15 @@ extern "C" int vox_hip_batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
     return batch_set_gemv_rows(b, max_rows);
 }
 
+extern "C" int vox_hip_batch_set_wmx4(vox_hip_batch_t* b, int on) {
+    if (!b) return set_err("batch_set_wmx4: null batch");
+    if (b->call.active) return set_err("batch_set_wmx4: a begun call was not finished");
+    if (on && !b->m->fstats[0])
+        return set_err("batch_set_wmx4: the model has no wmx4 fragment planes (vox_hip_set_wmx4_batch before its creation)");
+    b->wmx4 = on ? 1 : 0;
+    return 0;
+}
+
 extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out4) {
     if (!b || !out4) return set_err("batch_gemv_stats: null argument");
     out4[0] = b->gemv_rows;
@@ -3275,7 +3408,8 @@ static int slot_bucket(int n, int* g) {
 // `steps` batched steps over slots 0..nb-1: replays of the bucket's step graph (captured the
 // first time, and again only when the rope table moved), or eager launches
 static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kv16, int steps, int gemv) {
-    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kv16) : batch_step(b, nb, splits, kv16); };
+    const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
+    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kv16) : batch_step(b, nb, splits, kv16, wmx4); };
     if (gemv) b->n_gemv_replays += steps;
     if (!use_graphs()) {
         for (int k = 0; k < steps; k++)
@@ -3287,7 +3421,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = gemv ? b->gvexec[kv16][gb][gi] : b->gexec[kv16][gb][gi];
+    hipGraphExec_t& ge = gemv ? b->gvexec[kv16][gb][gi] : b->gexec[2 * wmx4 + kv16][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));

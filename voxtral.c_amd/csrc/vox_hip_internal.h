@@ -14,7 +14,8 @@ constexpr int ALT_PART = 10;         // per-block alt partial: m, s, 4 values, 4
 constexpr int ALT_REC = 8;           // per-step alt record: p_best, (id, p) x 3, pad
 enum { PRO_NONE = 0, PRO_NORM = 1, PRO_NORM_ADA = 2 };
 // k_gemv weight formats: bf16 rows, Q8 rows + row scales, wpack13 planes (vox_wpack.h), wmx4
-// plane (vox_wmx4.h)
+// plane (vox_wmx4.h).  The skinny MFMA kernels (k_skf, k_skl, k_skl2, k_sklx) take WF_BF16 and
+// WF_Q8 as fragment-major copies and WF_MX4 as the wmx4 fragment plane.
 enum { WF_BF16 = 0, WF_Q8 = 1, WF_P13 = 2, WF_MX4 = 3 };
 
 constexpr int GEMV_MAX_BLOCKS = 1024;  // 4 blocks of 256 threads per CU on 256 CUs
@@ -228,11 +229,13 @@ hipError_t launch_split_fplanes(const float* x, int nb, int K, uint16_t* xs, hip
 // silu(W1 x) * (W3 x) from the split W1|W3 slabs (N = 2H rows) into planes
 hipError_t launch_swiglu_fplanes(const float* part, int S, int H, int nb, uint16_t* xs, hipStream_t st);
 // C[j][n] = sum_k x_j[k] W[n][k] (LM head: k_skf)
+// mx4 (here and in the launchers below): Wf is the wmx4 fragment plane (vox_wmx4.h) of a bf16
+// matrix instead of its fragment-major copy; same geometry, same bits
 hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                           int ldc, hipStream_t st);
+                           int ldc, hipStream_t st, int mx4 = 0);
 // launch_gemm_skf for 17..32 rows (two 16-row blocks of planes, one weight read)
 hipError_t launch_gemm_skf2(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                            int ldc, hipStream_t st);
+                            int ldc, hipStream_t st, int mx4 = 0);
 // split-K slabs part[s][16][N], s < skl_splits(K, N) (projections: k_skl; k_sklx and the
 // encoder's skinny chain use skl_splits(K))
 int skl_splits(int K, int N = 0);
@@ -242,7 +245,7 @@ constexpr int SKL_MAX_SLICES = 12;  // D <= 3072
 // configuration exists (the batched step)
 hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb,
                            float* part, hipStream_t st, const float* ssq = nullptr, int nsl = 0, float eps = 0.f,
-                           int pair = 0);
+                           int pair = 0, int mx4 = 0);
 hipError_t launch_gemm_skl_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, int N, int nb, float* part,
                                hipStream_t st);  // tools/kbench sweep
 hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, int N, int nb, float* part,
@@ -252,7 +255,8 @@ hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const
 // launch_gemm_skl)
 hipError_t launch_resid_xw_fplanes(float* x, int nb, int D, const float* w, const float* ada, uint16_t* xs,
                                    const float* part, int S, const float* bias, float* ssq, hipStream_t st);
-// k_sklx: k_skl with the neighbouring row kernels folded in (bf16 weights).  Inputs are
+// k_sklx: k_skl with the neighbouring row kernels folded in (bf16 weights, or their wmx4
+// fragment plane).  Inputs are
 // always planes; SKX_PRO_SCALE planes hold x * w (* (1 + ada)) of an RMSNorm whose inverse RMS
 // is applied to the MFMA results, computed from the row sums of squares that the producer left
 // per column slice (ssq_in[rb][nsl][16], summed in slice order).  Epilogue: the slabs go out
@@ -285,8 +289,9 @@ struct SklFused {
 // column slices of a k_sklx launch (the ssq_out slices its consumer sums)
 int sklx_slices(int N, int K);
 constexpr int SKX_TICKETS = 4 * 1024;
+// mx4: SKX_PRO_SCALE / SKX_EPI_SWIGLU only (the batched decode step's W1|W3)
 hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const void* Wf, int N, int nb,
-                            const SklFused& f, hipStream_t st);
+                            const SklFused& f, hipStream_t st, int mx4 = 0);
 // k_gemmf (vox_hip_gemmf.hip): stream-K MFMA GEMM, planes x fragment-major bf16 weights;
 // epi in {STORE, RESID, GELU, GELU_ERF, SWIGLU}; SWIGLU with xo writes the gate rows as
 // planes [rb][3][16][N / 2].  ws: gemmf_ws_floats(gemmf_grid()) floats of partial tiles,

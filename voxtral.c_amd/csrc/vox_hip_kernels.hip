@@ -2575,21 +2575,75 @@ __device__ __forceinline__ bf16x8 i8x8_bf16(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(bf16x8, make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)));
 }
 
-// one 64-k block of R row groups (A halves) and of the three planes (B halves) of Z 16-row
+// e2m1 nibbles of one dword (weight k in bits 4k .. 4k + 3, vox_wmx4.h) times the block scale
+// 2^(byte - 127), given as the f32 byte << 23: four v_cvt_scalef32_pk_bf16_fp4, one per byte.
+// An e2m1 value times a power of two inside the wmx4 window is exactly a bf16, so the result
+// is the 16 bytes the bf16 fragment copy holds for this half.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ bf16x8 mx4x8_bf16(uint32_t w, float sc) {
+    const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0);
+    const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
+    const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2);
+    const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
+    return bf16x8{p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
+}
+
+// The A operand of the skinny MFMA kernels (k_skf, k_skl, k_skl2, k_sklx): one lane's part of
+// one 64-k block of a 16-row group, by weight format.  WF_BF16: two 16-B halves of the
+// fragment-major copy (2048 B per block); WF_Q8: one 16-B piece of 16 int8 (1024 B); WF_MX4:
+// the wmx4 fragment plane's record (vox_wmx4.h, 576 B) -- 8 B of nibbles and the lane's scale
+// byte, turned into the bf16 instance's halves in registers.
+template <int WF>
+struct SkA {
+    u32x4 v[WF == WF_Q8 ? 1 : 2];
+};
+template <>
+struct SkA<WF_MX4> {
+    u32x2 nib;
+    uint32_t sc;
+};
+template <int WF>
+constexpr int ska_bytes() { return WF == WF_MX4 ? 576 : WF == WF_Q8 ? 1024 : 2048; }
+// the lane's loads of the block at byte `soff` of the descriptor (non-temporal)
+template <int WF>
+__device__ __forceinline__ void ska_load(SkA<WF>& a, __amdgpu_buffer_rsrc_t W, int lane, int soff) {
+    if constexpr (WF == WF_MX4) {
+        a.nib = __builtin_amdgcn_raw_buffer_load_b64(W, lane * 8, soff, 2);
+        a.sc = __builtin_amdgcn_raw_buffer_load_b8(W, 512 + lane, soff, 2);
+    } else {
+#pragma unroll
+        for (int t = 0; t < (WF == WF_Q8 ? 1 : 2); t++) a.v[t] = __builtin_amdgcn_raw_buffer_load_b128(W, lane * 16 + t * 1024, soff, 2);
+    }
+}
+// half t of the block as the MFMA's A fragment
+template <int WF>
+__device__ __forceinline__ bf16x8 ska_frag(const SkA<WF>& a, int t) {
+    if constexpr (WF == WF_MX4) {
+        return mx4x8_bf16(t ? a.nib.y : a.nib.x, __uint_as_float(a.sc << 23));
+    } else if constexpr (WF == WF_Q8) {
+        const u32x4 q = a.v[0];
+        return t ? i8x8_bf16(q.z, q.w) : i8x8_bf16(q.x, q.y);
+    } else {
+        const u32x4 q = a.v[t];
+        return __builtin_bit_cast(bf16x8, make_uint4(q.x, q.y, q.z, q.w));
+    }
+}
+
+// one 64-k block of R row groups (A operand) and of the three planes (B halves) of Z 16-row
 // blocks of streams
-template <int WQ8, int R, int Z = 1>
+template <int WF, int R, int Z = 1>
 struct SkfRegs {
-    u32x4 a[R][WQ8 ? 1 : 2];
+    SkA<WF> a[R];
     uint4 x[Z][3][2];
 };
 
 // block b of the wave's range; past the range the loads go through zero-length descriptors
 // (they return 0 and move no bytes, so the ring below needs no branches)
-template <int WQ8, int R, int Z>
-__device__ __forceinline__ void skf_load(SkfRegs<WQ8, R, Z>& s, __amdgpu_buffer_rsrc_t W, __amdgpu_buffer_rsrc_t X,
+template <int WF, int R, int Z>
+__device__ __forceinline__ void skf_load(SkfRegs<WF, R, Z>& s, __amdgpu_buffer_rsrc_t W, __amdgpu_buffer_rsrc_t X,
                                          int kbytes, int b, int pbytes) {
-    constexpr int FB = WQ8 ? 1024 : 2048;
-    const int lo = (threadIdx.x & 63) * 16;
+    constexpr int FB = ska_bytes<WF>();
+    const int lane = threadIdx.x & 63, lo = lane * 16;
 #pragma unroll
     for (int z = 0; z < Z; z++)
 #pragma unroll
@@ -2600,26 +2654,16 @@ __device__ __forceinline__ void skf_load(SkfRegs<WQ8, R, Z>& s, __amdgpu_buffer_
                 s.x[z][p][t] = make_uint4(v.x, v.y, v.z, v.w);
             }
 #pragma unroll
-    for (int r = 0; r < R; r++)
-#pragma unroll
-        for (int t = 0; t < (WQ8 ? 1 : 2); t++)
-            s.a[r][t] = __builtin_amdgcn_raw_buffer_load_b128(W, lo + t * 1024, r * kbytes + b * FB, 2);
+    for (int r = 0; r < R; r++) ska_load<WF>(s.a[r], W, lane, r * kbytes + b * FB);
 }
 
-template <int WQ8, int R, int Z>
-__device__ __forceinline__ void skf_mma(const SkfRegs<WQ8, R, Z>& s, f32x4 (&acc)[Z][R]) {
+template <int WF, int R, int Z>
+__device__ __forceinline__ void skf_mma(const SkfRegs<WF, R, Z>& s, f32x4 (&acc)[Z][R]) {
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            bf16x8 af;
-            if (WQ8) {
-                const u32x4 q = s.a[r][0];
-                af = t ? i8x8_bf16(q.z, q.w) : i8x8_bf16(q.x, q.y);
-            } else {
-                const u32x4 q = s.a[r][t];
-                af = __builtin_bit_cast(bf16x8, make_uint4(q.x, q.y, q.z, q.w));
-            }
+            const bf16x8 af = ska_frag<WF>(s.a[r], t);
 #pragma unroll
             for (int z = 0; z < Z; z++)
 #pragma unroll
@@ -2634,12 +2678,13 @@ __device__ __forceinline__ void skf_mma(const SkfRegs<WQ8, R, Z>& s, f32x4 (&acc
 // over R = 4 groups).  Z = 2: both 16-row blocks of a 32-stream step against each weight
 // fragment the wave loads, so the 805 MB of embeddings cross the load path once per step
 // instead of once per row block (the planes of a row block z follow block z - 1's three).
-template <int WQ8, int R, int NW, int D, int Z = 1>
+template <int WF, int R, int NW, int D, int Z = 1>
 __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs, int K,
                                                  const uint8_t* __restrict__ W, const float* __restrict__ wscale,
                                                  int N, int nb, float* __restrict__ C, int ldc) {
     __shared__ float red[NW][Z * R][4][64];
-    constexpr int FB = WQ8 ? 1024 : 2048;
+    constexpr bool WQ8 = WF == WF_Q8;
+    constexpr int FB = ska_bytes<WF>();
     // wave index through readfirstlane: a provably uniform block range keeps the buffer
     // loads' soffset in an SGPR (else every load becomes a waterfall loop)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2661,12 +2706,12 @@ __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs
         for (int r = 0; r < R; r++) acc[z][r] = f32x4{0.f, 0.f, 0.f, 0.f};
     // register ring of D blocks: block b + D - 1 is requested before block b's MFMAs, so a
     // wave keeps D - 1 blocks of weights and planes in flight
-    SkfRegs<WQ8, R, Z> s[D];
+    SkfRegs<WF, R, Z> s[D];
 #define SKF_LOAD(slot, blk)                                                                  \
     do {                                                                                     \
         const int bb__ = (blk);                                                              \
         const bool in__ = bb__ < b1;                                                         \
-        skf_load<WQ8, R, Z>(s[slot], in__ ? Wd : Wz, in__ ? Xd : Xz, kbytes, in__ ? bb__ : 0, pbytes); \
+        skf_load<WF, R, Z>(s[slot], in__ ? Wd : Wz, in__ ? Xd : Xz, kbytes, in__ ? bb__ : 0, pbytes); \
     } while (0)
 #pragma unroll
     for (int i = 0; i < D - 1; i++) SKF_LOAD(i, b0 + i);
@@ -2675,7 +2720,7 @@ __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs
         for (int i = 0; i < D; i++) {
             SKF_LOAD((i + D - 1) % D, b + i + D - 1);
             __builtin_amdgcn_sched_barrier(0);
-            skf_mma<WQ8, R, Z>(s[i], acc);  // zeros past the range: acc + 0
+            skf_mma<WF, R, Z>(s[i], acc);  // zeros past the range: acc + 0
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -2713,14 +2758,15 @@ __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs
 // ssq != null: the planes hold x * w (* (1 + ada)) of an RMSNorm (k_resid_xw_fplanes) and
 // every result of stream row j is multiplied by 1 / sqrt(sum_t ssq[z][t][j] / K + eps), the
 // row's sum of squares from its nsl column slices added in slice order.
-template <int WQ8, int NW, int KS, int SC = 0>
+template <int WF, int NW, int KS, int SC = 0>
 __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs, int K,
                                                  const uint8_t* __restrict__ W, const float* __restrict__ wscale,
                                                  int N, int nb, float* __restrict__ part,
                                                  const float* __restrict__ ssq = nullptr, int nsl = 0, float eps = 0.f) {
     __shared__ uint4 xb[KS * 6 * 64];  // [block][plane][half][lane]
     __shared__ float s_sq[SC ? SK_ROWS * SKL_MAX_SLICES : 1];
-    constexpr int FB = WQ8 ? 1024 : 2048, NH = WQ8 ? 1 : 2;
+    constexpr bool WQ8 = WF == WF_Q8;
+    constexpr int FB = ska_bytes<WF>();
     constexpr int NF = KS * 6 / NW;  // 16-B plane pieces per thread
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int KB = K >> 6, S = KB / KS, X = N / (16 * NW);
@@ -2759,11 +2805,9 @@ __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs
     if (SC) sqv = ssq[(size_t)z * nsl * SK_ROWS + min(tid, nsl * SK_ROWS - 1)];
     const __amdgpu_buffer_rsrc_t Wd =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(W) + (size_t)g * KB * FB, 0, KB * FB, 0x00020000);
-    u32x4 a[KS][NH];
+    SkA<WF> a[KS];
 #pragma unroll
-    for (int kb = 0; kb < KS; kb++)
-#pragma unroll
-        for (int t = 0; t < NH; t++) a[kb][t] = __builtin_amdgcn_raw_buffer_load_b128(Wd, lane * 16 + t * 1024, (kb0 + kb) * FB, 2);
+    for (int kb = 0; kb < KS; kb++) ska_load<WF>(a[kb], Wd, lane, (kb0 + kb) * FB);
 #pragma unroll
     for (int i = 0; i < NF; i++) xb[tid + i * NW * 64] = f[i];
     if (SC && tid < nsl * SK_ROWS) s_sq[tid] = sqv;
@@ -2773,14 +2817,7 @@ __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            bf16x8 af;
-            if (WQ8) {
-                const u32x4 q = a[kb][0];
-                af = t ? i8x8_bf16(q.z, q.w) : i8x8_bf16(q.x, q.y);
-            } else {
-                const u32x4 q = a[kb][t];
-                af = __builtin_bit_cast(bf16x8, make_uint4(q.x, q.y, q.z, q.w));
-            }
+            const bf16x8 af = ska_frag<WF>(a[kb], t);
 #pragma unroll
             for (int p = 0; p < 3; p++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(bf16x8, xb[((kb * 3 + p) * 2 + t) * 64 + lane]),
@@ -2814,14 +2851,15 @@ __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs
 // both, so a weight byte crosses the CU's load path once per step instead of once per row
 // block (k_skl's Z > 1 grid streams each slice twice, the second time from L2).  Same splits,
 // per-output summation order and slab layout [rb][s][16][N] as k_skl: the same bits.
-template <int WQ8, int NW, int KS, int SC = 0>
+template <int WF, int NW, int KS, int SC = 0>
 __global__ __launch_bounds__(NW * 64) void k_skl2(const uint16_t* __restrict__ xs, int K,
                                                   const uint8_t* __restrict__ W, const float* __restrict__ wscale,
                                                   int N, int nb, float* __restrict__ part,
                                                   const float* __restrict__ ssq = nullptr, int nsl = 0, float eps = 0.f) {
     __shared__ uint4 xb[2][KS * 6 * 64];  // [row block][block][plane][half][lane]
     __shared__ float s_sq[SC ? 2 * SK_ROWS * SKL_MAX_SLICES : 1];
-    constexpr int FB = WQ8 ? 1024 : 2048, NH = WQ8 ? 1 : 2;
+    constexpr bool WQ8 = WF == WF_Q8;
+    constexpr int FB = ska_bytes<WF>();
     constexpr int NF = KS * 6 / NW;  // 16-B plane pieces per thread and row block
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int KB = K >> 6, S = KB / KS, X = N / (16 * NW);
@@ -2850,11 +2888,9 @@ __global__ __launch_bounds__(NW * 64) void k_skl2(const uint16_t* __restrict__ x
     }
     const __amdgpu_buffer_rsrc_t Wd =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(W) + (size_t)g * KB * FB, 0, KB * FB, 0x00020000);
-    u32x4 a[KS][NH];
+    SkA<WF> a[KS];
 #pragma unroll
-    for (int kb = 0; kb < KS; kb++)
-#pragma unroll
-        for (int t = 0; t < NH; t++) a[kb][t] = __builtin_amdgcn_raw_buffer_load_b128(Wd, lane * 16 + t * 1024, (kb0 + kb) * FB, 2);
+    for (int kb = 0; kb < KS; kb++) ska_load<WF>(a[kb], Wd, lane, (kb0 + kb) * FB);
 #pragma unroll
     for (int z = 0; z < 2; z++)
 #pragma unroll
@@ -2870,14 +2906,7 @@ __global__ __launch_bounds__(NW * 64) void k_skl2(const uint16_t* __restrict__ x
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            bf16x8 af;
-            if (WQ8) {
-                const u32x4 q = a[kb][0];
-                af = t ? i8x8_bf16(q.z, q.w) : i8x8_bf16(q.x, q.y);
-            } else {
-                const u32x4 q = a[kb][t];
-                af = __builtin_bit_cast(bf16x8, make_uint4(q.x, q.y, q.z, q.w));
-            }
+            const bf16x8 af = ska_frag<WF>(a[kb], t);
 #pragma unroll
             for (int z = 0; z < 2; z++)
 #pragma unroll
@@ -3005,15 +3034,16 @@ __global__ __launch_bounds__(256) void k_swiglu_fplanes(const float* __restrict_
 // ============================================================================
 // k_sklx: k_skl (above) with its neighbouring row kernels folded in, for the streaming
 // encoder's ~25-row chunks where those kernels (5 us each, latency only) cost as much as the
-// projections.  Same grid, planes and MFMA loop as k_skl (bf16 weights); see SklFused.
+// projections.  Same grid, planes and MFMA loop as k_skl (bf16 weights, or the wmx4 fragment
+// plane for the batched decode step's W1|W3); see SklFused.
 // ============================================================================
-template <int NW, int KS, int PRO, int EPI>
+template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16>
 __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ xs, int K,
                                                   const uint8_t* __restrict__ W, int N, int nb, const SklFused f) {
     __shared__ uint4 xb[KS * 6 * 64];  // [block][plane][half][lane]
     __shared__ float s_ss[PRO == SKX_PRO_SCALE ? 2 * NW * 64 : 1];
     __shared__ int s_fin;
-    constexpr int FB = 2048;
+    constexpr int FB = ska_bytes<WF>();
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int KB = K >> 6, S = KB / KS, X = N / (16 * NW);
     // 1-D grid, row blocks of one weight slice on one XCD (k_skl)
@@ -3030,7 +3060,7 @@ __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ x
     const int nbz = min(nb - z * SK_ROWS, SK_ROWS);  // rows of this row block
     const __amdgpu_buffer_rsrc_t Wd =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(W) + (size_t)g * KB * FB, 0, KB * FB, 0x00020000);
-    u32x4 a[KS][2];
+    SkA<WF> a[KS];
     constexpr int NF = KS * 6 / NW;
     const size_t P = (size_t)SK_ROWS * K;
     const uint16_t* xz = xs + (size_t)z * 3 * P;
@@ -3051,10 +3081,7 @@ __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ x
         if (tid + NW * 64 < nss) ss1 = sp[tid + NW * 64];
     }
 #pragma unroll
-    for (int kb = 0; kb < KS; kb++)
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-            a[kb][t] = __builtin_amdgcn_raw_buffer_load_b128(Wd, lane * 16 + t * 1024, (kb0 + kb) * FB, 2);
+    for (int kb = 0; kb < KS; kb++) ska_load<WF>(a[kb], Wd, lane, (kb0 + kb) * FB);
 #pragma unroll
     for (int i = 0; i < NF; i++) xb[tid + i * NW * 64] = fp[i];
     if (PRO == SKX_PRO_SCALE) {
@@ -3074,8 +3101,7 @@ __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ x
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            const u32x4 q = a[kb][t];
-            const bf16x8 af = __builtin_bit_cast(bf16x8, make_uint4(q.x, q.y, q.z, q.w));
+            const bf16x8 af = ska_frag<WF>(a[kb], t);
 #pragma unroll
             for (int p = 0; p < 3; p++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(bf16x8, xb[((kb * 3 + p) * 2 + t) * 64 + lane]),
@@ -4131,9 +4157,12 @@ static hipError_t skf_cfg(const uint16_t* xs, int K, const void* W, const float*
     return hipErrorInvalidValue;
 }
 
+// mx4: Wf is the wmx4 fragment plane (vox_wmx4.h) of a bf16 matrix, every launcher below alike;
+// the geometry is the bf16 instance's, so the two give the same bits
 hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                           int ldc, hipStream_t st) {
-    if (nb < 1 || nb > SK_ROWS || N % 64 || K % 64 || !C) return hipErrorInvalidValue;
+                           int ldc, hipStream_t st, int mx4) {
+    if (nb < 1 || nb > SK_ROWS || N % 64 || K % 64 || !C || (mx4 && wscale)) return hipErrorInvalidValue;
+    if (mx4) return skf_cfg<WF_MX4>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
     return wscale ? skf_cfg<1>(xs, K, Wf, wscale, N, nb, C, ldc, st) : skf_cfg<0>(xs, K, Wf, wscale, N, nb, C, ldc, st);
 }
 
@@ -4143,10 +4172,15 @@ hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const floa
 // launch at R = 1 / 2 / 4 328.1 / 192.1 / 149.3 us, the same bits
 VOX_KB_KNOB(g_skf2_r, 4);
 hipError_t launch_gemm_skf2(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                            int ldc, hipStream_t st) {
-    if (nb <= SK_ROWS || nb > 2 * SK_ROWS || N % 64 || K % 64 || !C) return hipErrorInvalidValue;
+                            int ldc, hipStream_t st, int mx4) {
+    if (nb <= SK_ROWS || nb > 2 * SK_ROWS || N % 64 || K % 64 || !C || (mx4 && wscale)) return hipErrorInvalidValue;
     const int r = g_skf2_r;
     if ((N / 16) % r) return hipErrorInvalidValue;
+    if (mx4) {
+        if (r == 1) return skf_launch<WF_MX4, 1, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
+        if (r == 4) return skf_launch<WF_MX4, 4, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
+        return skf_launch<WF_MX4, 2, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
+    }
     if (r == 1) return wscale ? skf_launch<1, 1, 4, 2, 2>(xs, K, Wf, wscale, N, nb, C, ldc, st)
                               : skf_launch<0, 1, 4, 2, 2>(xs, K, Wf, wscale, N, nb, C, ldc, st);
     if (r == 4) return wscale ? skf_launch<1, 4, 4, 2, 2>(xs, K, Wf, wscale, N, nb, C, ldc, st)
@@ -4222,14 +4256,15 @@ static hipError_t skl2_launch(const uint16_t* xs, int K, const void* W, const fl
 
 #define SKL2_CONFIGS(X) X(4, 4) X(8, 4) X(4, 6) X(4, 8) X(8, 8)
 static hipError_t skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, const float* wscale, int N,
-                           int nb, float* part, hipStream_t st, const float* ssq, int nsl, float eps) {
+                           int nb, float* part, hipStream_t st, const float* ssq, int nsl, float eps, int mx4 = 0) {
     if (nb <= SK_ROWS || nb > 2 * SK_ROWS || K % 64 || (K / 64) % ks || N % (16 * nw) || (ks * 6) % nw ||
         (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)))
         return hipErrorInvalidValue;
 #define SKL2_X(NWW, KSS)                                                                                      \
     if (nw == NWW && ks == KSS)                                                                               \
-        return wscale ? skl2_launch<1, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps)           \
-                      : skl2_launch<0, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
+        return mx4    ? skl2_launch<WF_MX4, NWW, KSS>(xs, K, Wf, nullptr, N, nb, part, st, ssq, nsl, eps)     \
+               : wscale ? skl2_launch<1, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps)         \
+                        : skl2_launch<0, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
     SKL2_CONFIGS(SKL2_X)
 #undef SKL2_X
     return hipErrorInvalidValue;
@@ -4242,11 +4277,12 @@ hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const
 }
 
 hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb,
-                           float* part, hipStream_t st, const float* ssq, int nsl, float eps, int pair) {
+                           float* part, hipStream_t st, const float* ssq, int nsl, float eps, int pair, int mx4) {
     const int S = skl_splits(K, N);
     // ssq: each row block's nsl x 16 sums ride with its planes (nsl * 16 <= the block's threads)
-    if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)))
+    if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)) || (mx4 && wscale))
         return hipErrorInvalidValue;
+    const int wf = mx4 ? WF_MX4 : wscale ? WF_Q8 : WF_BF16;
     const int ks = K / 64 / S;
     const int nw = ks == 6 ? 4 : skl_nw_for(N, S);
     if (N % (16 * nw)) return hipErrorInvalidValue;
@@ -4254,13 +4290,14 @@ hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const floa
     // waves and splits -- the same bits, each weight fragment loaded once (QKV 12.7 -> 11.4,
     // wo 9.8 -> 8.7, W2 17.7 -> 16.7 us at 32 rows, profiles/r6_kbench_skl2.txt)
     if (pair && nb > SK_ROWS && nb <= 2 * SK_ROWS) {
-        const hipError_t e = skl2_cfg(nw, ks, xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
+        const hipError_t e = skl2_cfg(nw, ks, xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps, mx4);
         if (e != hipErrorInvalidValue) return e;
     }
 #define SKL_X(Q, NWW, KSS) \
-    if ((wscale != nullptr) == Q && nw == NWW && ks == KSS) return skl_launch<Q, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
+    if (wf == Q && nw == NWW && ks == KSS) return skl_launch<Q, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
     SKL_X(0, 4, 8) SKL_X(0, 8, 8) SKL_X(0, 4, 4) SKL_X(0, 8, 4) SKL_X(0, 4, 6)
     SKL_X(1, 4, 8) SKL_X(1, 8, 8) SKL_X(1, 4, 4) SKL_X(1, 8, 4) SKL_X(1, 4, 6)
+    SKL_X(WF_MX4, 4, 8) SKL_X(WF_MX4, 8, 8) SKL_X(WF_MX4, 4, 4) SKL_X(WF_MX4, 8, 4) SKL_X(WF_MX4, 4, 6)
 #undef SKL_X
     return hipErrorInvalidValue;
 }
@@ -4284,19 +4321,19 @@ static int sklx_nw(int N, int K) {
 
 int sklx_slices(int N, int K) { return N / (16 * sklx_nw(N, K)); }
 
-template <int NW, int KS, int PRO, int EPI>
+template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16>
 static hipError_t sklx_launch(const uint16_t* xs, int K, const void* W, int N, int nb, const SklFused& f,
                               hipStream_t st) {
     const int units = (N / (16 * NW)) * (K / (64 * KS));
     const int Z = (nb + SK_ROWS - 1) / SK_ROWS;
     const int grid = Z > 1 ? (units + 7) / 8 * 8 * Z : units;
-    hipLaunchKernelGGL((k_sklx<NW, KS, PRO, EPI>), dim3(grid), dim3(NW * 64), 0, st, xs, K,
+    hipLaunchKernelGGL((k_sklx<NW, KS, PRO, EPI, WF>), dim3(grid), dim3(NW * 64), 0, st, xs, K,
                        static_cast<const uint8_t*>(W), N, nb, f);
     return hipGetLastError();
 }
 
 hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const void* Wf, int N, int nb,
-                            const SklFused& f, hipStream_t st) {
+                            const SklFused& f, hipStream_t st, int mx4) {
     const int S = skl_splits(K);
     if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || !f.part || !f.ticket) return hipErrorInvalidValue;
     const int ks = K / 64 / S, nw = sklx_nw(N, K);
@@ -4309,9 +4346,17 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
     if (epi == SKX_EPI_QKV && (!f.q || !f.Kc || !f.Vc || !f.rope || f.hd % 2 || f.qd % f.hd || f.cap < 1 ||
                                N != f.qd + 2 * f.kvd))
         return hipErrorInvalidValue;
+#define SKX_CFG(PP, EE) SKX_X(4, 4, PP, EE) SKX_X(4, 8, PP, EE) SKX_X(8, 4, PP, EE) SKX_X(8, 8, PP, EE)
+    if (mx4) {
+        // the wmx4 fragment plane: the batched decode step's W1|W3 only
+#define SKX_X(NWW, KSS, PP, EE) \
+    if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE, WF_MX4>(xs, K, Wf, N, nb, f, st);
+        SKX_CFG(SKX_PRO_SCALE, SKX_EPI_SWIGLU)
+#undef SKX_X
+        return hipErrorInvalidValue;
+    }
 #define SKX_X(NWW, KSS, PP, EE) \
     if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE>(xs, K, Wf, N, nb, f, st);
-#define SKX_CFG(PP, EE) SKX_X(4, 4, PP, EE) SKX_X(4, 8, PP, EE) SKX_X(8, 4, PP, EE) SKX_X(8, 8, PP, EE)
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_SCALE, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_RESID)

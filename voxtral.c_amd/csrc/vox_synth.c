@@ -132,3 +132,7 @@ void vox_wmx4_plane_layout(const uint32_t *nib, const uint8_t *scl, long long ro
                            uint32_t *out) {
     vox_wmx4_plane_layout_(nib, scl, rows, K, rb, swiglu, out);
 }
+long long vox_wmx4_frag_words_of(long long N, long long K) { return vox_wmx4_frag_words(N, K); }
+void vox_wmx4_frag_layout(const uint32_t *nib, const uint8_t *scl, long long N, long long K, uint32_t *out) {
+    vox_wmx4_frag_layout_(nib, scl, N, K, out);
+}

@@ -36,6 +36,21 @@
  * chunk c fetches a group's weights and scales with one record load per K round.  Repeating
  * the scale per chunk costs 8 bits per 8 weights: 5 stored bits per weight at RB = 4 and 8
  * (6 at RB = 2, where half of the scale dword is padding).
+ *
+ * Fragment plane, laid out for the batched step's MFMA kernels (k_skl, k_skl2, k_sklx, k_skf):
+ * the A operand of a [N, K] tensor in device row order, N % 16 == 0, K % 64 == 0.  One record
+ * of VOX_WMX4_FRAG_REC = 144 dwords (576 B) per (16-row group g, 64-k block b) at dword
+ * (g * K / 64 + b) * 144.  Lane l = 16 q + j of the wave that streams the group owns row
+ * 16 g + j, k 64 b + 16 q .. 64 b + 16 q + 15 (the two 8-k halves of the bf16 fragment copy's
+ * lane, frag_off in vox_hip_dev.h):
+ *   dwords 2 l, 2 l + 1:  the row's nibble dwords of chunks 8 b + 2 q and 8 b + 2 q + 1, in the
+ *                         compact form's nibble order (half t of the lane is dword 2 l + t);
+ *   byte l of dwords 128 .. 143 (byte l & 3 of dword 128 + l / 4, little end first): the e8m0
+ *                         byte of the row's block 2 b + (q >> 1), which holds both halves.
+ * A lane fetches its block with one 8-B load at byte 8 l and one 1-B load at byte 512 + l, both
+ * contiguous across the wave; the record does not depend on how many blocks a split takes.
+ * Repeating each scale for the two lanes that share it costs 64 B per 2048 weights: 4.5 stored
+ * bits per weight (576 B against the bf16 fragment's 2048).
  */
 #ifndef VOX_WMX4_H
 #define VOX_WMX4_H
@@ -196,5 +211,35 @@ static inline void vox_wmx4_plane_layout_(const uint32_t *nib, const uint8_t *sc
                                           int swiglu, uint32_t *out) {
 #pragma omp parallel for schedule(static) num_threads(16)
     for (long long g = 0; g < rows / rb; g++) vox_wmx4_plane_groups(nib, scl, g, g + 1, K, rb, swiglu, out);
+}
+
+/* ---- fragment plane (the batched step's A operand; layout in the header comment) ---- */
+#define VOX_WMX4_FRAG_REC 144 /* dwords per (16-row group, 64-k block): 128 of nibbles, 16 of scale bytes */
+/* dwords of the fragment plane of a [N, K] tensor; 0 for a shape it does not take */
+static inline long long vox_wmx4_frag_words(long long N, long long K) {
+    if (N <= 0 || K <= 0 || N % 16 || K % 64) return 0;
+    return N / 16 * (K / 64) * VOX_WMX4_FRAG_REC;
+}
+/* compact form -> 16-row groups g0..g1 of the fragment plane */
+static inline void vox_wmx4_frag_groups(const uint32_t *nib, const uint8_t *scl, long long g0, long long g1, long long K,
+                                        uint32_t *out) {
+    const long long kc = K / 8, kb = K / VOX_WMX4_BLOCK, nb = K / 64;
+    for (long long g = g0; g < g1; g++)
+        for (long long b = 0; b < nb; b++) {
+            uint32_t *rec = out + (g * nb + b) * VOX_WMX4_FRAG_REC;
+            memset(rec + 128, 0, 64);
+            for (int l = 0; l < 64; l++) {
+                const int q = l >> 4, j = l & 15;
+                const long long r = g * 16 + j, c = b * 8 + 2 * q;
+                rec[2 * l] = nib[r * kc + c];
+                rec[2 * l + 1] = nib[r * kc + c + 1];
+                rec[128 + (l >> 2)] |= (uint32_t)scl[r * kb + 2 * b + (q >> 1)] << (8 * (l & 3));
+            }
+        }
+}
+static inline void vox_wmx4_frag_layout_(const uint32_t *nib, const uint8_t *scl, long long N, long long K, uint32_t *out) {
+    if (!vox_wmx4_frag_words(N, K)) return;
+#pragma omp parallel for schedule(static) num_threads(16)
+    for (long long g = 0; g < N / 16; g++) vox_wmx4_frag_groups(nib, scl, g, g + 1, K, out);
 }
 #endif

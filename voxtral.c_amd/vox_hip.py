@@ -89,6 +89,8 @@ EXPORTS = [
     "vox_hip_model_ada_scale", "vox_hip_model_set_kv_fp16", "vox_hip_stream_kv_fp16",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
+    "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
+    "vox_hip_skinny_wmx4",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -131,6 +133,10 @@ def lib():
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
         "vox_hip_set_wmx4": (I, [I]), "vox_hip_wmx4": (I, []), "vox_hip_model_wmx4_stats": (I, [P, P]),
+        "vox_hip_set_wmx4_batch": (I, [I]), "vox_hip_wmx4_batch": (I, []),
+        "vox_hip_model_wmx4_batch_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_batch_set_wmx4": (I, [P, I]),
+        "vox_hip_skinny_wmx4": (I, [I, I, P, fp, I, fp, I, I]),
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -212,6 +218,34 @@ def wmx4() -> int:
     return lib().vox_hip_wmx4()
 
 
+def set_wmx4_batch(on: bool):
+    """wmx4 fragment planes for the batched MFMA step, for models created from now on (on top
+    of wmx4 mode 1 or 2; include/voxtral_hip.h)"""
+    if lib().vox_hip_set_wmx4_batch(int(bool(on))) != 0:
+        _err("set_wmx4_batch")
+
+
+def wmx4_batch() -> int:
+    return lib().vox_hip_wmx4_batch()
+
+
+def skinny_wmx4(W_bf16, x, fmt: int, head: bool = False) -> np.ndarray:
+    """Test entry: y [nb, N] = x [nb, K] @ W^T for nb <= 32 rows through the batched step's
+    launchers (vox_hip_skinny_wmx4): the projection kernels and their slab sum, or the LM-head
+    kernel (head).  fmt 0: the bf16 fragment-major copy, fmt 1: the wmx4 fragment plane (raises
+    for a matrix that is not MXFP4-valued)"""
+    init()
+    W = np.ascontiguousarray(W_bf16, np.uint16)
+    xv = np.ascontiguousarray(x, np.float32)
+    N, K = W.shape
+    assert xv.ndim == 2 and xv.shape[1] == K
+    nb = xv.shape[0]
+    y = np.empty((nb, N), np.float32)
+    if lib().vox_hip_skinny_wmx4(N, K, W.ctypes.data, fptr(xv), nb, fptr(y), int(fmt), int(bool(head))) != 0:
+        _err("skinny_wmx4")
+    return y
+
+
 def set_gemmf_wait(ticks: int) -> int:
     """the encoder GEMM owner's wait per partial tile (100 MHz ticks; < 0: always recompute);
     returns the previous value (a diagnostic knob for the tests)"""
@@ -267,6 +301,14 @@ class Model:
         if lib().vox_hip_model_wmx4_stats(self.h, ctypes.byref(st)) != 0:
             _err("wmx4_stats")
         return {name: getattr(st, name) for name, _ in WMx4StatsC._fields_}
+
+    def wmx4_batch_stats(self) -> dict:
+        """The wmx4 fragment planes the batched step may stream (vox_hip_model_wmx4_batch_stats):
+        tensors, plane bytes, the bf16 bytes they stand for, host microseconds"""
+        out = (ctypes.c_longlong * 4)()
+        if lib().vox_hip_model_wmx4_batch_stats(self.h, out) != 0:
+            _err("wmx4_batch_stats")
+        return dict(zip(("tensors", "plane_bytes", "bf16_bytes", "host_us"), (int(v) for v in out)))
 
     def ada_scale(self):
         c = self.cfg
@@ -656,6 +698,12 @@ class Batch:
         R-row GEMV step.  Returns 0, or -1 with last_error() set (another value, a Q8 model, a
         begun call)."""
         return lib().vox_hip_batch_set_gemv_rows(self.h, int(max_rows))
+
+    def set_wmx4(self, on: bool) -> int:
+        """vox_hip_batch_set_wmx4: the MFMA step streams the wmx4 fragment planes (on) or the bf16
+        fragment copies (off); the same bits.  Returns 0, or -1 with last_error() set (the model
+        has no fragment planes, a begun call)."""
+        return lib().vox_hip_batch_set_wmx4(self.h, int(bool(on)))
 
     def gemv_stats(self) -> tuple:
         """vox_hip_batch_gemv_stats: (max_rows, GEMV step replays, live rows, GEMV captures)"""

@@ -160,6 +160,9 @@ def synth_lib():
         lib.vox_wmx4_plane_words_of.restype = LL
         lib.vox_wmx4_plane_layout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, LL, LL, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_void_p]
+        lib.vox_wmx4_frag_words_of.argtypes = [LL, LL]
+        lib.vox_wmx4_frag_words_of.restype = LL
+        lib.vox_wmx4_frag_layout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, LL, LL, ctypes.c_void_p]
         _synth = lib
     return _synth
 
