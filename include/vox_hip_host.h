@@ -92,6 +92,12 @@ void vh_stream_stats(const vh_stream_t *s, vh_stats_t *out);
  * rows still pending */
 int vh_stream_pending(vh_stream_t *s);
 
+/* The decoder KV ring element of the streams vh_stream_init makes from now on: 0 f32 (default),
+ * 1 IEEE half, 2 FP8 E4M3 (vox_hip_model_set_kv_dtype, voxtral_hip.h: no scale, saturating,
+ * quality not evaluated).  0, or -1 (vh_last_error).  vh_stream_reset keeps a stream's type. */
+int vh_set_kv_dtype(vh_ctx_t *ctx, int dtype);
+int vh_stream_kv_dtype(const vh_stream_t *s);
+
 /* The model behind a context (for the model-level calls of voxtral_hip.h, such as
  * vox_hip_model_wmx4_stats); the context keeps owning it. */
 vox_hip_model_t *vh_model(const vh_ctx_t *ctx);

@@ -105,6 +105,18 @@ int vox_hip_model_ada_scale(vox_hip_model_t *m, float *out);
  * default f32 ring is the CPU reference's (voxtral_decoder.c:232-234).  head_dim 128 only
  * (Voxtral's); returns 0, or -1 (vox_hip_last_error) for another head_dim. */
 int vox_hip_model_set_kv_fp16(vox_hip_model_t *m, int on);
+/* The decoder KV ring element of streams created after this call: 0 f32 (the default), 1 IEEE
+ * half (what vox_hip_model_set_kv_fp16(m, 1) selects), 2 FP8 E4M3 (no reference counterpart).
+ * FP8: one byte per element, OCP "e4m3fn" (the gfx950 native format) by the rule of
+ * csrc/vox_kv8.h -- stores clamp to +-448 (the ring saturates; there is NO scale, a per-layer
+ * power-of-two scale needs a real checkpoint to calibrate against and is not built), round to
+ * nearest with ties to even, keep subnormals; loads widen exactly; all attention arithmetic
+ * stays f32 in the f32 ring's order.  A quarter of the f32 ring's bytes per step and per
+ * stream.  Its effect on transcripts is NOT evaluated.  Opt-in: off unless VOX_HIP_KV_FP8 is
+ * set nonzero at model creation (it wins over VOX_DECODER_KV_FP16) or dtype = 2 is passed.
+ * The encoder KV stays f32.  head_dim 128 only for 1 and 2; returns 0, or -1
+ * (vox_hip_last_error) for another head_dim or dtype. */
+int vox_hip_model_set_kv_dtype(vox_hip_model_t *m, int dtype);
 /* wpack13 (no reference counterpart): at creation every bf16 matrix of the single-stream
  * decode step (Q|K|V, wo, W1|W3, W2 per decoder layer, and the LM head) whose nonzero
  * exponents span at most 30 binades also gets a 13-bit-per-weight copy that the M = 1 GEMV
@@ -216,6 +228,18 @@ vox_hip_stream_t *vox_hip_stream_create(vox_hip_model_t *m);
 void vox_hip_stream_free(vox_hip_stream_t *s);
 /* 1 if the stream's decoder KV rings hold IEEE half (vox_hip_model_set_kv_fp16), else 0 */
 int vox_hip_stream_kv_fp16(const vox_hip_stream_t *s);
+/* the stream's decoder KV ring element: 0 f32, 1 IEEE half, 2 FP8 E4M3 (vox_hip_model_set_kv_dtype) */
+int vox_hip_stream_kv_dtype(const vox_hip_stream_t *s);
+/* Tests / diagnostics: the raw ring elements of decoder layer `layer` at logical positions
+ * [first_logical_pos, first_logical_pos + n), [n][dec_kv_heads * dec_head_dim] in the stream's
+ * element type (4, 2 or 1 bytes each) to k_out / v_out (either may be null).  Waits for the
+ * stream's queue.  -1 (vox_hip_last_error) for positions not appended yet or already
+ * overwritten by the ring's wrap. */
+int vox_hip_stream_read_kv(vox_hip_stream_t *s, int layer, int first_logical_pos, int n, void *k_out, void *v_out);
+/* Tests: the kernels' own FP8 ring store and load helpers run on the device over x[0..n):
+ * codes[i] = the byte a ring slot would hold, back[i] = the f32 the attention kernels read from
+ * it (either may be null).  Must equal csrc/vox_kv8.h for every input. */
+int vox_hip_kv8_convert(const float *x, int n, uint8_t *codes, float *back);
 /* stream_reset_full_state (voxtral.c:786-814) / stream_reset_decoder_state (:766-783) */
 int vox_hip_stream_reset(vox_hip_stream_t *s);
 int vox_hip_stream_reset_decoder(vox_hip_stream_t *s);

@@ -1263,6 +1263,39 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "attnkv")) {
+        // decode attention per ring element type (f32 / half / FP8 E4M3) as the decode step sees it:
+        // 26 layers' rings, one launch per layer in turn, the default grids (256 keys: k_attn_short)
+        const int NLd = 26, rcap = 8192 + 64;
+        const char* tn[3] = {"f32", "half", "fp8"};
+        for (int kvt : {0, 1, 2}) {
+            const size_t esz = kvt == 2 ? 1 : kvt == 1 ? 2 : 4, per = (size_t)rcap * DKV;
+            std::vector<float*> Ks(NLd), Vs(NLd);
+            for (int l = 0; l < NLd; l++) {
+                Ks[l] = (float*)dmalloc(per * esz, 1);
+                Vs[l] = (float*)dmalloc(per * esz, 1);
+            }
+            for (int L : {256, 4096, 8192}) {
+                int st4[4] = {L - 1, 0, 0, 0};
+                CK(hipMemcpy(state, st4, 16, hipMemcpyHostToDevice));
+                int splits = 1;
+                while (splits * ATT_BLOCK_KEYS < L) splits *= 2;
+                int l = 0;
+                char nm[96];
+                snprintf(nm, sizeof nm, "attn decode L=%d %s 26 layers", L, tn[kvt]);
+                add(nm, timeit([&] {
+                        CK(launch_attn_decode(HD, x, Ks[l % NLd], Vs[l % NLd], rcap, state, 0, 8192, 0.088f, H, KVH,
+                                              part, y, splits, st, kvt));
+                        l++;
+                    }, 260, st), (double)L * DKV * 2 * esz);
+            }
+            for (int l = 0; l < NLd; l++) {
+                CK(hipFree(Ks[l]));
+                CK(hipFree(Vs[l]));
+            }
+        }
+        return 0;
+    }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "attn")) {
         // long-context decode attention as the decode step sees it: 26 layers' rings (f32:
         // 1.76 GB, half: 0.88 GB, far past the 256 MB MALL), one launch per layer in turn

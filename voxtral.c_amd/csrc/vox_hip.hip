@@ -192,7 +192,7 @@ struct vox_hip_model {
     std::vector<DecFragD> dfrag;   // fragment-major decoder matrices (empty until a batch or a bf16 prefill)
     std::vector<DecFragD> efrag;   // fragment-major encoder matrices (empty until a short chunk)
     uint8_t* lm_frag;              // fragment-major LM head (tied embeddings)
-    int kv16;                      // decoder KV rings of streams created from now on in IEEE half
+    int kvt;                       // decoder KV ring element of streams created from now on (KV_F32 / KV_F16 / KV_FP8)
     WPackD plm;                    // wpack13 copy of the LM head
     int wpack;                     // VOX_HIP_WPACK (default 1), read once at creation
     vox_hip_wpack_stats_t wstats;
@@ -519,7 +519,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         // the reference's VOX_DECODER_KV_FP16 (voxtral.c:189-190); opt-in here (unset = f32,
         // the CPU reference's cache), vox_hip_model_set_kv_fp16 overrides
         const char* e = getenv("VOX_DECODER_KV_FP16");
-        m->kv16 = (e && atoi(e) != 0 && cfg->dec_head_dim == 128) ? 1 : 0;
+        m->kvt = (e && atoi(e) != 0 && cfg->dec_head_dim == 128) ? KV_F16 : KV_F32;
+        // the one-byte rings (FP8 E4M3, vox_kv8.h): opt-in, before the 16-bit variable when both
+        // are set, head_dim 128 only like it; vox_hip_model_set_kv_dtype overrides
+        const char* e8 = getenv("VOX_HIP_KV_FP8");
+        if (e8 && atoi(e8) != 0 && cfg->dec_head_dim == 128) m->kvt = KV_FP8;
     }
     m->conv0_w = m->conv1_w = nullptr;
     m->ad0 = m->ad1 = m->tok_emb = nullptr;
@@ -730,7 +734,15 @@ extern "C" int vox_hip_set_gemmf_wait(int ticks) { return set_gemmf_wait(ticks);
 
 extern "C" int vox_hip_model_set_kv_fp16(vox_hip_model_t* m, int on) {
     if (on && m->c.dec_head_dim != 128) return set_err("16-bit decoder KV: head_dim 128 only (got %d)", m->c.dec_head_dim);
-    m->kv16 = on ? 1 : 0;
+    m->kvt = on ? KV_F16 : KV_F32;
+    return 0;
+}
+
+extern "C" int vox_hip_model_set_kv_dtype(vox_hip_model_t* m, int dtype) {
+    if (dtype < KV_F32 || dtype > KV_FP8) return set_err("decoder KV element type: 0 (f32), 1 (half) or 2 (fp8), got %d", dtype);
+    if (dtype != KV_F32 && m->c.dec_head_dim != 128)
+        return set_err("%s decoder KV: head_dim 128 only (got %d)", dtype == KV_FP8 ? "FP8" : "16-bit", m->c.dec_head_dim);
+    m->kvt = dtype;
     return 0;
 }
 
@@ -756,9 +768,9 @@ struct vox_hip_stream {
     unsigned long long uid;  // unique per stream object ever created (batch graph keys)
     hipStream_t st;
     // rolling KV caches [layers][cap][kv_dim]
-    float *ek, *ev, *dk, *dv;   // dk / dv: f32 elements, or IEEE half ones when kv16
+    float *ek, *ev, *dk, *dv;   // dk / dv: elements of type kvt (f32, IEEE half or FP8 E4M3 bytes)
     int ecap, dcap;
-    int kv16;
+    int kvt;
     long long enc_pos;  // next encoder logical position
     // conv stem
     float *mel_p, *mel_tail, *c0_p, *c0_tail, *c0_res, *im2col;
@@ -880,12 +892,13 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     const int EQ = c.enc_heads * c.enc_head_dim;
     s->ecap = c.enc_window + ENC_SUB + 64;
     s->dcap = c.dec_window + DEC_SLACK;
-    s->kv16 = m->kv16;
+    s->kvt = m->kvt;
     TRYH(dalloc(&s->ek, (size_t)c.enc_layers * s->ecap * EKV));
     TRYH(dalloc(&s->ev, (size_t)c.enc_layers * s->ecap * EKV));
-    // (dalloc counts floats: a half ring takes half of them; DKV is even)
-    TRYH(dalloc(&s->dk, (size_t)c.dec_layers * s->dcap * DKV / (s->kv16 ? 2 : 1)));
-    TRYH(dalloc(&s->dv, (size_t)c.dec_layers * s->dcap * DKV / (s->kv16 ? 2 : 1)));
+    // (dalloc counts floats: a half ring takes half of them, a one-byte ring a quarter; the
+    // narrow modes have head_dim 128, so DKV is a multiple of 4)
+    TRYH(dalloc(&s->dk, (size_t)c.dec_layers * s->dcap * DKV / (4 / kv_esize(s->kvt))));
+    TRYH(dalloc(&s->dv, (size_t)c.dec_layers * s->dcap * DKV / (4 / kv_esize(s->kvt))));
     TRYH(dalloc(&s->mel_tail, (size_t)2 * c.mel_bins));
     TRYH(dalloc(&s->c0_tail, (size_t)2 * c.enc_dim));
     TRYH(dalloc(&s->c0_res, (size_t)c.enc_dim));
@@ -936,13 +949,14 @@ static hipError_t queue_high_priority(hipStream_t* q) {
     return hipStreamCreateWithPriority(q, hipStreamNonBlocking, hi);
 }
 
-extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s) { return s->kv16; }
+extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s) { return s->kvt == KV_F16; }
+extern "C" int vox_hip_stream_kv_dtype(const vox_hip_stream_t* s) { return s->kvt; }
 
 // layer l's decoder K or V ring (base = s->dk or s->dv) in the stream's element type
 static float* dec_ring(const vox_hip_stream_t* s, float* base, int l) {
     const vox_hip_config_t& c = s->m->c;
     const size_t elems = (size_t)l * s->dcap * c.dec_kv_heads * c.dec_head_dim;
-    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * (s->kv16 ? 2 : 4));
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * kv_esize(s->kvt));
 }
 
 extern "C" void vox_hip_stream_free(vox_hip_stream_t* s) {
@@ -2155,9 +2169,9 @@ static int run_decoder_rows(vox_hip_stream_t* s, float* x, int n, int pos0, cons
         return dec_layers_gemmf(s, GemmfQ{st, s->gws, s->gws_n, s->gflags, &s->gepoch}, x, n, [&](int l) -> int {
             float* Kc = dec_ring(s, s->dk, l);
             float* Vc = dec_ring(s, s->dv, l);
-            CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kv16));
+            CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kvt));
             CK(launch_attn_rows_mf(hd, s->qd_, DQ, Kc, Vc, s->dcap, s->attd, DQ, n, H, KVH, pos0, 0, c.dec_window, scale,
-                                   st, s->gws, s->gws_n, s->dpa, s->kv16));
+                                   st, s->gws, s->gws_n, s->dpa, s->kvt));
             return 0;
         });
     }
@@ -2167,9 +2181,9 @@ static int run_decoder_rows(vox_hip_stream_t* s, float* x, int n, int pos0, cons
         float* Vc = dec_ring(s, s->dv, l);
         CK(launch_rmsnorm_rows(x, DD, s->xnd, DD, L.attn_norm, nullptr, n, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_STORE, 3, s->xnd, DD, L.wqkv, L.sqkv, DD, n, DQ + 2 * DKV, nullptr, s->qkvd, DQ + 2 * DKV, st, s->gws, s->gws_n));
-        CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kv16));
+        CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kvt));
         CK(launch_attn_rows_mf(hd, s->qd_, DQ, Kc, Vc, s->dcap, s->attd, DQ, n, H, KVH, pos0, 0, c.dec_window, scale, st,
-                             s->gws, s->gws_n, nullptr, s->kv16));
+                             s->gws, s->gws_n, nullptr, s->kvt));
         CK(launch_gemm(EPI_RESID, 3, s->attd, DQ, L.wo, L.so, DQ, n, DD, nullptr, x, DD, st, s->gws, s->gws_n));
         CK(launch_rmsnorm_rows(x, DD, s->xnd, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, n, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_SWIGLU, 3, s->xnd, DD, L.w13, L.s13, DD, n, 2 * DH, nullptr, s->gated, DH, st, s->gws, s->gws_n));
@@ -2203,13 +2217,13 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         a.qd = DQ; a.kvd = DKV; a.hd = hd;
         a.state = state; a.pos = pos;
         a.rope = state ? m->rope_dec : rope_row - (size_t)pos * hd;
-        a.Kc = Kc; a.Vc = Vc; a.cap = s->dcap; a.kv16 = s->kv16;
+        a.Kc = Kc; a.Vc = Vc; a.cap = s->dcap; a.kvt = s->kvt;
         wpack_args(a, L.pqkv);
         wmx4_args(a, L.mqkv);
         CK(launch_gemv(PRO_NORM, EPI_QKV, a, st));
         // attention over the last min(pos+1, window) keys (decoder.c:724-733)
         CK(launch_attn_decode(hd, s->qd_, Kc, Vc, s->dcap, state, pos, c.dec_window, scale, H, KVH,
-                              s->part, s->attd, splits, st, s->kv16));
+                              s->part, s->attd, splits, st, s->kvt));
         // wo + residual (decoder.c:735-740)
         memset(&a, 0, sizeof a);
         a.x = s->attd; a.K = DQ; a.W = L.wo; a.wscale = L.so; a.rows = DD; a.y = s->xd;
@@ -2509,6 +2523,68 @@ extern "C" int vox_hip_stream_state(vox_hip_stream_t* s, int* out6) {
     out6[4] = s->eos_seen;
     out6[5] = s->n_generated;
     return 0;
+}
+
+// Raw ring elements of logical positions [first, first + n) of one decoder layer, in the
+// stream's element type, [n][kv_heads * head_dim] each (k_out / v_out may be null).  The
+// positions must still be resident: appended (< the stream's position) and not overwritten
+// by the ring's wrap (>= position - ring capacity).  Waits for the stream's queue.
+extern "C" int vox_hip_stream_read_kv(vox_hip_stream_t* s, int layer, int first, int n, void* k_out, void* v_out) {
+    const vox_hip_config_t& c = s->m->c;
+    const int pos = s->h_state[0];
+    if (layer < 0 || layer >= c.dec_layers) return set_err("read_kv: layer %d of %d", layer, c.dec_layers);
+    if (n < 0 || first < 0 || (long long)first + n > pos)
+        return set_err("read_kv: positions [%d, %d + %d) not appended yet (stream at %d)", first, first, n, pos);
+    if (first < pos - s->dcap)
+        return set_err("read_kv: position %d already overwritten (stream at %d, ring of %d)", first, pos, s->dcap);
+    CK(hipStreamSynchronize(s->st));
+    const size_t row = (size_t)c.dec_kv_heads * c.dec_head_dim * kv_esize(s->kvt);
+    void* outs[2] = {k_out, v_out};
+    float* bases[2] = {s->dk, s->dv};
+    for (int w = 0; w < 2; w++) {
+        if (!outs[w]) continue;
+        const char* ring = reinterpret_cast<const char*>(dec_ring(s, bases[w], layer));
+        for (int i = 0; i < n;) {
+            const int slot = (first + i) % s->dcap;
+            const int run = std::min(n - i, s->dcap - slot);  // up to the ring's end
+            CK(hipMemcpy(static_cast<char*>(outs[w]) + (size_t)i * row, ring + (size_t)slot * row, (size_t)run * row,
+                         hipMemcpyDeviceToHost));
+            i += run;
+        }
+    }
+    return 0;
+}
+
+// The kernels' own FP8 ring store (element pairs and single elements) and load helpers over n
+// values on the device: codes[i] = what a ring slot would hold for x[i], back[i] = what the
+// attention kernels read from it (tests against vox_kv8.h; codes / back may be null).
+extern "C" int vox_hip_kv8_convert(const float* x, int n, uint8_t* codes, float* back) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (n < 0 || (n > 0 && !x)) return set_err("kv8_convert: bad arguments");
+    if (n == 0) return 0;
+    const size_t np = ((size_t)n + 7) / 8 * 8;  // whole 8-element groups (the kernel's unit)
+    float *dx = nullptr, *db = nullptr;
+    uint8_t* dc = nullptr;
+    int rc = -1;
+    do {
+        if (hipMalloc((void**)&dx, np * 4) != hipSuccess || hipMalloc((void**)&db, np * 4) != hipSuccess ||
+            hipMalloc((void**)&dc, np) != hipSuccess) {
+            set_err("kv8_convert: out of device memory");
+            break;
+        }
+        if (hipMemset(dx, 0, np * 4) != hipSuccess || hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_kv8_convert(dx, (int)(np / 8), dc, db, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            (codes && hipMemcpy(codes, dc, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (back && hipMemcpy(back, db, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
+            set_err("kv8_convert: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+        rc = 0;
+    } while (0);
+    if (dx) hipFree(dx);
+    if (db) hipFree(db);
+    if (dc) hipFree(dc);
+    return rc;
 }
 
 extern "C" int vox_hip_stream_set_profiling(vox_hip_stream_t* s, int enable) {
@@ -3027,21 +3103,21 @@ struct vox_hip_batch {
     // in device memory and mirrored in pinned host memory (one copy each way per step chunk)
     BatchSlot* slots;
     BatchSlot* hslots;
-    // step graphs [kv16][slot bucket 1, 2, 4, 8, 16, 32][attention splits bucket]: their kernel
+    // step graphs [ring element type][slot bucket 1, 2, 4, 8, 16, 32][attention splits bucket]: their kernel
     // arguments point at the slot table and the batch's buffers only, so they stay valid as
     // streams come and go; captured again only when the model's rope table moves
-    // (wmx4: [2 wmx4 + kv16], the two weight sources keep graphs of their own)
-    hipGraphExec_t gexec[4][6][STEP_GRAPHS];
+    // (wmx4: [3 wmx4 + element type], the two weight sources keep graphs of their own)
+    hipGraphExec_t gexec[6][6][STEP_GRAPHS];
     int grope_gen;
     // the MFMA step streams the wmx4 fragment planes of the tensors that have one
     // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
     int wmx4;
     // the R-row GEMV step (batch_step_gemv): steps whose slot bucket is <= gemv_rows take it
-    // (0: off).  Its graphs [kv16][bucket 1, 2, 4, 8][splits bucket] have keys of their own, so
+    // (0: off).  Its graphs [element type][bucket 1, 2, 4, 8][splits bucket] have keys of their own, so
     // the mode changes between calls without a capture being dropped.
     int gemv_rows;
     float* hid;      // SwiGLU rows [GEMVR_MAX_ROWS][dec_hidden] (allocated when the mode is first set)
-    hipGraphExec_t gvexec[2][4][STEP_GRAPHS];
+    hipGraphExec_t gvexec[3][4][STEP_GRAPHS];
     long long n_gemv_replays, n_gemv_rows, n_gemv_captures;
     // rows of the last call (b->logits row i = stream luid[i], from its last step when llive[i])
     unsigned long long luid[VOX_MAX_BATCH];
@@ -3057,7 +3133,7 @@ struct vox_hip_batch {
     // a call begun by batch_begin and not yet finished (vox_hip_batch_begin_rows /
     // vox_hip_batch_finish): its streams, outputs and the steps left after the chunk in flight
     struct {
-        int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kv16, done, k;
+        int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kvt, done, k;
         int gemv;  // the call's steps take the GEMV path
         vox_hip_stream_t* streams[VOX_MAX_BATCH];
         int* tokens_out;
@@ -3208,7 +3284,7 @@ static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const ui
 }
 
 // one batched step over slots 0..nb-1 of the slot table (their input rows already in b->x)
-static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16, int wmx4) {
+static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4) {
     vox_hip_model_t* m = b->m;
     auto mx = [&](const WMx4D& M) -> const uint8_t* { return wmx4 ? M.frag : nullptr; };
     const vox_hip_config_t& c = m->c;
@@ -3216,7 +3292,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16, int wmx4
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
     const float scale = 1.0f / sqrtf((float)hd);
     const int cap = c.dec_window + DEC_SLACK;
-    const size_t ring_layer = (size_t)cap * DKV * (kv16 ? 2 : 4);
+    const size_t ring_layer = (size_t)cap * DKV * kv_esize(kvt);
     hipStream_t st = b->st;
     AttnPtrs ap;
     memset(&ap, 0, sizeof ap);
@@ -3243,7 +3319,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16, int wmx4
         // launch; past 256 keys the last key-range block of a kv head merges the partials)
         AttnFuse af;
         af.qkv = b->part; af.S = skl_splits(DD, DQ + 2 * DKV); af.N = DQ + 2 * DKV; af.rope = m->rope_dec; af.xs = b->xp_q;
-        CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kv16));
+        CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         CK(batch_gemm(b->xp_q, DQ, F.wo, mx(L.mo), L.so, DD, nb, b->part, st));
         CK(launch_resid_xw_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, b->xp_d, b->part,
                                    skl_splits(DQ, DD), nullptr, b->ssq, st));
@@ -3292,14 +3368,14 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kv16, int wmx4
 // the launches the rows live in b->x (residual stream, updated in place), b->q, b->att and
 // b->hid; attention is the slot-table kernel of the single-stream step.  b->x is complete
 // before and after either step, so the two may alternate from one call to the next.
-static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kv16) {
+static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
     const float scale = 1.0f / sqrtf((float)hd);
     const int cap = c.dec_window + DEC_SLACK;
-    const size_t ring_layer = (size_t)cap * DKV * (kv16 ? 2 : 4);
+    const size_t ring_layer = (size_t)cap * DKV * kv_esize(kvt);
     hipStream_t st = b->st;
     AttnPtrs ap;
     memset(&ap, 0, sizeof ap);
@@ -3317,11 +3393,11 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kv16) {
         memset(&a, 0, sizeof a);
         a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.wqkv; a.g.rows = DQ + 2 * DKV;
         a.g.norm_w = L.attn_norm; a.g.eps = c.dec_eps; a.g.y = b->q; a.ldy = DQ;
-        a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kv16 = kv16;
+        a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kvt = kvt;
         a.slots = b->slots; a.ring_off = ap.ring_off;
         wpack_args(a.g, L.pqkv);
         CK(launch_gemvr(PRO_NORM, EPI_QKV, nb, a, st));
-        CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kv16));
+        CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         // wo + residual
         memset(&a, 0, sizeof a);
         a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
@@ -3407,9 +3483,9 @@ static int slot_bucket(int n, int* g) {
 
 // `steps` batched steps over slots 0..nb-1: replays of the bucket's step graph (captured the
 // first time, and again only when the rope table moved), or eager launches
-static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kv16, int steps, int gemv) {
+static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
-    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kv16) : batch_step(b, nb, splits, kv16, wmx4); };
+    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kvt) : batch_step(b, nb, splits, kvt, wmx4); };
     if (gemv) b->n_gemv_replays += steps;
     if (!use_graphs()) {
         for (int k = 0; k < steps; k++)
@@ -3421,7 +3497,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = gemv ? b->gvexec[kv16][gb][gi] : b->gexec[2 * wmx4 + kv16][gb][gi];
+    hipGraphExec_t& ge = gemv ? b->gvexec[kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
@@ -3471,12 +3547,12 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
     // more prompts than one pass holds (ENC_SUB rows: 26 prompts of 39 rows): stacked passes of
     // as many as fit
     const int per = std::max(1, ENC_SUB / np);
-    if (B > per && !ss[0]->kv16) {
+    if (B > per && !ss[0]->kvt) {
         for (int i0 = 0; i0 < B; i0 += per)
             if (batch_prefill(b, ss + i0, std::min(per, B - i0), bounded)) return -1;
         return 0;
     }
-    if ((B == 1 && !bounded) || ss[0]->kv16 || B * np > ENC_SUB) {
+    if ((B == 1 && !bounded) || ss[0]->kvt || B * np > ENC_SUB) {
         for (int i = 0; i < B; i++) {
             if (stream_prefill(ss[i])) return -1;
             CK(hipStreamSynchronize(ss[i]->st));
@@ -3567,13 +3643,13 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     const int prompt_len = 1 + 32 + m->delay_tokens;
     for (int i = 0; i < n; i++) {
         if (!streams[i] || streams[i]->m != m) return set_err("batch streams must share the batch's model");
-        if (streams[i]->kv16 != streams[0]->kv16)
-            return set_err("batch streams must share the decoder KV element type (vox_hip_model_set_kv_fp16)");
+        if (streams[i]->kvt != streams[0]->kvt)
+            return set_err("batch streams must share the decoder KV element type (vox_hip_model_set_kv_dtype)");
         for (int j = 0; j < i; j++)
             if (streams[j] == streams[i]) return set_err("stream listed twice in a batch");
         counts_out[i] = 0;
     }
-    const int kv16 = streams[0]->kv16;
+    const int kvt = streams[0]->kvt;
     b->n_calls++;
     b->lnb = 0;
     // every member's queue is idle before the batch queue touches its buffers (adapter rows
@@ -3646,7 +3722,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     const int k = std::min(STEP_BATCH, K);
     // buckets of up to gemv_rows slots take the R-row GEMV step (vox_hip_batch_set_gemv_rows)
     const int gemv = b->gemv_rows && nb <= b->gemv_rows;
-    if (batch_run(b, nb, gb, gi, splits, kv16, k, gemv)) return -1;
+    if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv)) return -1;
     CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
     auto& cl = b->call;
     cl.active = 1;
@@ -3660,7 +3736,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     cl.gb = gb;
     cl.gi = gi;
     cl.splits = splits;
-    cl.kv16 = kv16;
+    cl.kvt = kvt;
     cl.done = 0;
     cl.k = k;
     cl.tokens_out = tokens_out;
@@ -3699,7 +3775,7 @@ static int batch_finish(vox_hip_batch_t* b) {
         }
         if (!any || done >= K) break;
         k = std::min(STEP_BATCH, K - done);
-        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kv16, k, cl.gemv)) return -1;
+        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv)) return -1;
         CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
     }
     // 4. host mirrors

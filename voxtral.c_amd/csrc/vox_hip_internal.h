@@ -44,15 +44,19 @@ struct GemvArgs {
     const float* rope;     // rope table [pos][hd]
     const int* state;      // device state (state[0] = logical position) or null
     int pos;               // logical position when state == null
-    float* Kc;             // decoder ring (f32, or IEEE half when kv16)
+    float* Kc;             // decoder ring (elements of type kvt)
     float* Vc;
     int cap;
-    int kv16 = 0;
+    int kvt = 0;           // KV_F32 / KV_F16 / KV_FP8
     // EPI_LOGITS(_ALT)
     float* part_val;
     int* part_idx;
     float* part_alt;       // EPI_LOGITS_ALT: [blocks][ALT_PART]
 };
+
+// decoder KV ring element types (vox_hip_model_set_kv_dtype); the element's size in bytes
+enum { KV_F32 = 0, KV_F16 = 1, KV_FP8 = 2 };
+static inline size_t kv_esize(int kvt) { return kvt == KV_FP8 ? 1 : kvt == KV_F16 ? 2 : 4; }
 
 constexpr int VOX_MAX_BATCH = 32;    // streams per batched decode step (two 16-row blocks of the MFMA B operand)
 
@@ -101,8 +105,9 @@ struct AttnPtrs {
     const BatchSlot* slots = nullptr;
     size_t ring_off = 0;
 };
-// Kc / Vc of the decoder rings point at f32 elements, or at IEEE half ones in the 16-bit
-// mode (the kv16 argument of the launchers, VOX_DECODER_KV_FP16)
+// Kc / Vc of the decoder rings point at f32 elements, at IEEE half ones in the 16-bit mode
+// (VOX_DECODER_KV_FP16) or at FP8 E4M3 bytes in the one-byte mode (VOX_HIP_KV_FP8, vox_kv8.h):
+// the kvt argument of the launchers
 
 // batched decode attention with the QKV epilogue folded in (k_attn_decode<.., FUSE = 1>):
 // RoPE of q / k and the KV append read the QKV projection's split-K slabs, and the output
@@ -131,11 +136,11 @@ hipError_t launch_gemm(int epi, int nsplit, const float* A, int lda, const void*
                        const float* wscale, int K, int M, int N, const float* bias, float* C,
                        int ldc, hipStream_t st, float* ws = nullptr, size_t ws_elems = 0);
 hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, const float* rope,
-                          int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st, int kv16 = 0);
+                          int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st, int kvt = 0);
 hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc, const float* Vc,
                              int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0,
                              int k_first, int window, float scale, hipStream_t st, float* ws = nullptr,
-                             size_t ws_elems = 0, uint16_t* xs = nullptr, int kv16 = 0);
+                             size_t ws_elems = 0, uint16_t* xs = nullptr, int kvt = 0);
 // xs: the output also (or only, through the combine kernel) as fragment-major planes
 // the skinny encoder's QKV slabs (+ bias) -> RoPE'd q rows and the K/V ring slots (one pass)
 hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bias, int qd, int kvd, int hd,
@@ -155,15 +160,17 @@ const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a);
 // the first launch) that count the split blocks' arrivals
 hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const float* Vc, int cap,
                               const int* state, int pos_host, int window, float scale, int H,
-                              int KVH, float* part, float* out, int splits, hipStream_t st, int kv16 = 0);
+                              int KVH, float* part, float* out, int splits, hipStream_t st, int kvt = 0);
 // the same over nb streams at once (device state positions; pointers per stream)
 hipError_t launch_attn_decode_batch(int hd, const AttnPtrs& p, int nb, int cap, int window, float scale,
-                                    int H, int KVH, int splits, hipStream_t st, int kv16 = 0);
+                                    int H, int KVH, int splits, hipStream_t st, int kvt = 0);
+// the FP8 ring helpers over groups of 8 values (vox_hip_kv8_convert): x [8 groups] -> codes, back
+hipError_t launch_kv8_convert(const float* x, int groups, uint8_t* codes, float* back, hipStream_t st);
 constexpr int ATT_BLOCK_KEYS = 256;  // keys one decode-attention block covers
 // the batched step's attention: RoPE + KV append from the QKV slabs, output as planes
 // (one block per stream x kv head x 256-key split; splits > 1 adds the combine kernel)
 hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window,
-                                   float scale, int H, int KVH, int splits, hipStream_t st, int kv16 = 0);
+                                   float scale, int H, int KVH, int splits, hipStream_t st, int kvt = 0);
 
 // a batched encoder pass: rows [off[b], off[b] + nr[b]) of the stacked rows belong to stream
 // b, at logical positions pos0[b] + i, with its own K/V ring (layer base)

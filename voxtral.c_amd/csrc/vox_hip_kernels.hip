@@ -7,6 +7,7 @@
 //                (rows 32g..32g+15 = w1[16g..], rows 32g+16..32g+31 = w3[16g..])
 //   KV caches    f32 rolling buffers [cap][kv_heads*head_dim] per layer, slot = pos % cap
 //                (decoder: IEEE half in the opt-in 16-bit mode, VOX_DECODER_KV_FP16)
+//                (decoder: FP8 E4M3 bytes in the opt-in one-byte mode, VOX_HIP_KV_FP8)
 //   rope tables  f32 [pos][head_dim/2][2] (cos, sin) computed on the host with the
 //                reference's float powf/cosf/sinf (voxtral_kernels.c:617-629)
 //
@@ -32,38 +33,72 @@ namespace vox {
 // mode (VOX_DECODER_KV_FP16, voxtral.c:189-190, voxtral_decoder.c:180-243) stores IEEE half:
 // stores round to nearest even, loads widen to f32, all arithmetic stays f32.  Kernels that
 // read the ring are templated on the element type; the two single-store epilogues (decode
-// QKV GEMV, batched RoPE + append) take it as a uniform runtime flag.
+// QKV GEMV, batched RoPE + append) take it as a uniform runtime value (KV_F32 / KV_F16 / KV_FP8).
 // ============================================================================
 typedef _Float16 kvh_t;
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+// The opt-in one-byte mode (VOX_HIP_KV_FP8, KV_FP8): OCP FP8 E4M3 without a scale, by the
+// rule of vox_kv8.h.  Loads widen with v_cvt_pk_f32_fp8 (exact); the store clamps to +-448 in
+// f32 first (the conversion by itself gives NaN past the largest finite value, the rule
+// saturates) and then rounds with v_cvt_pk_fp8_f32 (nearest, ties to even, subnormals kept);
+// NaN is written as 0x7f with the sign whatever the instruction makes of it.
+__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : v < -448.f ? -448.f : v; }
+__device__ __forceinline__ unsigned kv8_fix_nan(float v, unsigned code) {
+    return v != v ? (0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) : code;
+}
+// the pair (a, b) as two codes, a in bits 0..7
+__device__ __forceinline__ unsigned kv8_enc2(float a, float b) {
+    const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
+    return kv8_fix_nan(a, w & 0xffu) | (kv8_fix_nan(b, (w >> 8) & 0xffu) << 8);
+}
+struct kv8_t {
+    uint8_t b;
+    kv8_t() = default;
+    __device__ __forceinline__ explicit kv8_t(float v) : b((uint8_t)(kv8_enc2(v, v) & 0xffu)) {}
+    __device__ __forceinline__ explicit operator float() const {
+        return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0];
+    }
+};
+static_assert(sizeof(kv8_t) == 1, "kv8_t: one byte per ring element");
+// ring element type of the launchers' kvt argument
 template <class T> __device__ __forceinline__ float4 kv_ld4(const T* p) {
     if constexpr (sizeof(T) == 4) {
         return *reinterpret_cast<const float4*>(p);
-    } else {
+    } else if constexpr (sizeof(T) == 2) {
         const h16x4 h = *reinterpret_cast<const h16x4*>(p);
         return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+    } else {
+        const int w = *reinterpret_cast<const int*>(p);
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+        return make_float4(lo[0], lo[1], hi[0], hi[1]);
     }
 }
 template <class T> __device__ __forceinline__ float2 kv_ld2(const T* p) {
     if constexpr (sizeof(T) == 4) {
         return *reinterpret_cast<const float2*>(p);
-    } else {
+    } else if constexpr (sizeof(T) == 2) {
         const h16x2 h = *reinterpret_cast<const h16x2*>(p);
         return make_float2((float)h[0], (float)h[1]);
+    } else {
+        const auto v = __builtin_amdgcn_cvt_pk_f32_fp8((int)*reinterpret_cast<const uint16_t*>(p), false);
+        return make_float2(v[0], v[1]);
     }
 }
 template <class T> __device__ __forceinline__ float kv_round(float v) { return (float)(T)v; }
 template <class T> __device__ __forceinline__ void kv_st2(T* p, float a, float b) {
     if constexpr (sizeof(T) == 4) {
         *reinterpret_cast<float2*>(p) = make_float2(a, b);
-    } else {
+    } else if constexpr (sizeof(T) == 2) {
         *reinterpret_cast<h16x2*>(p) = h16x2{(T)a, (T)b};
+    } else {
+        *reinterpret_cast<uint16_t*>(p) = (uint16_t)kv8_enc2(a, b);
     }
 }
-// element e of a ring (f32 or half by the flag) written as the pair (a, b) at e, e + 1
-__device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float b, int kv16) {
-    if (kv16) kv_st2(reinterpret_cast<kvh_t*>(base) + e, a, b);
+// element e of a ring (f32, half or fp8 by the element type) written as the pair (a, b) at e, e + 1
+__device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float b, int kvt) {
+    if (kvt == KV_FP8) kv_st2(reinterpret_cast<kv8_t*>(base) + e, a, b);
+    else if (kvt == KV_F16) kv_st2(reinterpret_cast<kvh_t*>(base) + e, a, b);
     else kv_st2(base + e, a, b);
 }
 
@@ -1083,10 +1118,10 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
                         a.y[er0] = o0;
                         a.y[er1] = o1;
                     } else {
-                        kv_st2_rt(a.Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kv16);
+                        kv_st2_rt(a.Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kvt);
                     }
                 } else {
-                    kv_st2_rt(a.Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kv16);
+                    kv_st2_rt(a.Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kvt);
                 }
             }
         }
@@ -1355,10 +1390,10 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
                             yrow[er0] = o0;
                             yrow[er1] = o1;
                         } else if (live) {
-                            kv_st2_rt(Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kv16);
+                            kv_st2_rt(Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kvt);
                         }
                     } else if (live) {
-                        kv_st2_rt(Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kv16);
+                        kv_st2_rt(Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kvt);
                     }
                 }
             }
@@ -3483,11 +3518,48 @@ hipError_t launch_gemm(int epi, int nsplit, const float* A, int lda, const void*
     return hipErrorInvalidValue;
 }
 
+// vox_hip_kv8_convert: the FP8 ring helpers on the device.  Thread t takes values 8t..8t+7:
+// the store kernel writes 8t..8t+3 as two pairs (kv_st2: k_rope_kv, the epilogues, the fused
+// new key) and 8t+4..8t+7 one by one (the fused new value); the load kernel reads 8t..8t+3 as
+// one word (kv_ld4: the K rows), 8t+4..8t+5 as a pair (kv_ld2: the V rows) and the last two alone.
+__global__ __launch_bounds__(256) void k_kv8_store(const float* __restrict__ x, int groups, kv8_t* __restrict__ codes) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= groups) return;
+    const float* xr = x + (size_t)t * 8;
+    kv8_t* cr = codes + (size_t)t * 8;
+    kv_st2(cr, xr[0], xr[1]);
+    kv_st2(cr + 2, xr[2], xr[3]);
+    for (int i = 4; i < 8; i++) cr[i] = (kv8_t)xr[i];
+}
+__global__ __launch_bounds__(256) void k_kv8_load(const kv8_t* __restrict__ codes, int groups, float* __restrict__ back) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= groups) return;
+    const kv8_t* cr = codes + (size_t)t * 8;
+    float* br = back + (size_t)t * 8;
+    const float4 a = kv_ld4(cr);
+    const float2 b = kv_ld2(cr + 4);
+    br[0] = a.x; br[1] = a.y; br[2] = a.z; br[3] = a.w;
+    br[4] = b.x; br[5] = b.y;
+    br[6] = (float)cr[6];
+    br[7] = kv_round<kv8_t>((float)cr[7]);  // a stored value rounds to itself
+}
+hipError_t launch_kv8_convert(const float* x, int groups, uint8_t* codes, float* back, hipStream_t st) {
+    if (groups <= 0) return hipSuccess;
+    const dim3 grid((groups + 255) / 256);
+    hipLaunchKernelGGL(k_kv8_store, grid, dim3(256), 0, st, x, groups, reinterpret_cast<kv8_t*>(codes));
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_kv8_load, grid, dim3(256), 0, st, reinterpret_cast<const kv8_t*>(codes), groups, back);
+    LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, const float* rope,
-                          int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st, int kv16) {
+                          int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st, int kvt) {
     if (M <= 0) return hipSuccess;
-    if (kvd % 2) return hipErrorInvalidValue;
-    if (kv16)
+    if (kvd % 2 || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
+    if (kvt == KV_FP8)
+        hipLaunchKernelGGL(k_rope_kv<kv8_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
+    else if (kvt == KV_F16)
         hipLaunchKernelGGL(k_rope_kv<kvh_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
     else
         hipLaunchKernelGGL(k_rope_kv<float>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
@@ -3562,9 +3634,9 @@ hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, in
 hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc, const float* Vc,
                              int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0,
                              int k_first, int window, float scale, hipStream_t st, float* ws, size_t ws_elems,
-                             uint16_t* xs, int kv16) {
+                             uint16_t* xs, int kvt) {
     if (M <= 0) return hipSuccess;
-    if (hd != 64 && hd != 128) return hipErrorInvalidValue;
+    if ((hd != 64 && hd != 128) || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
     if (xs && (M > PLANE_MAX_ROWS || ldo != H * hd)) return hipErrorInvalidValue;
     // 16 queries per block: 32 (each K/V tile of a 25-row streaming chunk read once per head
     // instead of twice) measured slower, 15.7 vs 14.6 us (tools/kbench, round 1)
@@ -3583,7 +3655,12 @@ hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc,
         while (ns > 1 && (size_t)H * M * ns * (hd + 2) > ws_elems) ns--;
     }
     dim3 grid(H, qb, ns);
-    if (kv16) {
+    if (kvt == KV_FP8) {
+        // the one-byte decoder ring (prefill)
+        if (hd != 128) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_attn_mf<128, kv8_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH,
+                           q_pos0, k_first, window, scale, ns, ws);
+    } else if (kvt == KV_F16) {
         // the 16-bit decoder ring (prefill)
         if (hd != 128) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_attn_mf<128, kvh_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH,
@@ -3603,7 +3680,7 @@ hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc,
         else
             hipLaunchKernelGGL(k_attn_tiled_combine<128>, dim3(H, M), dim3(128), 0, st, ws, ns, M, O, ldo, xs);
         LAUNCH_CHECK();
-    } else if (xs && (kv16 || !att_planes())) {
+    } else if (xs && (kvt != KV_F32 || !att_planes())) {
         return launch_split_fplanes(O, M, H * hd, xs, st);
     }
     return hipSuccess;
@@ -3923,7 +4000,8 @@ int g_attn_short = -1;  // k_attn_short for one stream's contexts <= 256 keys (V
 // within noise of wave 4 (profiles/r4_attn_short_late_ab.txt, r4_attn_short_late2_ab.txt)
 hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const float* Vc, int cap,
                               const int* state, int pos_host, int window, float scale, int H,
-                              int KVH, float* part, float* out, int splits, hipStream_t st, int kv16) {
+                              int KVH, float* part, float* out, int splits, hipStream_t st, int kvt) {
+    if (kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
     if (g_attn_short < 0) {
         const char* e = getenv("VOX_HIP_ATT_SHORT");
         g_attn_short = (e && atoi(e) == 0) ? 0 : 1;
@@ -3932,7 +4010,11 @@ hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const flo
         // contexts of <= 256 keys (splits == 1) with a window of > 256: nothing has left the
         // window (lp < 256 < window) and the ring has not wrapped, so keys = slots 0..lp (a
         // window of exactly 256 would reach L = 256 again at lp >= 256 with wrapped slots)
-        if (kv16)
+        if (kvt == KV_FP8)
+            hipLaunchKernelGGL((k_attn_short<128, kv8_t, 4>), dim3(H), dim3(1024), 0, st, q,
+                               reinterpret_cast<const kv8_t*>(Kc), reinterpret_cast<const kv8_t*>(Vc), state, pos_host,
+                               scale, H, KVH, out);
+        else if (kvt == KV_F16)
             hipLaunchKernelGGL((k_attn_short<128, kvh_t, 4>), dim3(H), dim3(1024), 0, st, q,
                                reinterpret_cast<const kvh_t*>(Kc), reinterpret_cast<const kvh_t*>(Vc), state, pos_host,
                                scale, H, KVH, out);
@@ -3945,14 +4027,17 @@ hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const flo
     AttnPtrs p;
     memset(&p, 0, sizeof p);
     p.q[0] = q; p.Kc[0] = Kc; p.Vc[0] = Vc; p.state[0] = state; p.part[0] = part; p.out[0] = out;
-    return kv16 ? attn_launch<kvh_t>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st)
-                : attn_launch<float>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st);
+    return kvt == KV_FP8   ? attn_launch<kv8_t>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st)
+           : kvt == KV_F16 ? attn_launch<kvh_t>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st)
+                           : attn_launch<float>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st);
 }
 
 hipError_t launch_attn_decode_batch(int hd, const AttnPtrs& p, int nb, int cap, int window, float scale,
-                                    int H, int KVH, int splits, hipStream_t st, int kv16) {
-    return kv16 ? attn_launch<kvh_t>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st)
-                : attn_launch<float>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
+                                    int H, int KVH, int splits, hipStream_t st, int kvt) {
+    if (kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
+    return kvt == KV_FP8   ? attn_launch<kv8_t>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st)
+           : kvt == KV_F16 ? attn_launch<kvh_t>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st)
+                           : attn_launch<float>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
 }
 
 template <class KT>
@@ -3979,13 +4064,14 @@ static hipError_t attn_batch_fused(const AttnPtrs& p, const AttnFuse& f, int nb,
 }
 
 hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window,
-                                   float scale, int H, int KVH, int splits, hipStream_t st, int kv16) {
+                                   float scale, int H, int KVH, int splits, hipStream_t st, int kvt) {
     const int maxs = attn_maxch(window);
-    if (hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 || splits > attn_maxsplits(window) ||
+    if (kvt < KV_F32 || kvt > KV_FP8 || hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 || splits > attn_maxsplits(window) ||
         nb < 1 || nb > VOX_MAX_BATCH || !f.qkv || !f.rope || !f.xs || f.S < 1 || f.N != (H + 2 * KVH) * hd)
         return hipErrorInvalidValue;
-    return kv16 ? attn_batch_fused<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
-                : attn_batch_fused<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
+    return kvt == KV_FP8   ? attn_batch_fused<kv8_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
+           : kvt == KV_F16 ? attn_batch_fused<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
+                           : attn_batch_fused<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
 }
 // diagnostic variants for tools/kbench (not used by the engine)
 // the batched fused attention (128-key blocks, the bsplit grid) with per-wave phase stamps

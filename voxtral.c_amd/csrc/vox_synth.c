@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "vox_kv8.h"
 #include "vox_wmx4.h"
 #include "vox_wpack.h"
 
@@ -135,4 +136,20 @@ void vox_wmx4_plane_layout(const uint32_t *nib, const uint8_t *scl, long long ro
 long long vox_wmx4_frag_words_of(long long N, long long K) { return vox_wmx4_frag_words(N, K); }
 void vox_wmx4_frag_layout(const uint32_t *nib, const uint8_t *scl, long long N, long long K, uint32_t *out) {
     vox_wmx4_frag_layout_(nib, scl, N, K, out);
+}
+
+/* kv8 (vox_kv8.h): the FP8 E4M3 decoder KV ring element's rule, for tests and tools; the _n
+ * forms run it over arrays (codes and / or back may be null) */
+uint8_t vox_kv8_encode(float x) { return vox_kv8_encode_(x); }
+float vox_kv8_decode(uint8_t c) { return vox_kv8_decode_(c); }
+float vox_kv8_round(float x) { return vox_kv8_round_(x); }
+void vox_kv8_encode_n(const float *x, long long n, uint8_t *codes, float *back) {
+    for (long long i = 0; i < n; i++) {
+        const uint8_t c = vox_kv8_encode_(x[i]);
+        if (codes) codes[i] = c;
+        if (back) back[i] = vox_kv8_decode_(c);
+    }
+}
+void vox_kv8_decode_n(const uint8_t *codes, long long n, float *out) {
+    for (long long i = 0; i < n; i++) out[i] = vox_kv8_decode_(codes[i]);
 }

@@ -1039,6 +1039,13 @@ int vh_sched_detach(vh_sched_t *q, vh_stream_t *s) {
 
 void vh_sched_set_step_cap(vh_sched_t *q, int cap) { q->step_cap = cap > 0 ? cap : 0; }
 
+int vh_set_kv_dtype(vh_ctx_t *ctx, int dtype) {
+    if (vox_hip_model_set_kv_dtype(ctx->model, dtype)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_stream_kv_dtype(const vh_stream_t *s) { return vox_hip_stream_kv_dtype(s->st); }
+
 int vh_stream_pending(vh_stream_t *s) {
     int st6[6];
     vox_hip_stream_state(s->st, st6);

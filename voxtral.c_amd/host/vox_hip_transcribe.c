@@ -3,7 +3,7 @@
  * MI355X backend through the C host API (include/vox_hip_host.h):
  *
  *   vox_hip_transcribe -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms]
- *                      [--alt cutoff] [--continuous] [--mx4]
+ *                      [--alt cutoff] [--continuous] [--mx4] [--kv8]
  *
  * The audio is fed in pieces of min(interval, 1 s) of samples, as main.c's feed_and_drain
  * does; every generated token id is printed to stdout (the tokenizer is out of scope) --
@@ -12,8 +12,10 @@
  * and the microphone, main.c:208-209) on the file's samples.  --mx4 (no reference
  * counterpart) rounds the decoder's matrices to MXFP4 values at load and streams them as such
  * in the single-stream decode step (vox_hip_set_wmx4(2), voxtral_hip.h; a checkpoint that is
- * already MXFP4-valued needs only VOX_HIP_WMX4=1); one stderr line reports what was built.  The
- * the reference's stderr lines ("Audio:", "Encoder:", "Decoder:") are kept so its
+ * already MXFP4-valued needs only VOX_HIP_WMX4=1); one stderr line reports what was built.
+ * --kv8 (no reference counterpart) keeps the decoder KV rings in FP8 E4M3 (vh_set_kv_dtype(ctx, 2):
+ * a quarter of the f32 rings' bytes, no scale, effect on transcripts not evaluated).  The
+ * reference's stderr lines ("Audio:", "Encoder:", "Decoder:") are kept so its
  * benchmark.py regexes parse this program's output too.
  */
 #include "../../include/vox_hip_host.h"
@@ -40,7 +42,7 @@ static void drain(vh_stream_t *s, int *text_tokens, int alt) {
 int main(int argc, char **argv) {
     const char *model = NULL, *wav = NULL;
     float interval = -1.0f, alt_cutoff = -1.0f;
-    int delay_ms = -1, continuous = 0, mx4 = 0;
+    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-d") && i + 1 < argc) model = argv[++i];
         else if (!strcmp(argv[i], "-i") && i + 1 < argc) wav = argv[++i];
@@ -49,6 +51,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--alt") && i + 1 < argc) alt_cutoff = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--continuous")) continuous = 1;
         else if (!strcmp(argv[i], "--mx4")) mx4 = 1;
+        else if (!strcmp(argv[i], "--kv8")) kv8 = 1;
         else {
             model = NULL;
             break;
@@ -56,7 +59,7 @@ int main(int argc, char **argv) {
     }
     if (!model || !wav || (alt_cutoff != -1.0f && (alt_cutoff < 0 || alt_cutoff > 1))) {
         fprintf(stderr, "usage: %s -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms] "
-                        "[--alt 0..1] [--continuous] [--mx4]\n", argv[0]);
+                        "[--alt 0..1] [--continuous] [--mx4] [--kv8]\n", argv[0]);
         return 2;
     }
     if (mx4 && vox_hip_set_wmx4(2)) return 1;
@@ -70,6 +73,7 @@ int main(int argc, char **argv) {
                 vox_hip_wmx4(), ms.wmx4_tensors, ms.refused_tensors, ms.plane_bytes / 1e6, ms.bf16_bytes / 1e6,
                 ms.bits_per_weight, ms.scan_ms, ms.round_ms, ms.pack_ms);
     }
+    if (kv8 && vh_set_kv_dtype(ctx, 2)) return 1;
     if (delay_ms > 0 && vh_set_delay(ctx, delay_ms)) return 1;
     vh_stream_t *s = vh_stream_init(ctx);
     if (!s) return 1;

@@ -87,6 +87,7 @@ EXPORTS = [
     "vox_hip_last_error", "vox_hip_clear_error", "vox_hip_set_device", "vox_hip_config_voxtral_4b",
     "vox_hip_model_create", "vox_hip_model_free", "vox_hip_model_set_delay",
     "vox_hip_model_ada_scale", "vox_hip_model_set_kv_fp16", "vox_hip_stream_kv_fp16",
+    "vox_hip_model_set_kv_dtype", "vox_hip_stream_kv_dtype", "vox_hip_stream_read_kv", "vox_hip_kv8_convert",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
@@ -130,6 +131,9 @@ def lib():
         "vox_hip_model_create": (P, [P, P, I]), "vox_hip_model_free": (None, [P]),
         "vox_hip_model_set_delay": (I, [P, I]), "vox_hip_model_ada_scale": (I, [P, fp]),
         "vox_hip_model_set_kv_fp16": (I, [P, I]), "vox_hip_stream_kv_fp16": (I, [P]),
+        "vox_hip_model_set_kv_dtype": (I, [P, I]), "vox_hip_stream_kv_dtype": (I, [P]),
+        "vox_hip_stream_read_kv": (I, [P, I, I, I, P, P]),
+        "vox_hip_kv8_convert": (I, [fp, I, P, fp]),
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
         "vox_hip_set_wmx4": (I, [I]), "vox_hip_wmx4": (I, []), "vox_hip_model_wmx4_stats": (I, [P, P]),
@@ -195,6 +199,31 @@ def fptr(a: np.ndarray):
 def _err(what):
     msg = lib().vox_hip_last_error()
     raise RuntimeError(f"{what}: {msg.decode() if msg else 'unknown error'}")
+
+
+KV_F32, KV_F16, KV_FP8 = 0, 1, 2                       # decoder KV ring element types
+KV_NP_DTYPE = {KV_F32: np.float32, KV_F16: np.float16, KV_FP8: np.uint8}
+
+
+def kv8_decode(codes) -> np.ndarray:
+    """FP8 E4M3 codes (uint8; csrc/vox_kv8.h) -> their f32 values, exactly"""
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e - 10.0))
+    v[(c & 0x7f) == 0x7f] = np.nan
+    lut = np.where(c & 0x80, -v, v).astype(np.float32)
+    return lut[np.asarray(codes, np.uint8)]
+
+
+def kv8_convert(x):
+    """vox_hip_kv8_convert: the kernels' FP8 ring store and load helpers on the device over x
+    -> (codes uint8, the f32 values read back)"""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    codes = np.empty(x.size, np.uint8)
+    back = np.empty(x.size, np.float32)
+    if lib().vox_hip_kv8_convert(fptr(x), x.size, codes.ctypes.data, fptr(back)) != 0:
+        _err("kv8_convert")
+    return codes, back
 
 
 def set_gemm_planes(planes: int):
@@ -286,6 +315,13 @@ class Model:
         if lib().vox_hip_model_set_kv_fp16(self.h, int(on)) != 0:
             _err("set_kv_fp16")
 
+    def set_kv_dtype(self, dtype: int):
+        """vox_hip_model_set_kv_dtype: streams created afterwards keep their decoder K/V rings
+        in f32 (KV_F32 = 0), IEEE half (KV_F16 = 1) or FP8 E4M3 (KV_FP8 = 2: no scale,
+        saturating at 448, quality not evaluated)"""
+        if lib().vox_hip_model_set_kv_dtype(self.h, int(dtype)) != 0:
+            _err("set_kv_dtype")
+
     def wpack_stats(self) -> dict:
         """What the single-stream decode GEMV streams as wpack13 planes (13 bits per bf16
         weight, lossless) and what stayed raw: tensor counts, bytes, host packing time"""
@@ -358,6 +394,26 @@ class Stream:
     @property
     def kv_fp16(self) -> bool:
         return bool(lib().vox_hip_stream_kv_fp16(self.h))
+
+    @property
+    def kv_dtype(self) -> int:
+        """the decoder KV ring element: KV_F32, KV_F16 or KV_FP8"""
+        return lib().vox_hip_stream_kv_dtype(self.h)
+
+    def read_kv(self, layer: int, first: int, n: int, decoded: bool = False):
+        """vox_hip_stream_read_kv: the K and V ring elements of logical positions
+        [first, first + n) of one decoder layer, [n, kv_heads * head_dim] each: raw (float32,
+        float16 or uint8 codes by kv_dtype) or, decoded, widened to float32"""
+        dt = KV_NP_DTYPE[self.kv_dtype]
+        kvd = self.cfg.dec_kv_heads * self.cfg.dec_head_dim
+        k, v = np.empty((n, kvd), dt), np.empty((n, kvd), dt)
+        if lib().vox_hip_stream_read_kv(self.h, int(layer), int(first), int(n), k.ctypes.data, v.ctypes.data) != 0:
+            _err("read_kv")
+        if not decoded:
+            return k, v
+        if dt is np.uint8:
+            return kv8_decode(k), kv8_decode(v)
+        return k.astype(np.float32), v.astype(np.float32)
 
     def encode_mel(self, mel: np.ndarray) -> int:
         mel = np.ascontiguousarray(mel, dtype=np.float32)
