@@ -190,8 +190,9 @@ int vox_hip_model_wmx4_stats(const vox_hip_model_t *m, vox_hip_wmx4_stats_t *out
  * splits, slabs and summation order, so the step's logits and ids are bit-identical to the
  * step on the bf16 copies.  A tensor the scan refuses keeps only its bf16 copy; Q8 models and
  * VOX_HIP_WPACK=0 build nothing; the bf16 fragment copies stay (prefill reads them).  Off
- * (default), or wmx4 mode 0: nothing changes.  The R-row GEMV step, prefill, the encoder and
- * the single-stream step are untouched.  What MXFP4 rounding does to transcription quality
+ * (default), or wmx4 mode 0: nothing changes.  Prefill, the encoder and the single-stream step
+ * are untouched; the R-row GEMV step has a switch of its own (vox_hip_batch_set_gemv_wmx4: it
+ * streams the wmx4 GEMV planes, not these fragment planes).  What MXFP4 rounding does to transcription quality
  * has not been evaluated.
  * vox_hip_set_wmx4_batch returns 0. */
 int vox_hip_set_wmx4_batch(int on);
@@ -374,6 +375,20 @@ int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
 /* [0] max_rows in effect, [1] step replays on the GEMV path, [2] live rows over those,
  * [3] GEMV step-graph captures.  ([1]..[3] are also counted in vox_hip_batch_stats.) */
 int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
+/* The R-row GEMV step's weight source (opt-in, on top of wmx4 mode 1 or 2): on = 1 makes the
+ * step stream the wmx4 GEMV plane of every tensor that has one -- the plane the single-stream
+ * step reads, 5 bits per weight, no second copy -- through k_gemvr's wmx4 instances, which
+ * decode each weight once for the bucket's rows and run the bf16 instance's FMA chains: same
+ * bits as on = 0.  A tensor the scan refused keeps its wpack13 or raw launch, so a step may mix
+ * formats per tensor.  The two modes keep step graphs of their own, so the flag may change
+ * between calls.  VOX_HIP_BATCH_GEMV_WMX4=1 sets the initial value at vox_hip_batch_create
+ * (ignored where this call would fail).  Default off.  Returns 0; -1 (vox_hip_last_error) when
+ * the model has no wmx4 GEMV plane (wmx4 mode 0, Q8, VOX_HIP_WPACK=0), or between
+ * vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+int vox_hip_batch_set_gemv_wmx4(vox_hip_batch_t *b, int on);
+/* [0] the flag in effect, [1] GEMV step replays that streamed at least one wmx4 plane,
+ * [2] tensors of the step (4 per layer and the LM head) with a wmx4 GEMV plane, [3] without. */
+int vox_hip_batch_gemv_wmx4_stats(const vox_hip_batch_t *b, long long out4[4]);
 /* The batched MFMA step's weight source: on = 1 streams the wmx4 fragment plane of every tensor
  * that has one (the bf16 fragment copy of the others), on = 0 the bf16 fragment copies.  Both
  * give the same bits.  A batch created on a model with fragment planes (vox_hip_set_wmx4_batch)
@@ -383,8 +398,10 @@ int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
  * vox_hip_batch_begin_rows and vox_hip_batch_finish. */
 int vox_hip_batch_set_wmx4(vox_hip_batch_t *b, int on);
 /* Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
- * bucket >= R (unused rows zero).  Returns flags: bit 0 the packed instance ran, bit 1 the
- * per-row summation order is the single-row GEMV's; -1 on error. */
+ * bucket >= R (unused rows zero), from the raw rows (packed = 0), the wpack13 planes (1) or
+ * the wmx4 plane built from W (2, as vox_hip_gemv_wpack).  Returns flags: bit 0 the wpack13
+ * instance ran, bit 1 the per-row summation order is the single-row GEMV's, bit 2 the wmx4
+ * instance ran (clear, and the raw rows streamed, when W is not MXFP4-valued); -1 on error. */
 int vox_hip_gemv_rows(int rows, int K, const uint16_t *W, const float *x, int R, float *y, int packed);
 /* Decoder state snapshot: [0]=kv logical length, [1]=next adapter row, [2]=prev token,
  * [3]=started, [4]=eos_seen, [5]=tokens generated. */

@@ -746,6 +746,166 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemvrmx4")) {
+        // k_gemvr on the wmx4 GEMV plane (k_gemvr<.., WF_MX4, R>) beside its wpack13 instance: the
+        // five full-size shapes, cold weights (a set of planes per layer), R = 1, 2, 4, 8, the two
+        // formats alternating three times (medians), with k_gemv<WF_MX4> on the same plane as the
+        // R = 1 twin.  First, per shape, a seeded random matrix is rounded and packed on the host
+        // and the outputs of the wmx4, wpack13 and raw instances (y rows; for QKV also the rows
+        // appended to the slots' rings) are compared bit for bit at every R (the LM head at 65536
+        // rows).  VOX_KB_GEMVR_SHAPES=w2 (or any list of qkv,wo,w13,w2,lm) limits the shapes.
+        struct S { const char* n; int pro, epi, epi1, K, rows, crows; std::vector<uint16_t*>* w; };
+        const char* only = getenv("VOX_KB_GEMVR_SHAPES");
+        CK(hipMemset(state, 0, 16));
+        std::vector<uint16_t*> lm1(1, emb);
+        const int RM = GEMVR_MAX_ROWS;
+        float* xr = (float*)dmalloc((size_t)RM * DH * 4, 1);
+        float* yr = (float*)dmalloc((size_t)RM * V * 4, 0);
+        BatchSlot hs[RM];
+        memset(hs, 0, sizeof hs);
+        for (int s = 0; s < RM; s++) {
+            hs[s].Kc = (char*)(Kc + (size_t)s * 1024 * DKV);
+            hs[s].Vc = (char*)(Vc + (size_t)s * 1024 * DKV);
+            hs[s].live = 1;
+        }
+        BatchSlot* slots = (BatchSlot*)dmalloc(sizeof hs, 0);
+        CK(hipMemcpy(slots, hs, sizeof hs, hipMemcpyHostToDevice));
+        struct T { char nm[24]; double us[3][3], bytes[2]; int occ[2]; };
+        std::vector<T> table;
+        for (S o : {S{"qkv", PRO_NORM, EPI_QKV, EPI_QKV, D, DQ + 2 * DKV, DQ + 2 * DKV, &wqkv},
+                    S{"wo", PRO_NONE, EPI_RESID, EPI_RESID, DQ, D, D, &wo},
+                    S{"w13", PRO_NORM_ADA, EPI_SWIGLU, EPI_SWIGLU, D, 2 * DH, 2 * DH, &w13},
+                    S{"w2", PRO_NONE, EPI_RESID, EPI_RESID, DH, D, D, &w2}, S{"lm", PRO_NORM, EPI_STORE, EPI_LOGITS, D, V, 65536, &lm1}}) {
+            if (only && !strstr(only, o.n)) continue;
+            const int rb = gemv_rowgroup(o.rows), sw = vox_wpack13_side_words(o.K, rb), swiglu = o.epi == EPI_SWIGLU;
+            const int rbm = gemv_rowgroup_mx4(o.rows);
+            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sideb = (size_t)o.rows / rb * 256 * sw * 4;
+            const size_t mxb = (size_t)vox_wmx4_plane_words(o.rows, o.K, rbm) * 4;
+            if (!gemvr_ok_mx4(o.pro, o.epi, o.rows, o.K)) { printf("%s: no wmx4 k_gemvr instance\n", o.n); return 1; }
+            const int ldy = o.epi == EPI_QKV ? DQ : o.epi == EPI_SWIGLU ? DH : o.rows;
+            auto args = [&](const void* W, const void* pm, const void* ps, int d, const void* mx, int rows) {
+                GemvRArgs a;
+                memset(&a, 0, sizeof a);
+                a.g.x = xr; a.ldx = o.K; a.g.K = o.K; a.g.W = W; a.g.rows = rows; a.g.norm_w = normw; a.g.ada = ada;
+                a.g.eps = 1e-5f; a.g.y = yr; a.ldy = ldy; a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = HD; a.g.rope = rope;
+                a.g.state = state; a.g.Kc = Kc; a.g.Vc = Vc; a.g.cap = 1024; a.g.part_val = pv; a.g.part_idx = pi;
+                a.slots = slots;
+                a.g.wp_main = pm; a.g.wp_side = ps; a.g.wp_d = d; a.g.wm_plane = mx;
+                return a;
+            };
+            {   // bit check on seeded random weights (uniform, std 1/sqrt(3072)), rounded, and random x rows
+                const int rows = o.crows;
+                if (gemv_rowgroup_mx4(rows) != rbm || gemv_rowgroup(rows) != rb) { printf("%s: check rows use another row group\n", o.n); return 1; }
+                std::vector<uint16_t> hw((size_t)rows * o.K);
+                uint64_t z = 0x9E3779B97F4A7C15ull ^ (uint64_t)o.K * 131 ^ (uint64_t)o.rows;
+                auto rnd = [&] { z = z * 6364136223846793005ull + 1442695040888963407ull; return (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f; };
+                for (auto& v : hw) {
+                    const float f = 0.03125f * rnd();
+                    uint32_t u;
+                    memcpy(&u, &f, 4);
+                    v = (uint16_t)(u >> 16);
+                }
+                vox_wmx4_round_(hw.data(), rows, o.K, hw.data());
+                if (!vox_wmx4_scan_(hw.data(), rows, o.K)) { printf("%s: rounded weights fail the scan\n", o.n); return 1; }
+                std::vector<float> hx((size_t)RM * DH);
+                for (auto& v : hx) v = rnd();
+                CK(hipMemcpy(xr, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+                int emin, emax, d = 0;
+                if (!vox_wpack13_scan_(hw.data(), hw.size(), &emin, &emax, &d)) { printf("%s: not packable\n", o.n); return 1; }
+                std::vector<uint32_t> hm((size_t)rows * o.K / 8 * 3), hsd((size_t)rows / rb * 256 * sw);
+                std::vector<uint8_t> hb((size_t)rows * o.K / 8);
+                vox_wpack13_pack_(hw.data(), rows, o.K, d, hm.data(), hb.data());
+                vox_wpack13_side_layout_(hb.data(), rows, o.K, rb, swiglu, hsd.data());
+                std::vector<uint32_t> nib((size_t)rows * o.K / 8), pl((size_t)vox_wmx4_plane_words(rows, o.K, rbm));
+                std::vector<uint8_t> scl((size_t)rows * o.K / 32);
+                vox_wmx4_pack_(hw.data(), rows, o.K, nib.data(), scl.data());
+                vox_wmx4_plane_layout_(nib.data(), scl.data(), rows, o.K, rbm, swiglu, pl.data());
+                uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
+                uint32_t* dm = (uint32_t*)dmalloc(hm.size() * 4, 0);
+                uint32_t* ds = (uint32_t*)dmalloc(hsd.size() * 4, 0);
+                uint32_t* dp = (uint32_t*)dmalloc(pl.size() * 4, 0);
+                CK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+                CK(hipMemcpy(dm, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+                CK(hipMemcpy(ds, hsd.data(), hsd.size() * 4, hipMemcpyHostToDevice));
+                CK(hipMemcpy(dp, pl.data(), pl.size() * 4, hipMemcpyHostToDevice));
+                const int cldy = o.epi == EPI_QKV ? DQ : o.epi == EPI_SWIGLU ? DH : rows;
+                const size_t ny = (size_t)RM * cldy, nkv = o.epi == EPI_QKV ? (size_t)DKV : 0;
+                for (int R : {1, 2, 4, 8}) {
+                    std::vector<float> out[3];
+                    for (int f = 0; f < 3; f++) {
+                        CK(hipMemsetAsync(yr, 0, ny * 4, st));
+                        for (int s = 0; s < RM && nkv; s++) {
+                            CK(hipMemsetAsync(hs[s].Kc, 0, nkv * 4, st));
+                            CK(hipMemsetAsync(hs[s].Vc, 0, nkv * 4, st));
+                        }
+                        GemvRArgs a = args(dw, f == 1 ? dm : nullptr, f == 1 ? ds : nullptr, f == 1 ? d : 0, f == 2 ? dp : nullptr, rows);
+                        a.ldy = cldy;
+                        CK(launch_gemvr(o.pro, o.epi, R, a, st));
+                        CK(hipStreamSynchronize(st));
+                        out[f].resize(ny + 2 * nkv * RM);
+                        CK(hipMemcpy(out[f].data(), yr, ny * 4, hipMemcpyDeviceToHost));
+                        for (int s = 0; s < RM && nkv; s++) {
+                            CK(hipMemcpy(out[f].data() + ny + (2 * s) * nkv, hs[s].Kc, nkv * 4, hipMemcpyDeviceToHost));
+                            CK(hipMemcpy(out[f].data() + ny + (2 * s + 1) * nkv, hs[s].Vc, nkv * 4, hipMemcpyDeviceToHost));
+                        }
+                    }
+                    double sum = 0;
+                    for (float v : out[0]) sum += fabs((double)v);
+                    const bool same = !memcmp(out[0].data(), out[2].data(), out[0].size() * 4) &&
+                                      !memcmp(out[1].data(), out[2].data(), out[0].size() * 4);
+                    printf("gemvrmx4 %-4s check R = %d: %d-row groups (bf16 %d), %zu words, mean |y| %.4g: wmx4 / wpack13 / raw %s\n", o.n, R,
+                           rbm, rb, out[0].size(), sum / out[0].size(), same ? "same bits" : "BITS DIFFER");
+                    fflush(stdout);
+                    if (!same) return 1;
+                }
+                CK(hipFree(dw)); CK(hipFree(dm)); CK(hipFree(ds)); CK(hipFree(dp));
+                CK(hipMemsetD32(xr, 0x3c003c01u, (size_t)RM * DH));
+            }
+            // timing: constant planes (values do not matter; every byte 0x78 is a valid scale and a
+            // valid nibble pair), one set of planes per layer
+            const int nl = (int)o.w->size();
+            std::vector<void*> pm(nl), ps(nl), mx(nl);
+            for (int l = 0; l < nl; l++) {
+                pm[l] = dmalloc(mainb, 1);
+                ps[l] = dmalloc(sideb, 0);
+                mx[l] = dmalloc(mxb, 0);
+                CK(hipMemsetD32(mx[l], 0x78787878u, mxb / 4));
+            }
+            const int it = nl == 1 ? iters / 10 + 1 : iters;
+            for (int R : {1, 2, 4, 8}) {
+                T t;
+                snprintf(t.nm, sizeof t.nm, "%-4s R = %d", o.n, R);
+                t.bytes[0] = (double)mainb + sideb;
+                t.bytes[1] = (double)mxb;
+                t.occ[0] = gemv_occupancy(gemvr_kernel(o.pro, o.epi, R, args((*o.w)[0], pm[0], ps[0], 0, nullptr, o.rows)));
+                t.occ[1] = gemv_occupancy(gemvr_kernel(o.pro, o.epi, R, args((*o.w)[0], nullptr, nullptr, 0, mx[0], o.rows)));
+                for (int r = 0; r < 3; r++) {
+                    t.us[0][r] = timeit([&] { const int l = layer++ % nl; GemvRArgs a = args((*o.w)[l], pm[l], ps[l], 0, nullptr, o.rows);
+                                              CK(launch_gemvr(o.pro, o.epi, R, a, st)); }, it, st);
+                    t.us[1][r] = timeit([&] { const int l = layer++ % nl; GemvRArgs a = args((*o.w)[l], nullptr, nullptr, 0, mx[l], o.rows);
+                                              CK(launch_gemvr(o.pro, o.epi, R, a, st)); }, it, st);
+                    // the single-row twin on the same planes, in the same rotation
+                    t.us[2][r] = timeit([&] { const int l = layer++ % nl; GemvRArgs a = args((*o.w)[l], nullptr, nullptr, 0, mx[l], o.rows);
+                                              CK(launch_gemv(o.pro, o.epi1, a.g, st)); }, it, st);
+                }
+                table.push_back(t);
+            }
+            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); CK(hipFree(mx[l])); }
+        }
+        printf("\ngemvrmx4 medians of three: us per launch, MB streamed, fraction of 8 TB/s, blocks per CU\n");
+        printf("%-10s %10s %7s %6s %3s   %8s %7s %6s %3s   %10s  %s\n", "", "wpack13 us", "MB", "of 8T", "b", "wmx4 us", "MB", "of 8T", "b",
+               "wmx4 / p13", "k_gemv<MX4> us (wmx4 / it)");
+        for (T& t : table) {
+            double m[3];
+            for (int f = 0; f < 3; f++) {
+                std::sort(t.us[f], t.us[f] + 3);
+                m[f] = t.us[f][1];
+            }
+            printf("%-10s %10.2f %7.1f %6.3f %3d   %8.2f %7.1f %6.3f %3d   %10.3f  %.2f (%.2fx)\n", t.nm, m[0], t.bytes[0] / 1e6,
+                   t.bytes[0] / m[0] / 8e6, t.occ[0], m[1], t.bytes[1] / 1e6, t.bytes[1] / m[1] / 8e6, t.occ[1], m[1] / m[0], m[2], m[1] / m[2]);
+        }
+        return 0;
+    }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gpe")) {
         // where the fused prologue / epilogue cost of the W1|W3 and QKV GEMVs sits: each
         // prologue x epilogue combination of the same weights, bf16 and Q8

@@ -2782,42 +2782,50 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
 }
 
 // Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
-// bucket >= R (the bucket's unused rows are zero), from the wpack13 planes (packed = 1) or
-// from the raw rows.  Returns flags: bit 0 the packed instance ran, bit 1 the per-row
-// summation order is k_gemv's (every shape: k_gemvr never splits K); -1 on error.
+// bucket >= R (the bucket's unused rows are zero), from the wpack13 planes (packed = 1), the
+// wmx4 plane built from W (packed = 2, as vox_hip_gemv_wpack) or the raw rows.  Returns flags:
+// bit 0 the wpack13 instance ran, bit 1 the per-row summation order is k_gemv's (every shape:
+// k_gemvr never splits K), bit 2 the wmx4 instance ran (clear, and the raw rows streamed, when W
+// is not MXFP4-valued or the shape has no wmx4 instance); -1 on error.
 extern "C" int vox_hip_gemv_rows(int rows, int K, const uint16_t* W, const float* x, int R, float* y, int packed) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
     if (!W || !x || !y) return set_err("gemv_rows: null argument");
     if (R < 1 || R > GEMVR_MAX_ROWS) return set_err("gemv_rows: %d rows (1..%d)", R, GEMVR_MAX_ROWS);
     if (!gemvr_ok(PRO_NONE, EPI_STORE, rows, K)) return set_err("gemv_rows: no k_gemvr instance for %d x %d", rows, K);
+    if (packed < 0 || packed > 2) return set_err("gemv_rows: packed must be 0, 1 or 2 (got %d)", packed);
     if (twin_init()) return -1;
     int Rb = 1;
     while (Rb < R) Rb *= 2;
     uint8_t* dW = nullptr;
     float *dx = nullptr, *dy = nullptr;
     WPackD P = {nullptr, nullptr, 0};
+    WMx4D M = {nullptr, nullptr};
     vox_hip_wpack_stats_t S;
+    vox_hip_wmx4_stats_t MS;
     memset(&S, 0, sizeof S);
+    memset(&MS, 0, sizeof MS);
     auto run = [&]() -> int {
         CK(dalloc(&dW, (size_t)rows * K * 2));
         CK(dalloc(&dx, (size_t)Rb * K));
         CK(dalloc(&dy, (size_t)Rb * rows));
         CK(hipMemset(dx, 0, (size_t)Rb * K * 4));
         if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)R * K * 4)) return -1;
-        if (wpack_make(packed, S, &P, W, rows, K, 0)) return -1;
+        if (wpack_make(packed == 1, S, &P, W, rows, K, 0)) return -1;
+        if (wmx4_make(packed == 2 && gemvr_ok_mx4(PRO_NONE, EPI_STORE, rows, K), MS, &M, W, rows, K, 0)) return -1;
         GemvRArgs a;
         memset(&a, 0, sizeof a);
         a.g.x = dx; a.ldx = K; a.g.K = K; a.g.W = dW; a.g.rows = rows; a.g.y = dy; a.ldy = rows;
         wpack_args(a.g, P);
+        wmx4_args(a.g, M);
         CK(launch_gemvr(PRO_NONE, EPI_STORE, Rb, a, g_twin_st));
         CK(hipStreamSynchronize(g_twin_st));
         CK(hipMemcpy(y, dy, (size_t)R * rows * 4, hipMemcpyDeviceToHost));
         return 0;
     };
     const int rc = run();
-    const int was_packed = P.main != nullptr;
-    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side);
-    return rc ? -1 : (was_packed | 2);
+    const int ran = (P.main ? 1 : 0) | (M.plane ? 4 : 0);
+    dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side); dfree(M.plane);
+    return rc ? -1 : (ran | 2);
 }
 
 // Test entry: nb rows x [nb][K] against one bf16 matrix W [N][K] through the batched step's own
@@ -3117,8 +3125,13 @@ struct vox_hip_batch {
     // the mode changes between calls without a capture being dropped.
     int gemv_rows;
     float* hid;      // SwiGLU rows [GEMVR_MAX_ROWS][dec_hidden] (allocated when the mode is first set)
-    hipGraphExec_t gvexec[3][4][STEP_GRAPHS];
+    // (gemv_wmx4: [3 gemv_wmx4 + element type], as gexec)
+    hipGraphExec_t gvexec[6][4][STEP_GRAPHS];
     long long n_gemv_replays, n_gemv_rows, n_gemv_captures;
+    // the GEMV step streams the wmx4 GEMV plane of every tensor that has one
+    // (vox_hip_batch_set_gemv_wmx4); a tensor without one keeps its wpack13 or raw launch
+    int gemv_wmx4;
+    long long n_gemv_wmx4_replays;
     // rows of the last call (b->logits row i = stream luid[i], from its last step when llive[i])
     unsigned long long luid[VOX_MAX_BATCH];
     int llive[VOX_MAX_BATCH];
@@ -3213,6 +3226,7 @@ extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
 }
 
 static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows);
+static int batch_set_gemv_wmx4(vox_hip_batch_t* b, int on, bool quiet);
 
 extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_streams) {
     if (!m || max_streams < 1 || max_streams > VOX_MAX_BATCH) {
@@ -3272,6 +3286,10 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
         if (r && !(m->tok_emb_s || m->dec[0].sqkv) && batch_set_gemv_rows(b, r)) return fail();
     }
     b->wmx4 = m->fstats[0] ? 1 : 0;
+    // VOX_HIP_BATCH_GEMV_WMX4=1: the GEMV step's initial weight source (unset: 0; a model
+    // without a wmx4 GEMV plane keeps 0)
+    if (const char* e = getenv("VOX_HIP_BATCH_GEMV_WMX4"))
+        if (atoi(e) == 1) batch_set_gemv_wmx4(b, 1, true);
     return b;
 }
 
@@ -3363,13 +3381,15 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
 }
 
 // The same step for a bucket of nb <= 8 slots on the R-row GEMV (k_gemvr): the
-// single-stream step's five launches per layer with every weight byte (bf16 rows, or the
-// model's wpack13 planes) read once for the nb rows, and no planes, slabs or tickets.  Between
+// single-stream step's five launches per layer with every weight byte (bf16 rows, the model's
+// wpack13 planes or, with wmx4 set, the wmx4 GEMV plane of each tensor that has one) read once
+// for the nb rows, and no planes, slabs or tickets.  Between
 // the launches the rows live in b->x (residual stream, updated in place), b->q, b->att and
 // b->hid; attention is the slot-table kernel of the single-stream step.  b->x is complete
 // before and after either step, so the two may alternate from one call to the next.
-static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt) {
+static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4) {
     vox_hip_model_t* m = b->m;
+    auto mx = [&](GemvArgs& g, const WMx4D& M) { if (wmx4) wmx4_args(g, M); };
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
@@ -3396,23 +3416,27 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt) {
         a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kvt = kvt;
         a.slots = b->slots; a.ring_off = ap.ring_off;
         wpack_args(a.g, L.pqkv);
+        mx(a.g, L.mqkv);
         CK(launch_gemvr(PRO_NORM, EPI_QKV, nb, a, st));
         CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         // wo + residual
         memset(&a, 0, sizeof a);
         a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
         wpack_args(a.g, L.po);
+        mx(a.g, L.mo);
         CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up
         memset(&a, 0, sizeof a);
         a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.w13; a.g.rows = 2 * DH; a.g.norm_w = L.ffn_norm;
         a.g.ada = m->ada_scale + (size_t)l * DD; a.g.eps = c.dec_eps; a.g.y = b->hid; a.ldy = DH;
         wpack_args(a.g, L.p13);
+        mx(a.g, L.m13);
         CK(launch_gemvr(PRO_NORM_ADA, EPI_SWIGLU, nb, a, st));
         // W2 + residual
         memset(&a, 0, sizeof a);
         a.g.x = b->hid; a.ldx = DH; a.g.K = DH; a.g.W = L.w2; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
         wpack_args(a.g, L.p2);
+        mx(a.g, L.m2);
         CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
     }
     // final norm + LM head rows, then the batched step's own end (argmax, alternatives, token
@@ -3421,19 +3445,40 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = m->tok_emb; a.g.rows = c.vocab; a.g.norm_w = m->dec_norm;
     a.g.eps = c.dec_eps; a.g.y = b->logits; a.ldy = c.vocab;
     wpack_args(a.g, m->plm);
+    mx(a.g, m->mlm);
     CK(launch_gemvr(PRO_NORM, EPI_STORE, nb, a, st));
     CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
 }
 
-// the shapes of the model all have k_gemvr instances
-static bool model_gemvr_ok(const vox_hip_model_t* m) {
+// the shapes of the model all have k_gemvr instances; wmx4: the tensors that have a wmx4 GEMV
+// plane have wmx4 instances too
+static bool model_gemvr_ok(const vox_hip_model_t* m, int wmx4 = 0) {
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
-    return gemvr_ok(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DQ) &&
-           gemvr_ok(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DH) &&
-           gemvr_ok(PRO_NORM, EPI_STORE, c.vocab, DD);
+    if (!(gemvr_ok(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DQ) &&
+          gemvr_ok(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DH) &&
+          gemvr_ok(PRO_NORM, EPI_STORE, c.vocab, DD)))
+        return false;
+    if (!wmx4) return true;
+    for (const DecLayerD& L : m->dec)
+        if ((L.mqkv.plane && !gemvr_ok_mx4(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD)) ||
+            (L.mo.plane && !gemvr_ok_mx4(PRO_NONE, EPI_RESID, DD, DQ)) ||
+            (L.m13.plane && !gemvr_ok_mx4(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD)) ||
+            (L.m2.plane && !gemvr_ok_mx4(PRO_NONE, EPI_RESID, DD, DH)))
+            return false;
+    return !m->mlm.plane || gemvr_ok_mx4(PRO_NORM, EPI_STORE, c.vocab, DD);
+}
+
+// tensors of the GEMV step (4 per layer and the LM head) with / without a wmx4 GEMV plane
+static void model_gemv_wmx4_count(const vox_hip_model_t* m, long long* with, long long* without) {
+    long long n = 0;
+    for (const DecLayerD& L : m->dec)
+        for (const WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) n += M->plane != nullptr;
+    n += m->mlm.plane != nullptr;
+    *with = n;
+    *without = 4LL * (long long)m->dec.size() + 1 - n;
 }
 
 static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
@@ -3453,6 +3498,36 @@ static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
 extern "C" int vox_hip_batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
     if (!b) return set_err("batch_set_gemv_rows: null batch");
     return batch_set_gemv_rows(b, max_rows);
+}
+
+static int batch_set_gemv_wmx4(vox_hip_batch_t* b, int on, bool quiet) {
+    if (b->call.active) return quiet ? -1 : set_err("batch_set_gemv_wmx4: a begun call was not finished");
+    if (on) {
+        const vox_hip_model_t* m = b->m;
+        long long with = 0, without = 0;
+        model_gemv_wmx4_count(m, &with, &without);
+        if (!with)
+            return quiet ? -1
+                         : set_err("batch_set_gemv_wmx4: the model has no wmx4 GEMV plane (vox_hip_set_wmx4 before its creation; "
+                                   "not Q8, not VOX_HIP_WPACK=0)");
+        if (!model_gemvr_ok(m, 1))
+            return quiet ? -1 : set_err("batch_set_gemv_wmx4: no wmx4 k_gemvr instance for this model's shapes");
+    }
+    b->gemv_wmx4 = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int vox_hip_batch_set_gemv_wmx4(vox_hip_batch_t* b, int on) {
+    if (!b) return set_err("batch_set_gemv_wmx4: null batch");
+    return batch_set_gemv_wmx4(b, on, false);
+}
+
+extern "C" int vox_hip_batch_gemv_wmx4_stats(const vox_hip_batch_t* b, long long out4[4]) {
+    if (!b || !out4) return set_err("batch_gemv_wmx4_stats: null argument");
+    out4[0] = b->gemv_wmx4;
+    out4[1] = b->n_gemv_wmx4_replays;
+    model_gemv_wmx4_count(b->m, &out4[2], &out4[3]);
+    return 0;
 }
 
 extern "C" int vox_hip_batch_set_wmx4(vox_hip_batch_t* b, int on) {
@@ -3485,8 +3560,10 @@ static int slot_bucket(int n, int* g) {
 // first time, and again only when the rope table moved), or eager launches
 static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
-    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kvt) : batch_step(b, nb, splits, kvt, wmx4); };
+    const int gwmx4 = b->gemv_wmx4;  // likewise (vox_hip_batch_set_gemv_wmx4: on only with a plane to stream)
+    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4); };
     if (gemv) b->n_gemv_replays += steps;
+    if (gemv && gwmx4) b->n_gemv_wmx4_replays += steps;
     if (!use_graphs()) {
         for (int k = 0; k < steps; k++)
             if (step()) return -1;
@@ -3497,7 +3574,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = gemv ? b->gvexec[kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
+    hipGraphExec_t& ge = gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));

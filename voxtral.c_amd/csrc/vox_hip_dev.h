@@ -209,6 +209,33 @@ __device__ __forceinline__ float dot8m4(uint32_t w, uint32_t scale_byte, float4 
     return acc;
 }
 
+// dot8m4 in two halves, for a kernel that feeds one decoded chunk to several input rows
+// (k_gemvr): dec8m4 runs dot8m4's four converts once, dot8f runs dot8's FMAs in dot8's order
+// on the eight f32 weights.  dot8f(dec8m4(w, s), a, b, acc) has dot8m4(w, s, a, b, acc)'s bits.
+struct f32x8 {
+    f32x2 p[4];
+};
+__device__ __forceinline__ f32x8 dec8m4(uint32_t w, uint32_t scale_byte) {
+    const float sc = __uint_as_float(scale_byte << 23);
+    f32x8 d;
+    d.p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 0);
+    d.p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 1);
+    d.p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 2);
+    d.p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, 3);
+    return d;
+}
+__device__ __forceinline__ float dot8f(const f32x8& d, float4 a, float4 b, float acc) {
+    acc = fmaf(d.p[0].x, a.x, acc);
+    acc = fmaf(d.p[0].y, a.y, acc);
+    acc = fmaf(d.p[1].x, a.z, acc);
+    acc = fmaf(d.p[1].y, a.w, acc);
+    acc = fmaf(d.p[2].x, b.x, acc);
+    acc = fmaf(d.p[2].y, b.y, acc);
+    acc = fmaf(d.p[3].x, b.z, acc);
+    acc = fmaf(d.p[3].y, b.w, acc);
+    return acc;
+}
+
 // dot of 16 int8 weights (one uint4, Q8 rows) with 16 f32 activations: each byte is
 // sign-extended and converted exactly (q8_matvec_fused, voxtral_kernels.c:277-318)
 __device__ __forceinline__ float i8f(uint32_t w, int b) { return (float)((int32_t)(w << (24 - 8 * b)) >> 24); }

@@ -154,6 +154,9 @@ int gemv_occupancy(const void* fn);
 // LM head), NONE/STORE}.  gemvr_ok: the launch has an instance (K rounds <= 2 where the input
 // is a dec_dim row or the group is 8 rows, <= 5 otherwise)
 bool gemvr_ok(int pro, int epi, int rows, int K);
+// the same for the wmx4 instances (g.wm_plane set: streamed in preference to the wpack13 planes,
+// in groups of gemv_rowgroup_mx4(rows) = 4 or 8 rows)
+bool gemvr_ok_mx4(int pro, int epi, int rows, int K);
 hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st);
 const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a);
 // part: H * attn_maxch(window) * (hd + 2) floats of partials, then KVH ints (zeroed before

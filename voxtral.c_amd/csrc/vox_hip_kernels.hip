@@ -1164,7 +1164,9 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 // R-row weight-streaming GEMV (R = 1, 2, 4, 8: the slot buckets of a small batched decode
 // step): y[r] = W x[r].  k_gemv's block, row groups, grid, chunk mapping, non-temporal buffer
 // loads, early next-group loads and zero-length descriptor, so the P13 instance streams the
-// model's own wpack13 planes; every weight register feeds R FMA chains.  The x rows of a pass
+// model's own wpack13 planes and the MX4 instance its wmx4 GEMV plane (one record load per K
+// round, k_gemv<WF_MX4>'s fetch; each (round, row) nibble dword is decoded to eight f32 once
+// and feeds the R chains); every weight register feeds R FMA chains.  The x rows of a pass
 // live in registers (R * KQ * 8 floats per thread).  More than 160 floats (R * KQ > 20: W2 of
 // the full model at 8 rows would take 320) do not fit beside the weights: such an instance
 // runs two passes of R / 2 rows over the block's groups and reads its weights twice
@@ -1181,9 +1183,10 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 // ============================================================================
 template <int PRO, int EPI, int RB, int KQ, int WF, int R>
 __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
-    static_assert(WF == WF_BF16 || WF == WF_P13, "k_gemvr streams bf16 rows or wpack13 planes");
-    constexpr bool WP = WF == WF_P13;
+    static_assert(WF == WF_BF16 || WF == WF_P13 || WF == WF_MX4, "k_gemvr streams bf16 rows, wpack13 planes or the wmx4 plane");
+    constexpr bool WP = WF == WF_P13, WM = WF == WF_MX4;
     constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
+    constexpr int RW = RB + (RB + 3) / 4;           // wmx4 record dwords per (group, chunk)
     constexpr int RP = R * KQ > 20 ? R / 2 : R;     // rows per pass
     constexpr bool QKVE = EPI == EPI_QKV;
     constexpr bool PAIRED = QKVE || EPI == EPI_SWIGLU;
@@ -1196,9 +1199,11 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
     const int K = a.K, KC = K >> 3;
     const int ngroups = a.rows / RB;
     const int G = gridDim.x;
-    const int rowbytes = WP ? KC * 12 : K * 2;
-    void* const wbase = const_cast<void*>(WP ? a.wp_main : a.W);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, a.rows * rowbytes, 0x00020000);
+    // wmx4: "rowbytes" is a group's bytes (KC records), the plane ngroups of them (k_gemv)
+    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * 2;
+    void* const wbase = const_cast<void*>(WM ? a.wm_plane : WP ? a.wp_main : a.W);
+    const __amdgpu_buffer_rsrc_t wrs =
+        __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
     void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
@@ -1208,7 +1213,7 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
 #pragma unroll
     for (int j = 0; j < KQ; j++) {
         const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * (WP ? 12 : 16);
+        voff[j] = (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
     }
     // epilogue ownership: thread orow * NL + ol of wave 0 finishes row (or row pair) ol of the
     // group for input row orow of the pass
@@ -1220,12 +1225,14 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
     for (int r0 = 0; r0 < R; r0 += RP) {
         int g = blockIdx.x;
         int rows[RB];
-        uint4 wv[KQ][RB];
+        uint4 wv[WM ? 1 : KQ][RB];
+        uint32_t mr[WM ? KQ : 1][RW];
         uint32_t sd[SW];
         // first group's weights are independent of x: issue them before the prologue
         gemv_rows<EPI, RB>(g, rows);
         if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);
-        gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
+        if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
+        else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
 
         float4 xr[RP][KQ][2];
         float4 nwr[KQ][2], adr[KQ][2];
@@ -1347,12 +1354,20 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
 #pragma unroll
             for (int j = 0; j < KQ; j++)
 #pragma unroll
-                for (int i = 0; i < RB; i++)
+                for (int i = 0; i < RB; i++) {
+                    if constexpr (WM) {
+                        // one decode per (round, row) of the group, then dot8's FMAs per input row
+                        const f32x8 wd = dec8m4(mr[j][i], (mr[j][RB + (i >> 2)] >> (8 * (i & 3))) & 0xffu);
 #pragma unroll
-                    for (int r = 0; r < RP; r++) {
-                        if (WP) acc[r][i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[r][j][0], xr[r][j][1], acc[r][i]);
-                        else acc[r][i] = dot8(wv[j][i], xr[r][j][0], xr[r][j][1], acc[r][i]);
+                        for (int r = 0; r < RP; r++) acc[r][i] = dot8f(wd, xr[r][j][0], xr[r][j][1], acc[r][i]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RP; r++) {
+                            if (WP) acc[r][i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[r][j][0], xr[r][j][1], acc[r][i]);
+                            else acc[r][i] = dot8(wv[j][i], xr[r][j][0], xr[r][j][1], acc[r][i]);
+                        }
                     }
+                }
             g += G;
             // the next group's loads before this group's reduction, unconditionally; past the
             // last group through the zero-length descriptor (k_gemv)
@@ -1360,7 +1375,8 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
                 const bool more = g < ngroups;
                 gemv_rows<EPI, RB>(more ? g : 0, rows);
                 if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
-                gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
+                if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
+                else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
             }
 #pragma unroll
             for (int r = 0; r < RP; r++)
@@ -3891,30 +3907,42 @@ static const void* gemvr_fn_kq(int kq, int R) {
         default: return nullptr;
     }
 }
+// wf: WF_BF16, WF_P13 or WF_MX4.  The MX4 instances exist for the 4- and 8-row groups of the
+// wmx4 plane (gemv_rb_mx4 of a row count that is a multiple of 4); a 2-row wmx4 plane has none
 template <int P, int E>
-static const void* gemvr_fn(int rb, int kq, bool packed, int R) {
+static const void* gemvr_fn(int rb, int kq, int wf, int R) {
+    if (wf == WF_MX4) {
+        if (rb == 4) return gemvr_fn_kq<P, E, 4, WF_MX4>(kq, R);
+        if (rb == 8) return gemvr_fn_kq<P, E, 8, WF_MX4>(kq, R);
+        return nullptr;
+    }
 #define GEMVR_RB(RB) \
-    if (rb == RB) return packed ? gemvr_fn_kq<P, E, RB, WF_P13>(kq, R) : gemvr_fn_kq<P, E, RB, WF_BF16>(kq, R);
+    if (rb == RB) return wf == WF_P13 ? gemvr_fn_kq<P, E, RB, WF_P13>(kq, R) : gemvr_fn_kq<P, E, RB, WF_BF16>(kq, R);
     GEMVR_RB(2) GEMVR_RB(4) GEMVR_RB(8)
 #undef GEMVR_RB
     return nullptr;
 }
-static const void* gemvr_pick(int pro, int epi, int rows, int K, bool packed, int R) {
+static const void* gemvr_pick(int pro, int epi, int rows, int K, int wf, int R) {
     if (!gemv_ok(rows, K, 0)) return nullptr;
-    const int rb = gemv_rb(rows), kq = ((K >> 3) + 255) / 256;
+    if (wf == WF_MX4 && !gemv_ok_mx4(rows, K)) return nullptr;
+    const int rb = wf == WF_MX4 ? gemv_rb_mx4(rows) : gemv_rb(rows), kq = ((K >> 3) + 255) / 256;
 #define GEMVR_FN(P, E) \
-    if (pro == P && epi == E) return gemvr_fn<P, E>(rb, kq, packed, R);
+    if (pro == P && epi == E) return gemvr_fn<P, E>(rb, kq, wf, R);
     GEMVR_FN(PRO_NORM, EPI_QKV) GEMVR_FN(PRO_NONE, EPI_RESID) GEMVR_FN(PRO_NORM_ADA, EPI_SWIGLU)
     GEMVR_FN(PRO_NORM, EPI_STORE) GEMVR_FN(PRO_NONE, EPI_STORE)
 #undef GEMVR_FN
     return nullptr;
 }
 
-bool gemvr_ok(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, false, 1) != nullptr; }
+bool gemvr_ok(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_BF16, 1) != nullptr; }
+bool gemvr_ok_mx4(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_MX4, 1) != nullptr; }
+
+// weight source of a launch, in gemv_k's order: the wmx4 plane, the wpack13 planes, the raw rows
+static int gemvr_wf(const GemvRArgs& a) { return a.g.wm_plane ? WF_MX4 : a.g.wp_main ? WF_P13 : WF_BF16; }
 
 // kernel instance launch_gemvr would use (tools, occupancy queries)
 const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a) {
-    return gemvr_pick(pro, epi, a.g.rows, a.g.K, a.g.wp_main != nullptr, R);
+    return gemvr_pick(pro, epi, a.g.rows, a.g.K, gemvr_wf(a), R);
 }
 
 hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st) {
@@ -3923,7 +3951,9 @@ hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t
     if (!fn) return hipErrorInvalidValue;
     GemvRArgs args = a;
     void* kargs[] = {&args};
-    return hipLaunchKernel(fn, dim3(gemv_grid(a.g.rows)), dim3(256), kargs, 0, st);
+    // the wmx4 plane has its own group size, hence its own grid (k_gemv's wmx4 launch)
+    const int grid = a.g.wm_plane ? gemv_grid_mx4(a.g.rows) : gemv_grid(a.g.rows);
+    return hipLaunchKernel(fn, dim3(grid), dim3(256), kargs, 0, st);
 }
 
 // partial slots per head (at least 4)

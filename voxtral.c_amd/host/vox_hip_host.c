@@ -1039,6 +1039,25 @@ int vh_sched_detach(vh_sched_t *q, vh_stream_t *s) {
 
 void vh_sched_set_step_cap(vh_sched_t *q, int cap) { q->step_cap = cap > 0 ? cap : 0; }
 
+static int sched_batch(vh_sched_t *q) {
+    if (!q->batch) q->batch = vox_hip_batch_create(q->ctx->model, q->cap);
+    return q->batch ? 0 : fail("batch: %s", vox_hip_last_error());
+}
+
+int vh_sched_set_gemv_rows(vh_sched_t *q, int max_rows) {
+    if (!q) return fail("sched_set_gemv_rows: null scheduler");
+    if (sched_batch(q)) return -1;
+    if (vox_hip_batch_set_gemv_rows(q->batch, max_rows)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_sched_set_gemv_wmx4(vh_sched_t *q, int on) {
+    if (!q) return fail("sched_set_gemv_wmx4: null scheduler");
+    if (sched_batch(q)) return -1;
+    if (vox_hip_batch_set_gemv_wmx4(q->batch, on)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
 int vh_set_kv_dtype(vh_ctx_t *ctx, int dtype) {
     if (vox_hip_model_set_kv_dtype(ctx->model, dtype)) return fail("%s", vox_hip_last_error());
     return 0;

@@ -64,10 +64,11 @@ def gemv_wpack(W_bf16, x, packed):
     return y, (rc if int(packed) == 2 else bool(rc))
 
 
-def gemv_rows(W_bf16, x, packed: bool):
+def gemv_rows(W_bf16, x, packed):
     """Test entry: (y [R, rows], flags) of y[r] = W x[r] for R <= 8 rows through the R-row GEMV
-    (vox_hip_gemv_rows); flags bit 0: the packed instance ran, bit 1: the per-row summation
-    order is the single-row GEMV's"""
+    (vox_hip_gemv_rows); packed: 0 raw rows, 1 (or True) wpack13 planes, 2 the wmx4 plane.
+    flags bit 0: the wpack13 instance ran, bit 1: the per-row summation order is the single-row
+    GEMV's, bit 2: the wmx4 instance ran"""
     init()
     W = np.ascontiguousarray(W_bf16, np.uint16)
     xv = np.ascontiguousarray(x, np.float32)
@@ -100,6 +101,7 @@ EXPORTS = [
     "vox_hip_batch_begin_rows", "vox_hip_batch_finish",
     "vox_hip_batch_read_logits",
     "vox_hip_batch_stats", "vox_hip_batch_set_gemv_rows", "vox_hip_batch_gemv_stats", "vox_hip_gemv_rows",
+    "vox_hip_batch_set_gemv_wmx4", "vox_hip_batch_gemv_wmx4_stats",
     "vox_hip_stream_state", "vox_hip_stream_set_alt", "vox_hip_stream_read_alts", "vox_hip_sgemm_bf16", "vox_hip_sgemm_q8", "vox_hip_fused_qkv_bf16",
     "vox_hip_fused_ffn_bf16", "vox_hip_encoder_attention", "vox_hip_encoder_full_step",
     "vox_hip_decoder_prefill_step", "vox_hip_decoder_start", "vox_hip_decoder_end",
@@ -160,6 +162,8 @@ def lib():
         "vox_hip_batch_set_gemv_rows": (I, [P, I]),
         "vox_hip_batch_gemv_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_gemv_rows": (I, [I, I, P, fp, I, fp, I]),
+        "vox_hip_batch_set_gemv_wmx4": (I, [P, I]),
+        "vox_hip_batch_gemv_wmx4_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_stream_set_alt": (I, [P, I, F]),
         "vox_hip_stream_read_alts": (I, [P, I, I, ip, fp]),
         "vox_hip_sgemm_bf16": (None, [I, I, I, fp, P, fp]),
@@ -760,6 +764,20 @@ class Batch:
         fragment copies (off); the same bits.  Returns 0, or -1 with last_error() set (the model
         has no fragment planes, a begun call)."""
         return lib().vox_hip_batch_set_wmx4(self.h, int(bool(on)))
+
+    def set_gemv_wmx4(self, on: bool) -> int:
+        """vox_hip_batch_set_gemv_wmx4: the R-row GEMV step streams the wmx4 GEMV plane of every
+        tensor that has one (on) or the wpack13 planes / raw rows (off); same bits.  0, or -1
+        (vox_hip.last_error()) when the model has no wmx4 GEMV plane or inside a begun call."""
+        return lib().vox_hip_batch_set_gemv_wmx4(self.h, int(bool(on)))
+
+    def gemv_wmx4_stats(self) -> tuple:
+        """vox_hip_batch_gemv_wmx4_stats: (flag, GEMV step replays on wmx4 planes, step tensors
+        with a wmx4 GEMV plane, step tensors without)"""
+        out = (ctypes.c_longlong * 4)()
+        if lib().vox_hip_batch_gemv_wmx4_stats(self.h, out) != 0:
+            _err("vox_hip_batch_gemv_wmx4_stats")
+        return tuple(int(v) for v in out)
 
     def gemv_stats(self) -> tuple:
         """vox_hip_batch_gemv_stats: (max_rows, GEMV step replays, live rows, GEMV captures)"""
