@@ -114,8 +114,9 @@ int vox_hip_model_set_kv_fp16(vox_hip_model_t *m, int on);
  * stays f32 in the f32 ring's order.  A quarter of the f32 ring's bytes per step and per
  * stream.  Its effect on transcripts is NOT evaluated.  Opt-in: off unless VOX_HIP_KV_FP8 is
  * set nonzero at model creation (it wins over VOX_DECODER_KV_FP16) or dtype = 2 is passed.
- * The encoder KV stays f32.  head_dim 128 only for 1 and 2; returns 0, or -1
- * (vox_hip_last_error) for another head_dim or dtype. */
+ * The encoder KV stays f32.  Every decoder path honours the element type, the batch's stacked
+ * prefill of joining streams included (vox_hip_batch_set_prefill_kv).  head_dim 128 only for 1
+ * and 2; returns 0, or -1 (vox_hip_last_error) for another head_dim or dtype. */
 int vox_hip_model_set_kv_dtype(vox_hip_model_t *m, int dtype);
 /* wpack13 (no reference counterpart): at creation every bf16 matrix of the single-stream
  * decode step (Q|K|V, wo, W1|W3, W2 per decoder layer, and the LM head) whose nonzero
@@ -325,7 +326,8 @@ int vox_hip_stream_read_alts(vox_hip_stream_t *s, int first, int n, int *ids_out
  * stream that has adapter rows left by one greedy token per step; the weights are streamed
  * once per step for all of them, attention / KV / argmax use each stream's own state.
  * Streams not started yet whose prompt is complete are prefilled first (several of them in
- * one stacked pass) and take their first token in the batched steps.  Every stream stops on
+ * one stacked pass) and take their first token in the batched steps.  The stacked prefill
+ * covers all three decoder KV ring types (f32, IEEE half, FP8 E4M3; vox_hip_batch_set_prefill_kv).  Every stream stops on
  * the device when it has used its adapter rows, after max_steps tokens or (stop_at_eos) after
  * EOS, while the others go on; streams join and leave a batch without a graph capture (the
  * step graphs read a device slot table).  Streams with alternatives on
@@ -361,6 +363,16 @@ int vox_hip_batch_read_logits(vox_hip_batch_t *b, vox_hip_stream_t *s, float *ou
 /* Counters since creation: [0] calls, [1] step replays, [2] live rows over those steps,
  * [3] step-graph captures, [4] batched prefill passes, [5] prefilled streams. */
 int vox_hip_batch_stats(const vox_hip_batch_t *b, long long *out6);
+/* The prefill of joining streams whose decoder KV rings are IEEE half or FP8: on = 1 (the
+ * default) stacks their prompts into the shared passes on the batch queue exactly as f32
+ * streams' are -- the layers' weights read once per pass of up to 26 prompts, no wait on the
+ * members' queues in vox_hip_batch_decode_rows / begin_rows --, with the RoPE + K/V append and
+ * the causal attention at the ring's element type (same stores, same f32 arithmetic and order as
+ * the single-stream prefill).  on = 0 prefills each such stream on its own queue, one pass and
+ * one host wait per stream (what the batch did before; for measurements).  f32 streams ignore
+ * the flag.  VOX_HIP_BATCH_PREFILL_KV=0 sets the initial value at vox_hip_batch_create.  Returns
+ * 0; -1 (vox_hip_last_error) between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+int vox_hip_batch_set_prefill_kv(vox_hip_batch_t *b, int on);
 /* Opt-in step for small batches: the R-row GEMV (k_gemvr) streams each weight matrix once per
  * step for the whole bucket -- bf16 rows or the model's wpack13 planes, as the single-stream
  * step does -- in five launches per layer, instead of the skinny MFMA GEMMs over the

@@ -3132,6 +3132,9 @@ struct vox_hip_batch {
     // (vox_hip_batch_set_gemv_wmx4); a tensor without one keeps its wpack13 or raw launch
     int gemv_wmx4;
     long long n_gemv_wmx4_replays;
+    // the stacked prefill takes streams with 16-bit and one-byte rings too (default; 0: those
+    // streams prefill one by one on their own queues, vox_hip_batch_set_prefill_kv)
+    int prefill_kv;
     // rows of the last call (b->logits row i = stream luid[i], from its last step when llive[i])
     unsigned long long luid[VOX_MAX_BATCH];
     int llive[VOX_MAX_BATCH];
@@ -3290,6 +3293,12 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
     // without a wmx4 GEMV plane keeps 0)
     if (const char* e = getenv("VOX_HIP_BATCH_GEMV_WMX4"))
         if (atoi(e) == 1) batch_set_gemv_wmx4(b, 1, true);
+    // VOX_HIP_BATCH_PREFILL_KV=0: new streams with 16-bit or one-byte rings take the per-stream
+    // prefill on their own queues instead of the stacked pass (A/B; f32 streams ignore it)
+    {
+        const char* e = getenv("VOX_HIP_BATCH_PREFILL_KV");
+        b->prefill_kv = (e && atoi(e) == 0) ? 0 : 1;
+    }
     return b;
 }
 
@@ -3539,6 +3548,13 @@ extern "C" int vox_hip_batch_set_wmx4(vox_hip_batch_t* b, int on) {
     return 0;
 }
 
+extern "C" int vox_hip_batch_set_prefill_kv(vox_hip_batch_t* b, int on) {
+    if (!b) return set_err("batch_set_prefill_kv: null batch");
+    if (b->call.active) return set_err("batch_set_prefill_kv: a begun call was not finished");
+    b->prefill_kv = on ? 1 : 0;
+    return 0;
+}
+
 extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out4) {
     if (!b || !out4) return set_err("batch_gemv_stats: null argument");
     out4[0] = b->gemv_rows;
@@ -3611,12 +3627,15 @@ static void stream_steps_done(vox_hip_stream_t* s, int produced, int last_token)
 // decoder prefill of voxtral.c:1036-1057 per stream; rows [b np, (b + 1) np) = stream b):
 // RMSNorm and the projections over all rows (every weight byte read once for the group),
 // RoPE + K/V append and the causal attention per stream against its own ring (the batched
-// encoder's row-offset kernels), scratch of ss[0].  One stream, or 16-bit rings, take the
+// encoder's row-offset kernels, at the ring element type of the streams: batch_begin refuses
+// mixed types, so ss[0]->kvt speaks for the group), scratch of ss[0].  One stream takes the
 // single-stream prefill.  The member queues must be idle.
 // bounded (vox_hip_batch_decode_rows): a single new stream takes the stacked path too, on the
-// batch queue -- its own queue may be busy with an encoder pass the steps overlap; 16-bit rings and
-// stacks past ENC_SUB rows still take the per-stream prefill on the member's own queue and
-// wait there for any encoder pass queued on it (correct; the overlap is lost for them)
+// batch queue -- its own queue may be busy with an encoder pass the steps overlap; only stacks
+// past ENC_SUB rows (a prompt longer than one pass) still take the per-stream prefill on the
+// member's own queue and wait there for any encoder pass queued on it.
+// prefill_kv == 0 (vox_hip_batch_set_prefill_kv, A/B): streams with 16-bit or one-byte rings
+// take that per-stream prefill as well (correct; the shared weight pass and the overlap are lost)
 static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B, bool bounded) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
@@ -3624,12 +3643,14 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
     // more prompts than one pass holds (ENC_SUB rows: 26 prompts of 39 rows): stacked passes of
     // as many as fit
     const int per = std::max(1, ENC_SUB / np);
-    if (B > per && !ss[0]->kvt) {
+    const int kvt = ss[0]->kvt;
+    const bool one_by_one = kvt != KV_F32 && !b->prefill_kv;
+    if (B > per && !one_by_one) {
         for (int i0 = 0; i0 < B; i0 += per)
             if (batch_prefill(b, ss + i0, std::min(per, B - i0), bounded)) return -1;
         return 0;
     }
-    if ((B == 1 && !bounded) || ss[0]->kvt || B * np > ENC_SUB) {
+    if ((B == 1 && !bounded) || one_by_one || B * np > ENC_SUB) {
         for (int i = 0; i < B; i++) {
             if (stream_prefill(ss[i])) return -1;
             CK(hipStreamSynchronize(ss[i]->st));
@@ -3668,9 +3689,9 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
                     er.Kc[i] = dec_ring(ss[i], ss[i]->dk, l);
                     er.Vc[i] = dec_ring(ss[i], ss[i]->dv, l);
                 }
-                CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st));
+                CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st, kvt));
                 CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
-                                    lead->dpa));
+                                    lead->dpa, kvt));
                 return 0;
             }))
             return -1;
@@ -3689,9 +3710,9 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
         CK(launch_rmsnorm_rows(X, DD, lead->xnd, DD, L.attn_norm, nullptr, N, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_STORE, 3, lead->xnd, DD, L.wqkv, L.sqkv, DD, N, DQ + 2 * DKV, nullptr, lead->qkvd, DQ + 2 * DKV,
                        st, gws, gws_n));
-        CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st));
-        CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n,
-                            st));
+        CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st, kvt));
+        CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
+                            nullptr, kvt));
         CK(launch_gemm(EPI_RESID, 3, lead->attd, DQ, L.wo, L.so, DQ, N, DD, nullptr, X, DD, st, gws, gws_n));
         CK(launch_rmsnorm_rows(X, DD, lead->xnd, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, N, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_SWIGLU, 3, lead->xnd, DD, L.w13, L.s13, DD, N, 2 * DH, nullptr, lead->gated, DH, st, gws, gws_n));

@@ -184,12 +184,15 @@ struct EncRows {
     float* Vc[VOX_MAX_BATCH];
 };
 // RoPE + K/V append of every stacked row into its stream's ring (k_rope_kv per row block)
+// kvt (here and in launch_attn_rows): the rings' element type, KV_F32 for the encoder's; the
+// decoder's 16-bit and one-byte rings at head_dim 128 only, er.Kc / er.Vc then point at them
 hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd, const float* rope_table,
-                               const EncRows& er, float* q, int cap, hipStream_t st);
+                               const EncRows& er, float* q, int cap, hipStream_t st, int kvt = 0);
 // windowed attention of every stream's rows against its own ring, one launch (+ one combine):
 // Q / O stacked [N, H*hd]
 hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, int cap, float* O, int H, int KVH,
-                            int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs = nullptr);
+                            int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs = nullptr,
+                            int kvt = 0);
 constexpr int STEP_GRAPHS = 8;       // step graphs by attention split count 1, 2, 4, ..., 128
 hipError_t launch_attn_batch_dbg(const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
                                  int KVH, int splits, hipStream_t st);

@@ -435,7 +435,10 @@ __global__ __launch_bounds__(256) void k_rope_kv(const float* __restrict__ qkv, 
 }
 
 // k_rope_kv over the stacked rows of a batched encoder pass: block = one row, its stream found
-// from the row offsets (same operations per row as k_rope_kv)
+// from the row offsets (same operations per row as k_rope_kv).  KT: the ring element (float for
+// the encoder's rings; the decoder's stacked prefill takes its streams' type, er.Kc / er.Vc
+// being layer bases in bytes whatever they point at)
+template <class KT>
 __global__ __launch_bounds__(256) void k_rope_kv_rows(const float* __restrict__ qkv, int qd, int kvd, int hd,
                                                       const float* __restrict__ rope_table, const EncRows er,
                                                       float* __restrict__ q, int cap) {
@@ -447,8 +450,8 @@ __global__ __launch_bounds__(256) void k_rope_kv_rows(const float* __restrict__ 
     const float* xr = qkv + (size_t)row * ld;
     const float* rp = rope_table + (size_t)(er.pos0[b] + i) * hd;
     const int slot = (er.pos0[b] + i) % cap;
-    float* kr = er.Kc[b] + (size_t)slot * kvd;
-    float* vr = er.Vc[b] + (size_t)slot * kvd;
+    KT* kr = reinterpret_cast<KT*>(er.Kc[b]) + (size_t)slot * kvd;
+    KT* vr = reinterpret_cast<KT*>(er.Vc[b]) + (size_t)slot * kvd;
     for (int p = threadIdx.x; p < qd / 2; p += 256) {
         int d = (2 * p) % hd / 2;
         float c = rp[2 * d], sn = rp[2 * d + 1];
@@ -3586,10 +3589,16 @@ hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, cons
 VOX_KB_KNOB(g_attn_blocks, 0);  // tools/kbench knob: target grid size of the key-range split (0 = 512)
 
 hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd, const float* rope_table,
-                               const EncRows& er, float* q, int cap, hipStream_t st) {
+                               const EncRows& er, float* q, int cap, hipStream_t st, int kvt) {
     if (N <= 0) return hipSuccess;
-    if (er.B < 1 || er.B > VOX_MAX_BATCH) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rope_kv_rows, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
+    if (er.B < 1 || er.B > VOX_MAX_BATCH || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
+    if (kvt != KV_F32 && (hd != 128 || kvd % 2)) return hipErrorInvalidValue;
+    if (kvt == KV_FP8)
+        hipLaunchKernelGGL(k_rope_kv_rows<kv8_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
+    else if (kvt == KV_F16)
+        hipLaunchKernelGGL(k_rope_kv_rows<kvh_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
+    else
+        hipLaunchKernelGGL(k_rope_kv_rows<float>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
     LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -3606,9 +3615,10 @@ static bool att_planes() {
 }
 
 hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, int cap, float* O, int H, int KVH,
-                            int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs) {
+                            int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs, int kvt) {
     if (N <= 0) return hipSuccess;
     if (er.B < 1 || er.B > VOX_MAX_BATCH || (hd != 64 && hd != 128)) return hipErrorInvalidValue;
+    if (kvt < KV_F32 || kvt > KV_FP8 || (kvt != KV_F32 && hd != 128)) return hipErrorInvalidValue;
     if (xs && N > PLANE_MAX_ROWS) return hipErrorInvalidValue;
     int qbm = 0, keys = 0;
     for (int b = 0; b < er.B; b++) {
@@ -3627,8 +3637,15 @@ hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, in
     }
     dim3 grid(H, qbm, ns * er.B);
     // xs: the output rows as the wo input's planes (by the attention itself, or by the combine)
-    uint16_t* kxs = ns == 1 && att_planes() ? xs : nullptr;
-    if (hd == 64)
+    // (a 16-bit or one-byte ring: planes by k_split_fplanes after the kernel, as launch_attn_rows_mf)
+    uint16_t* kxs = ns == 1 && kvt == KV_F32 && att_planes() ? xs : nullptr;
+    if (kvt == KV_FP8)
+        hipLaunchKernelGGL((k_attn_mf<128, kv8_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
+                           H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, nullptr);
+    else if (kvt == KV_F16)
+        hipLaunchKernelGGL((k_attn_mf<128, kvh_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
+                           H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, nullptr);
+    else if (hd == 64)
         hipLaunchKernelGGL((k_attn_mf<64, float, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O, H * hd,
                            N, H, KVH, 0, 0, window, scale, ns, ws, er, kxs);
     else

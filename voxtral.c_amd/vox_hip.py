@@ -101,7 +101,7 @@ EXPORTS = [
     "vox_hip_batch_begin_rows", "vox_hip_batch_finish",
     "vox_hip_batch_read_logits",
     "vox_hip_batch_stats", "vox_hip_batch_set_gemv_rows", "vox_hip_batch_gemv_stats", "vox_hip_gemv_rows",
-    "vox_hip_batch_set_gemv_wmx4", "vox_hip_batch_gemv_wmx4_stats",
+    "vox_hip_batch_set_gemv_wmx4", "vox_hip_batch_gemv_wmx4_stats", "vox_hip_batch_set_prefill_kv",
     "vox_hip_stream_state", "vox_hip_stream_set_alt", "vox_hip_stream_read_alts", "vox_hip_sgemm_bf16", "vox_hip_sgemm_q8", "vox_hip_fused_qkv_bf16",
     "vox_hip_fused_ffn_bf16", "vox_hip_encoder_attention", "vox_hip_encoder_full_step",
     "vox_hip_decoder_prefill_step", "vox_hip_decoder_start", "vox_hip_decoder_end",
@@ -164,6 +164,7 @@ def lib():
         "vox_hip_gemv_rows": (I, [I, I, P, fp, I, fp, I]),
         "vox_hip_batch_set_gemv_wmx4": (I, [P, I]),
         "vox_hip_batch_gemv_wmx4_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_batch_set_prefill_kv": (I, [P, I]),
         "vox_hip_stream_set_alt": (I, [P, I, F]),
         "vox_hip_stream_read_alts": (I, [P, I, I, ip, fp]),
         "vox_hip_sgemm_bf16": (None, [I, I, I, fp, P, fp]),
@@ -770,6 +771,13 @@ class Batch:
         tensor that has one (on) or the wpack13 planes / raw rows (off); same bits.  0, or -1
         (vox_hip.last_error()) when the model has no wmx4 GEMV plane or inside a begun call."""
         return lib().vox_hip_batch_set_gemv_wmx4(self.h, int(bool(on)))
+
+    def set_prefill_kv(self, on: bool) -> int:
+        """vox_hip_batch_set_prefill_kv: joining streams with half or FP8 decoder KV rings are
+        prefilled in the stacked passes on the batch queue (on, the default) or one by one on
+        their own queues (off); f32 streams ignore it.  0, or -1 (vox_hip.last_error()) inside a
+        begun call."""
+        return lib().vox_hip_batch_set_prefill_kv(self.h, int(bool(on)))
 
     def gemv_wmx4_stats(self) -> tuple:
         """vox_hip_batch_gemv_wmx4_stats: (flag, GEMV step replays on wmx4 planes, step tensors
