@@ -159,10 +159,11 @@ void vh_sched_stats(const vh_sched_t *q, vh_sched_stats_t *out);
  * stream, as vox_stream_feed does. */
 void vh_sched_set_step_cap(vh_sched_t *q, int cap);
 /* The scheduler's batch on the R-row GEMV step (vox_hip_batch_set_gemv_rows: buckets of up to
- * max_rows = 0, 1, 2, 4 or 8 slots) and that step on the wmx4 GEMV planes
- * (vox_hip_batch_set_gemv_wmx4).  Both create the batch if no step has yet; 0, or -1
- * (vh_last_error) where the library call fails. */
+ * max_rows = 0, 1, 2, 4 or 8 slots; vox_hip_batch_set_gemv_rows_q8: the same for a model with
+ * Q8 step tensors) and that step on the wmx4 GEMV planes (vox_hip_batch_set_gemv_wmx4).  Each
+ * creates the batch if no step has yet; 0, or -1 (vh_last_error) where the library call fails. */
 int vh_sched_set_gemv_rows(vh_sched_t *q, int max_rows);
+int vh_sched_set_gemv_rows_q8(vh_sched_t *q, int max_rows);
 int vh_sched_set_gemv_wmx4(vh_sched_t *q, int on);
 
 /* vox_load_wav (voxtral_audio.c:49-166): 16-bit PCM WAV of any channel count and rate, mixed

@@ -384,6 +384,17 @@ int vox_hip_batch_set_prefill_kv(vox_hip_batch_t *b, int on);
  * vox_hip_batch_create (ignored for a Q8 model).  Returns 0; -1 (vox_hip_last_error) for
  * another value, for a Q8 model, or between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
 int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
+/* The same opt-in for a model with Q8 step tensors (int8 rows and one f32 scale per row): the
+ * step's k_gemvr launches stream each Q8 tensor's int8 rows once for the bucket, in the
+ * single-stream Q8 GEMV's order per row -- exact int8 -> f32, f32 FMAs, the row's scale times
+ * the reduced sum before the epilogue -- and a tensor without scales keeps its bf16 / wpack13
+ * launch.  max_rows as above (0 = off, the default); it sets the value that
+ * vox_hip_batch_gemv_stats reports, and the bucket dispatch, graphs and counters are the same.
+ * VOX_HIP_BATCH_GEMV_Q8=<0|1|2|4|8> sets the initial value at vox_hip_batch_create (ignored for
+ * a model with no Q8 step tensor).  Returns 0; -1 (vox_hip_last_error) for another value, for a
+ * model with no Q8 step tensor (vox_hip_batch_set_gemv_rows is its switch), for a model shape
+ * without a kernel instance, or between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+int vox_hip_batch_set_gemv_rows_q8(vox_hip_batch_t *b, int max_rows);
 /* [0] max_rows in effect, [1] step replays on the GEMV path, [2] live rows over those,
  * [3] GEMV step-graph captures.  ([1]..[3] are also counted in vox_hip_batch_stats.) */
 int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
@@ -415,6 +426,12 @@ int vox_hip_batch_set_wmx4(vox_hip_batch_t *b, int on);
  * instance ran, bit 1 the per-row summation order is the single-row GEMV's, bit 2 the wmx4
  * instance ran (clear, and the raw rows streamed, when W is not MXFP4-valued); -1 on error. */
 int vox_hip_gemv_rows(int rows, int K, const uint16_t *W, const float *x, int R, float *y, int packed);
+/* Test entries for Q8 rows (W int8 [rows][K], scales [rows]): y[R][rows] = scale * (W x[r]) for R
+ * in 1..8 rows through k_gemvr's Q8 STORE instance of the bucket >= R (unused rows zero), and
+ * y[rows] for one row through the single-row Q8 GEMV, whose bits every row of the first has.
+ * 0, or -1 (vox_hip_last_error) for a shape without an instance. */
+int vox_hip_gemv_rows_q8(int rows, int K, const int8_t *W, const float *scales, const float *x, int R, float *y);
+int vox_hip_gemv_q8(int rows, int K, const int8_t *W, const float *scales, const float *x, float *y);
 /* Decoder state snapshot: [0]=kv logical length, [1]=next adapter row, [2]=prev token,
  * [3]=started, [4]=eos_seen, [5]=tokens generated. */
 int vox_hip_stream_state(vox_hip_stream_t *s, int *out6);

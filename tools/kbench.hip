@@ -746,6 +746,65 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemvrq8")) {
+        // k_gemvr on Q8 rows (k_gemvr<.., WF_Q8, R>): each full-size projection and
+        // the LM head at R = 1, 2, 4, 8, cold weights (a buffer per layer, read as int8 rows), with
+        // k_gemv<WF_Q8> on the same shape in the same process.  us per launch, bytes streamed once
+        // (a multi-pass instance reads them once per pass: the passes are printed), fraction of
+        // 8 TB/s.  VOX_KB_GEMVR_SHAPES=w2 (or any list of qkv,wo,w13,w2,lm) limits the shapes.
+        struct S { const char* n; int pro, epi, epi1, K, rows; std::vector<uint16_t*>* w; };
+        const char* only = getenv("VOX_KB_GEMVR_SHAPES");
+        CK(hipMemset(state, 0, 16));
+        std::vector<uint16_t*> lm1(1, emb);
+        const int RM = GEMVR_MAX_ROWS;
+        float* xr = (float*)dmalloc((size_t)RM * DH * 4, 1);
+        float* yr = (float*)dmalloc((size_t)RM * V * 4, 0);
+        BatchSlot hs[RM];
+        memset(hs, 0, sizeof hs);
+        for (int s = 0; s < RM; s++) {
+            hs[s].Kc = (char*)(Kc + (size_t)s * 1024 * DKV);
+            hs[s].Vc = (char*)(Vc + (size_t)s * 1024 * DKV);
+            hs[s].live = 1;
+        }
+        BatchSlot* slots = (BatchSlot*)dmalloc(sizeof hs, 0);
+        CK(hipMemcpy(slots, hs, sizeof hs, hipMemcpyHostToDevice));
+        for (S o : {S{"qkv", PRO_NORM, EPI_QKV, EPI_QKV, D, DQ + 2 * DKV, &wqkv}, S{"wo", PRO_NONE, EPI_RESID, EPI_RESID, DQ, D, &wo},
+                    S{"w13", PRO_NORM_ADA, EPI_SWIGLU, EPI_SWIGLU, D, 2 * DH, &w13}, S{"w2", PRO_NONE, EPI_RESID, EPI_RESID, DH, D, &w2},
+                    S{"lm", PRO_NORM, EPI_STORE, EPI_LOGITS, D, V, &lm1}}) {
+            if (only && !strstr(only, o.n)) continue;
+            if (!gemvr_ok_q8(o.pro, o.epi, o.rows, o.K)) { printf("gemvrq8 %s: no Q8 instance\n", o.n); return 1; }
+            const int nl = (int)o.w->size();
+            const int ldy = o.epi == EPI_QKV ? DQ : o.epi == EPI_SWIGLU ? DH : o.rows;
+            const int kq = (o.K / 16 + 255) / 256;
+            auto args = [&](int l) {
+                GemvRArgs a;
+                memset(&a, 0, sizeof a);
+                a.g.x = xr; a.ldx = o.K; a.g.K = o.K; a.g.W = (*o.w)[l]; a.g.wscale = wsc; a.g.rows = o.rows; a.g.norm_w = normw;
+                a.g.ada = ada; a.g.eps = 1e-5f; a.g.y = yr; a.ldy = ldy; a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = HD; a.g.rope = rope;
+                a.g.state = state; a.g.Kc = Kc; a.g.Vc = Vc; a.g.cap = 1024; a.g.part_val = pv; a.g.part_idx = pi;
+                a.slots = slots;
+                return a;
+            };
+            const int it = nl == 1 ? iters / 10 + 1 : iters;
+            const double bytes = (double)o.rows * o.K;
+            char nm[96];
+            snprintf(nm, sizeof nm, "gemvrq8 %-4s k_gemv<Q8>", o.n);
+            const double us1 = timeit([&] { GemvRArgs a = args(layer++ % nl); CK(launch_gemv(o.pro, o.epi1, a.g, st)); }, it, st);
+            printf("%-26s %9.2f us  %6.1f MB  %5.1f %% of 8 TB/s\n", nm, us1, bytes / 1e6, bytes / us1 / 8e6 * 100);
+            for (int R : {1, 2, 4, 8}) {
+                GemvRArgs a0 = args(0);
+                const int occ = gemv_occupancy(gemvr_kernel(o.pro, o.epi, R, a0));
+                int rp = R;
+                while (rp > 1 && rp * kq * 16 > 160) rp /= 2;
+                snprintf(nm, sizeof nm, "gemvrq8 %-4s R = %d", o.n, R);
+                const double us = timeit([&] { GemvRArgs a = args(layer++ % nl); CK(launch_gemvr(o.pro, o.epi, R, a, st)); }, it, st);
+                printf("%-26s %9.2f us  %6.1f MB  %5.1f %% of 8 TB/s  %d pass%s  %d blocks/CU  %.2fx k_gemv\n", nm, us, bytes / 1e6,
+                       bytes / us / 8e6 * 100, R / rp, R / rp > 1 ? "es" : "", occ, us / us1);
+                fflush(stdout);
+            }
+        }
+        return 0;
+    }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemvrmx4")) {
         // k_gemvr on the wmx4 GEMV plane (k_gemvr<.., WF_MX4, R>) beside its wpack13 instance: the
         // five full-size shapes, cold weights (a set of planes per layer), R = 1, 2, 4, 8, the two

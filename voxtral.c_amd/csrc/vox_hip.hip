@@ -2828,6 +2828,51 @@ extern "C" int vox_hip_gemv_rows(int rows, int K, const uint16_t* W, const float
     return rc ? -1 : (ran | 2);
 }
 
+// Test entries for Q8 rows (W int8 [rows][K], one f32 scale per row): y[R][rows] = scale * (W x[r])
+// through k_gemvr's Q8 STORE instance of the bucket >= R (the bucket's unused rows are zero),
+// and its single-row twin through k_gemv<WF_Q8>'s STORE instance.  0, or -1 on error.
+static int gemv_q8_entry(const char* who, int rows, int K, const int8_t* W, const float* scales, const float* x, int R,
+                         float* y, bool rowsk) {
+    std::lock_guard<std::mutex> lk(g_twin_mu);
+    if (!W || !scales || !x || !y) return set_err("%s: null argument", who);
+    if (R < 1 || R > GEMVR_MAX_ROWS) return set_err("%s: %d rows (1..%d)", who, R, GEMVR_MAX_ROWS);
+    if (rowsk ? !gemvr_ok_q8(PRO_NONE, EPI_STORE, rows, K) : !gemv_ok(rows, K, 1))
+        return set_err("%s: no Q8 instance for %d x %d", who, rows, K);
+    if (twin_init()) return -1;
+    int Rb = 1;
+    while (Rb < R) Rb *= 2;
+    uint8_t* dW = nullptr;
+    float *ds = nullptr, *dx = nullptr, *dy = nullptr;
+    auto run = [&]() -> int {
+        CK(dalloc(&dW, (size_t)rows * K));
+        CK(dalloc(&ds, (size_t)rows));
+        CK(dalloc(&dx, (size_t)Rb * K));
+        CK(dalloc(&dy, (size_t)Rb * rows));
+        CK(hipMemset(dx, 0, (size_t)Rb * K * 4));
+        if (upload(dW, W, (size_t)rows * K) || upload(ds, scales, (size_t)rows * 4) || upload(dx, x, (size_t)R * K * 4))
+            return -1;
+        GemvRArgs a;
+        memset(&a, 0, sizeof a);
+        a.g.x = dx; a.ldx = K; a.g.K = K; a.g.W = dW; a.g.wscale = ds; a.g.rows = rows; a.g.y = dy; a.ldy = rows;
+        if (rowsk) CK(launch_gemvr(PRO_NONE, EPI_STORE, Rb, a, g_twin_st));
+        else CK(launch_gemv(PRO_NONE, EPI_STORE, a.g, g_twin_st));
+        CK(hipStreamSynchronize(g_twin_st));
+        CK(hipMemcpy(y, dy, (size_t)R * rows * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    dfree(dW); dfree(ds); dfree(dx); dfree(dy);
+    return rc ? -1 : 0;
+}
+
+extern "C" int vox_hip_gemv_rows_q8(int rows, int K, const int8_t* W, const float* scales, const float* x, int R, float* y) {
+    return gemv_q8_entry("gemv_rows_q8", rows, K, W, scales, x, R, y, true);
+}
+
+extern "C" int vox_hip_gemv_q8(int rows, int K, const int8_t* W, const float* scales, const float* x, float* y) {
+    return gemv_q8_entry("gemv_q8", rows, K, W, scales, x, 1, y, false);
+}
+
 // Test entry: nb rows x [nb][K] against one bf16 matrix W [N][K] through the batched step's own
 // launchers (include/voxtral_hip.h): planes by launch_split_fplanes, then launch_gemm_skl with
 // pair = 1 and its slabs summed in slab order on the host (head = 0), or launch_gemm_skf /
@@ -3229,6 +3274,8 @@ extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
 }
 
 static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows);
+static int batch_set_gemv_rows_q8(vox_hip_batch_t* b, int max_rows);
+static int model_gemv_q8_count(const vox_hip_model_t* m);
 static int batch_set_gemv_wmx4(vox_hip_batch_t* b, int on, bool quiet);
 
 extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_streams) {
@@ -3287,6 +3334,12 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
     if (const char* e = getenv("VOX_HIP_BATCH_GEMV")) {
         const int r = atoi(e);
         if (r && !(m->tok_emb_s || m->dec[0].sqkv) && batch_set_gemv_rows(b, r)) return fail();
+    }
+    // VOX_HIP_BATCH_GEMV_Q8=<0|1|2|4|8>: the same for a model with Q8 step tensors (a model
+    // without one ignores it)
+    if (const char* e = getenv("VOX_HIP_BATCH_GEMV_Q8")) {
+        const int r = atoi(e);
+        if (r && model_gemv_q8_count(m) && batch_set_gemv_rows_q8(b, r)) return fail();
     }
     b->wmx4 = m->fstats[0] ? 1 : 0;
     // VOX_HIP_BATCH_GEMV_WMX4=1: the GEMV step's initial weight source (unset: 0; a model
@@ -3391,8 +3444,9 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
 
 // The same step for a bucket of nb <= 8 slots on the R-row GEMV (k_gemvr): the
 // single-stream step's five launches per layer with every weight byte (bf16 rows, the model's
-// wpack13 planes or, with wmx4 set, the wmx4 GEMV plane of each tensor that has one) read once
-// for the nb rows, and no planes, slabs or tickets.  Between
+// wpack13 planes, with wmx4 set the wmx4 GEMV plane of each tensor that has one, or the int8
+// rows and scales of a Q8 tensor) read once for the nb rows, and no planes, slabs
+// or tickets.  Between
 // the launches the rows live in b->x (residual stream, updated in place), b->q, b->att and
 // b->hid; attention is the slot-table kernel of the single-stream step.  b->x is complete
 // before and after either step, so the two may alternate from one call to the next.
@@ -3420,7 +3474,7 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
         ap.ring_off = (size_t)l * ring_layer;
         // norm -> QKV -> RoPE -> KV append of every live slot
         memset(&a, 0, sizeof a);
-        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.wqkv; a.g.rows = DQ + 2 * DKV;
+        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.wqkv; a.g.wscale = L.sqkv; a.g.rows = DQ + 2 * DKV;
         a.g.norm_w = L.attn_norm; a.g.eps = c.dec_eps; a.g.y = b->q; a.ldy = DQ;
         a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kvt = kvt;
         a.slots = b->slots; a.ring_off = ap.ring_off;
@@ -3430,20 +3484,22 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
         CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         // wo + residual
         memset(&a, 0, sizeof a);
-        a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
+        a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.wscale = L.so; a.g.rows = DD; a.g.y = b->x;
+        a.ldy = DD;
         wpack_args(a.g, L.po);
         mx(a.g, L.mo);
         CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up
         memset(&a, 0, sizeof a);
-        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.w13; a.g.rows = 2 * DH; a.g.norm_w = L.ffn_norm;
-        a.g.ada = m->ada_scale + (size_t)l * DD; a.g.eps = c.dec_eps; a.g.y = b->hid; a.ldy = DH;
+        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.w13; a.g.wscale = L.s13; a.g.rows = 2 * DH;
+        a.g.norm_w = L.ffn_norm; a.g.ada = m->ada_scale + (size_t)l * DD; a.g.eps = c.dec_eps; a.g.y = b->hid; a.ldy = DH;
         wpack_args(a.g, L.p13);
         mx(a.g, L.m13);
         CK(launch_gemvr(PRO_NORM_ADA, EPI_SWIGLU, nb, a, st));
         // W2 + residual
         memset(&a, 0, sizeof a);
-        a.g.x = b->hid; a.ldx = DH; a.g.K = DH; a.g.W = L.w2; a.g.rows = DD; a.g.y = b->x; a.ldy = DD;
+        a.g.x = b->hid; a.ldx = DH; a.g.K = DH; a.g.W = L.w2; a.g.wscale = L.s2; a.g.rows = DD; a.g.y = b->x;
+        a.ldy = DD;
         wpack_args(a.g, L.p2);
         mx(a.g, L.m2);
         CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
@@ -3451,8 +3507,8 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
     // final norm + LM head rows, then the batched step's own end (argmax, alternatives, token
     // log, state, next inputs)
     memset(&a, 0, sizeof a);
-    a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = m->tok_emb; a.g.rows = c.vocab; a.g.norm_w = m->dec_norm;
-    a.g.eps = c.dec_eps; a.g.y = b->logits; a.ldy = c.vocab;
+    a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = m->tok_emb; a.g.wscale = m->tok_emb_s; a.g.rows = c.vocab;
+    a.g.norm_w = m->dec_norm; a.g.eps = c.dec_eps; a.g.y = b->logits; a.ldy = c.vocab;
     wpack_args(a.g, m->plm);
     mx(a.g, m->mlm);
     CK(launch_gemvr(PRO_NORM, EPI_STORE, nb, a, st));
@@ -3507,6 +3563,50 @@ static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
 extern "C" int vox_hip_batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
     if (!b) return set_err("batch_set_gemv_rows: null batch");
     return batch_set_gemv_rows(b, max_rows);
+}
+
+// Q8 step tensors of the model (4 per layer and the LM head: those with a scale vector)
+static int model_gemv_q8_count(const vox_hip_model_t* m) {
+    int n = m->tok_emb_s != nullptr;
+    for (const DecLayerD& L : m->dec) n += (L.sqkv != nullptr) + (L.so != nullptr) + (L.s13 != nullptr) + (L.s2 != nullptr);
+    return n;
+}
+
+// every step tensor has a k_gemvr instance in its own format: the Q8 one where it has scales,
+// the bf16 / wpack13 one otherwise (a checkpoint may quantise only some tensors)
+static bool model_gemvr_ok_q8(const vox_hip_model_t* m) {
+    const vox_hip_config_t& c = m->c;
+    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
+    auto ok = [](const float* s, int pro, int epi, int rows, int K) {
+        return s ? gemvr_ok_q8(pro, epi, rows, K) : gemvr_ok(pro, epi, rows, K);
+    };
+    for (const DecLayerD& L : m->dec)
+        if (!(ok(L.sqkv, PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && ok(L.so, PRO_NONE, EPI_RESID, DD, DQ) &&
+              ok(L.s13, PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && ok(L.s2, PRO_NONE, EPI_RESID, DD, DH)))
+            return false;
+    return ok(m->tok_emb_s, PRO_NORM, EPI_STORE, c.vocab, DD);
+}
+
+// The Q8 model's opt-in of its own: the same gemv_rows field, so the bucket
+// dispatch, graphs and counters are the bf16 mode's
+static int batch_set_gemv_rows_q8(vox_hip_batch_t* b, int max_rows) {
+    if (max_rows != 0 && max_rows != 1 && max_rows != 2 && max_rows != 4 && max_rows != 8)
+        return set_err("batch_set_gemv_rows_q8: max_rows %d is not 0, 1, 2, 4 or 8", max_rows);
+    if (b->call.active) return set_err("batch_set_gemv_rows_q8: a begun call was not finished");
+    const vox_hip_model_t* m = b->m;
+    if (!model_gemv_q8_count(m))
+        return set_err("batch_set_gemv_rows_q8: the model has no Q8 step tensor (vox_hip_batch_set_gemv_rows is its switch)");
+    if (max_rows) {
+        if (!model_gemvr_ok_q8(m)) return set_err("batch_set_gemv_rows_q8: no k_gemvr instance for this model's shapes");
+        if (!b->hid) CK(dalloc(&b->hid, (size_t)GEMVR_MAX_ROWS * m->c.dec_hidden));
+    }
+    b->gemv_rows = max_rows;
+    return 0;
+}
+
+extern "C" int vox_hip_batch_set_gemv_rows_q8(vox_hip_batch_t* b, int max_rows) {
+    if (!b) return set_err("batch_set_gemv_rows_q8: null batch");
+    return batch_set_gemv_rows_q8(b, max_rows);
 }
 
 static int batch_set_gemv_wmx4(vox_hip_batch_t* b, int on, bool quiet) {

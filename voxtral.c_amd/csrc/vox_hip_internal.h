@@ -81,7 +81,7 @@ struct BatchSlot {
 };
 static_assert(sizeof(BatchSlot) == 72, "BatchSlot layout");
 // k_gemvr: k_gemv over R <= 8 input rows (a small batched decode step).  g describes row 0
-// (x, y) and everything the rows share; Q8 weights and biases are not taken.
+// (x, y) and everything the rows share; biases are not taken.
 constexpr int GEMVR_MAX_ROWS = 8;
 struct GemvRArgs {
     GemvArgs g;
@@ -157,6 +157,9 @@ bool gemvr_ok(int pro, int epi, int rows, int K);
 // the same for the wmx4 instances (g.wm_plane set: streamed in preference to the wpack13 planes,
 // in groups of gemv_rowgroup_mx4(rows) = 4 or 8 rows)
 bool gemvr_ok_mx4(int pro, int epi, int rows, int K);
+// the same for the Q8 instances (g.wscale set: int8 rows of K bytes with one f32 scale per row,
+// taken in preference to every plane; K rounds of 256 16-weight chunks, <= 3)
+bool gemvr_ok_q8(int pro, int epi, int rows, int K);
 hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st);
 const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a);
 // part: H * attn_maxch(window) * (hd + 2) floats of partials, then KVH ints (zeroed before

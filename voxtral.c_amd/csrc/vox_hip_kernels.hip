@@ -1173,7 +1173,10 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 // live in registers (R * KQ * 8 floats per thread).  More than 160 floats (R * KQ > 20: W2 of
 // the full model at 8 rows would take 320) do not fit beside the weights: such an instance
 // runs two passes of R / 2 rows over the block's groups and reads its weights twice
-// (DESIGN.md 18.3).
+// (DESIGN.md 18.3).  The Q8 instance (WF_Q8) streams int8 rows as k_gemv<WF_Q8>
+// does: 16 weights per chunk, so R * KQ * 16 floats of x, the same 160-float bound per pass
+// (up to four passes), dot16q per (chunk, row) and the row's f32 scale times the reduced sum
+// in the epilogue owner, before the epilogue.
 //
 // Each row's arithmetic is k_gemv's, in k_gemv's order, in registers of its own: chunks in j
 // order, the wave sum, the four waves added ((0 + 1) + 2) + 3, and the RMSNorm prologue per
@@ -1184,13 +1187,21 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
 // hidden buffer, QKV with RoPE at slots[r].pos, q into row r of y and K/V into the slot's own
 // rings (a slot that is not live appends nothing; its q row is never read).
 // ============================================================================
+// Q8 instance: rows per pass.  A pass holds RP * KQ * 16 floats of x per lane, at most the 160
+// the bf16 instances hold; wider instances run R / RP passes
+constexpr int gemvr_rp_q8(int R, int KQ) {
+    int rp = R;
+    while (rp > 1 && rp * KQ * 16 > 160) rp /= 2;
+    return rp;
+}
+
 template <int PRO, int EPI, int RB, int KQ, int WF, int R>
 __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
-    static_assert(WF == WF_BF16 || WF == WF_P13 || WF == WF_MX4, "k_gemvr streams bf16 rows, wpack13 planes or the wmx4 plane");
-    constexpr bool WP = WF == WF_P13, WM = WF == WF_MX4;
+    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13, WM = WF == WF_MX4;
+    constexpr int XPC = WQ8 ? 4 : 2;  // float4 of x per 16-B chunk
     constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
     constexpr int RW = RB + (RB + 3) / 4;           // wmx4 record dwords per (group, chunk)
-    constexpr int RP = R * KQ > 20 ? R / 2 : R;     // rows per pass
+    constexpr int RP = WQ8 ? gemvr_rp_q8(R, KQ) : R * KQ > 20 ? R / 2 : R;  // rows per pass
     constexpr bool QKVE = EPI == EPI_QKV;
     constexpr bool PAIRED = QKVE || EPI == EPI_SWIGLU;
     constexpr int NL = PAIRED ? RB / 2 : RB;        // epilogue lanes per row
@@ -1199,11 +1210,11 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
     __shared__ float sred[4][RP];
     const GemvArgs& a = ra.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, KC = K >> 3;
+    const int K = a.K, KC = WQ8 ? K >> 4 : K >> 3;
     const int ngroups = a.rows / RB;
     const int G = gridDim.x;
     // wmx4: "rowbytes" is a group's bytes (KC records), the plane ngroups of them (k_gemv)
-    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * 2;
+    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * (WQ8 ? 1 : 2);
     void* const wbase = const_cast<void*>(WM ? a.wm_plane : WP ? a.wp_main : a.W);
     const __amdgpu_buffer_rsrc_t wrs =
         __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
@@ -1237,8 +1248,11 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
         if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
         else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
 
-        float4 xr[RP][KQ][2];
-        float4 nwr[KQ][2], adr[KQ][2];
+        float4 xr[RP][KQ][XPC];
+        // Q8 (16 x values per chunk) fetches the norm and ada rows after the row sums, as
+        // k_gemv<WF_Q8> does: they are not held across the sum's barrier
+        constexpr bool EARLY = !WQ8;
+        float4 nwr[KQ][EARLY ? XPC : 1], adr[KQ][EARLY ? XPC : 1];
         float ss[RP];
 #pragma unroll
         for (int r = 0; r < RP; r++) ss[r] = 0.f;
@@ -1249,26 +1263,28 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int r = 0; r < RP; r++) {
-                const float4* xp = reinterpret_cast<const float4*>(a.x + (size_t)(r0 + r) * ra.ldx) + 2 * cc;
+                const float4* xp = reinterpret_cast<const float4*>(a.x + (size_t)(r0 + r) * ra.ldx) + XPC * cc;
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
+                for (int h = 0; h < XPC; h++) {
                     const float4 xv = xp[h];
                     xr[r][j][h] = c < KC ? xv : z;
                 }
             }
             if (PRO != PRO_NONE) {
                 // the norm weights (and the ada row) are shared by the rows
-                const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + 2 * cc;
-                const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + 2 * cc;
+                const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * cc;
+                const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * cc;
+                if constexpr (EARLY) {
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    nwr[j][h] = wp[h];
-                    if (PRO == PRO_NORM_ADA) adr[j][h] = ap[h];
+                    for (int h = 0; h < XPC; h++) {
+                        nwr[j][h] = wp[h];
+                        if (PRO == PRO_NORM_ADA) adr[j][h] = ap[h];
+                    }
                 }
 #pragma unroll
                 for (int r = 0; r < RP; r++)
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
+                    for (int h = 0; h < XPC; h++) {
                         const float4 v = xr[r][j][h];
                         ss[r] = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss[r]))));
                     }
@@ -1282,25 +1298,60 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
                 if (lane == 0) sred[wave][r] = ss[r];
             }
             __syncthreads();
+            if constexpr (WQ8) {
+                // one fetch of each norm / ada float4 for the RP rows; per element the
+                // arithmetic below is the other branch's
+                float inv[RP];
 #pragma unroll
-            for (int r = 0; r < RP; r++) {
-                const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
-                const float inv = 1.0f / sqrtf(tot / (float)K + a.eps);
+                for (int r = 0; r < RP; r++) {
+                    const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
+                    inv[r] = 1.0f / sqrtf(tot / (float)K + a.eps);
+                }
 #pragma unroll
-                for (int j = 0; j < KQ; j++)
+                for (int j = 0; j < KQ; j++) {
+                    const int c0 = (j * 4 + wave) * 64 + lane;
+                    const int cc = c0 < KC ? c0 : 0;
+                    const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * cc;
+                    const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * cc;
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        float4 v = xr[r][j][h];
-                        const float4 nw = nwr[j][h];
-                        v.x = v.x * inv * nw.x; v.y = v.y * inv * nw.y;
-                        v.z = v.z * inv * nw.z; v.w = v.w * inv * nw.w;
-                        if (PRO == PRO_NORM_ADA) {
-                            const float4 ad = adr[j][h];
-                            v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
-                            v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
+                    for (int h = 0; h < XPC; h++) {
+                        const float4 nw = wp[h];
+                        float4 ad = nw;
+                        if (PRO == PRO_NORM_ADA) ad = ap[h];
+#pragma unroll
+                        for (int r = 0; r < RP; r++) {
+                            float4 v = xr[r][j][h];
+                            v.x = v.x * inv[r] * nw.x; v.y = v.y * inv[r] * nw.y;
+                            v.z = v.z * inv[r] * nw.z; v.w = v.w * inv[r] * nw.w;
+                            if (PRO == PRO_NORM_ADA) {
+                                v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
+                                v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
+                            }
+                            xr[r][j][h] = v;
                         }
-                        xr[r][j][h] = v;
                     }
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < RP; r++) {
+                    const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
+                    const float inv = 1.0f / sqrtf(tot / (float)K + a.eps);
+#pragma unroll
+                    for (int j = 0; j < KQ; j++)
+#pragma unroll
+                        for (int h = 0; h < 2; h++) {
+                            float4 v = xr[r][j][h];
+                            const float4 nw = nwr[j][h];
+                            v.x = v.x * inv * nw.x; v.y = v.y * inv * nw.y;
+                            v.z = v.z * inv * nw.z; v.w = v.w * inv * nw.w;
+                            if (PRO == PRO_NORM_ADA) {
+                                const float4 ad = adr[j][h];
+                                v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
+                                v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
+                            }
+                            xr[r][j][h] = v;
+                        }
+                }
             }
         }
         if (WP) {
@@ -1332,7 +1383,7 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
             const int gcur = g;
             // epilogue inputs of this group (independent of the dot products)
             int er0 = 0, er1 = 0;
-            float ein0 = 0.f, ein1 = 0.f;
+            float ein0 = 0.f, ein1 = 0.f, esc0 = 1.f, esc1 = 1.f;
             if (owner) {
                 int rr[RB];
                 gemv_rows<EPI, RB>(gcur, rr);
@@ -1340,6 +1391,10 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
                 for (int i = 0; i < RB; i++) {
                     if (i == i0) er0 = rr[i];
                     if (i == i0 + 1) er1 = rr[i];
+                }
+                if (WQ8) {
+                    esc0 = a.wscale[er0];
+                    if (PAIRED) esc1 = a.wscale[er1];
                 }
                 if (EPI == EPI_RESID) ein0 = yrow[er0];
                 if (QKVE && er0 < a.qd + a.kvd) {
@@ -1363,6 +1418,10 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
                         const f32x8 wd = dec8m4(mr[j][i], (mr[j][RB + (i >> 2)] >> (8 * (i & 3))) & 0xffu);
 #pragma unroll
                         for (int r = 0; r < RP; r++) acc[r][i] = dot8f(wd, xr[r][j][0], xr[r][j][1], acc[r][i]);
+                    } else if constexpr (WQ8) {
+#pragma unroll
+                        for (int r = 0; r < RP; r++)
+                            acc[r][i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[r][j]), acc[r][i]);
                     } else {
 #pragma unroll
                         for (int r = 0; r < RP; r++) {
@@ -1393,11 +1452,15 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
             }
             __syncthreads();
             if (owner) {
-                const float v0 = ((red[buf][0][orow][i0] + red[buf][1][orow][i0]) + red[buf][2][orow][i0]) + red[buf][3][orow][i0];
+                float v0 = ((red[buf][0][orow][i0] + red[buf][1][orow][i0]) + red[buf][2][orow][i0]) + red[buf][3][orow][i0];
                 float v1 = 0.f;
                 if (PAIRED)
                     v1 = ((red[buf][0][orow][i0 + 1] + red[buf][1][orow][i0 + 1]) + red[buf][2][orow][i0 + 1]) +
                          red[buf][3][orow][i0 + 1];
+                if (WQ8) {  // y = scale * sum before anything else (k_gemv)
+                    v0 *= esc0;
+                    v1 *= esc1;
+                }
                 if (EPI == EPI_STORE || EPI == EPI_RESID) {
                     yrow[er0] = ein0 + v0;
                 } else if (EPI == EPI_SWIGLU) {
@@ -3926,8 +3989,25 @@ static const void* gemvr_fn_kq(int kq, int R) {
 }
 // wf: WF_BF16, WF_P13 or WF_MX4.  The MX4 instances exist for the 4- and 8-row groups of the
 // wmx4 plane (gemv_rb_mx4 of a row count that is a multiple of 4); a 2-row wmx4 plane has none
+// The Q8 instances: the same (PRO, EPI, RB) set with K rounds of 256 16-weight
+// chunks, 1..3 of them (K <= 12,288; gemvr_inst: the third only for wo / W2-like launches)
+template <int P, int E, int RB>
+static const void* gemvr_fn_kq_q8(int kq, int R) {
+    switch (kq) {
+        case 1: return gemvr_fn_r<P, E, RB, 1, WF_Q8>(R);
+        case 2: return gemvr_fn_r<P, E, RB, 2, WF_Q8>(R);
+        case 3: return gemvr_fn_r<P, E, RB, 3, WF_Q8>(R);
+        default: return nullptr;
+    }
+}
 template <int P, int E>
 static const void* gemvr_fn(int rb, int kq, int wf, int R) {
+    if (wf == WF_Q8) {
+        if (rb == 2) return gemvr_fn_kq_q8<P, E, 2>(kq, R);
+        if (rb == 4) return gemvr_fn_kq_q8<P, E, 4>(kq, R);
+        if (rb == 8) return gemvr_fn_kq_q8<P, E, 8>(kq, R);
+        return nullptr;
+    }
     if (wf == WF_MX4) {
         if (rb == 4) return gemvr_fn_kq<P, E, 4, WF_MX4>(kq, R);
         if (rb == 8) return gemvr_fn_kq<P, E, 8, WF_MX4>(kq, R);
@@ -3940,9 +4020,10 @@ static const void* gemvr_fn(int rb, int kq, int wf, int R) {
     return nullptr;
 }
 static const void* gemvr_pick(int pro, int epi, int rows, int K, int wf, int R) {
-    if (!gemv_ok(rows, K, 0)) return nullptr;
+    if (!gemv_ok(rows, K, wf == WF_Q8)) return nullptr;
     if (wf == WF_MX4 && !gemv_ok_mx4(rows, K)) return nullptr;
-    const int rb = wf == WF_MX4 ? gemv_rb_mx4(rows) : gemv_rb(rows), kq = ((K >> 3) + 255) / 256;
+    const int rb = wf == WF_MX4 ? gemv_rb_mx4(rows) : gemv_rb(rows);
+    const int kq = ((wf == WF_Q8 ? K >> 4 : K >> 3) + 255) / 256;
 #define GEMVR_FN(P, E) \
     if (pro == P && epi == E) return gemvr_fn<P, E>(rb, kq, wf, R);
     GEMVR_FN(PRO_NORM, EPI_QKV) GEMVR_FN(PRO_NONE, EPI_RESID) GEMVR_FN(PRO_NORM_ADA, EPI_SWIGLU)
@@ -3953,9 +4034,13 @@ static const void* gemvr_pick(int pro, int epi, int rows, int K, int wf, int R) 
 
 bool gemvr_ok(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_BF16, 1) != nullptr; }
 bool gemvr_ok_mx4(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_MX4, 1) != nullptr; }
+bool gemvr_ok_q8(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_Q8, 1) != nullptr; }
 
-// weight source of a launch, in gemv_k's order: the wmx4 plane, the wpack13 planes, the raw rows
-static int gemvr_wf(const GemvRArgs& a) { return a.g.wm_plane ? WF_MX4 : a.g.wp_main ? WF_P13 : WF_BF16; }
+// weight source of a launch, in gemv_q's order: Q8 rows (wscale), the wmx4 plane, the wpack13
+// planes, the raw rows
+static int gemvr_wf(const GemvRArgs& a) {
+    return a.g.wscale ? WF_Q8 : a.g.wm_plane ? WF_MX4 : a.g.wp_main ? WF_P13 : WF_BF16;
+}
 
 // kernel instance launch_gemvr would use (tools, occupancy queries)
 const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a) {
@@ -3963,13 +4048,13 @@ const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a) {
 }
 
 hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st) {
-    if (a.g.wscale || a.g.bias || (epi == EPI_QKV && !a.slots)) return hipErrorInvalidValue;
+    if (a.g.bias || (epi == EPI_QKV && !a.slots)) return hipErrorInvalidValue;
     const void* fn = gemvr_kernel(pro, epi, R, a);
     if (!fn) return hipErrorInvalidValue;
     GemvRArgs args = a;
     void* kargs[] = {&args};
     // the wmx4 plane has its own group size, hence its own grid (k_gemv's wmx4 launch)
-    const int grid = a.g.wm_plane ? gemv_grid_mx4(a.g.rows) : gemv_grid(a.g.rows);
+    const int grid = gemvr_wf(a) == WF_MX4 ? gemv_grid_mx4(a.g.rows) : gemv_grid(a.g.rows);
     return hipLaunchKernel(fn, dim3(grid), dim3(256), kargs, 0, st);
 }
 

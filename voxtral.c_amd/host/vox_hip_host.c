@@ -1051,6 +1051,13 @@ int vh_sched_set_gemv_rows(vh_sched_t *q, int max_rows) {
     return 0;
 }
 
+int vh_sched_set_gemv_rows_q8(vh_sched_t *q, int max_rows) {
+    if (!q) return fail("sched_set_gemv_rows_q8: null scheduler");
+    if (sched_batch(q)) return -1;
+    if (vox_hip_batch_set_gemv_rows_q8(q->batch, max_rows)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
 int vh_sched_set_gemv_wmx4(vh_sched_t *q, int on) {
     if (!q) return fail("sched_set_gemv_wmx4: null scheduler");
     if (sched_batch(q)) return -1;

@@ -82,6 +82,39 @@ def gemv_rows(W_bf16, x, packed):
     return y, rc
 
 
+def _q8_args(W_i8, scales, x):
+    W = np.ascontiguousarray(W_i8, np.int8)
+    sc = np.ascontiguousarray(scales, np.float32)
+    xv = np.ascontiguousarray(x, np.float32)
+    rows, K = W.shape
+    assert sc.shape == (rows,) and xv.shape[-1] == K
+    return W, sc, xv, rows, K
+
+
+def gemv_rows_q8(W_i8, scales, x):
+    """Test entry: y [R, rows] of y[r] = scales * (W x[r]) for R <= 8 rows through the R-row
+    GEMV's Q8 instance (vox_hip_gemv_rows_q8); W int8 [rows, K], scales f32 [rows]"""
+    init()
+    W, sc, xv, rows, K = _q8_args(W_i8, scales, x)
+    assert xv.ndim == 2
+    R = xv.shape[0]
+    y = np.empty((R, rows), np.float32)
+    if lib().vox_hip_gemv_rows_q8(rows, K, W.ctypes.data, fptr(sc), fptr(xv), R, fptr(y)) < 0:
+        _err("gemv_rows_q8")
+    return y
+
+
+def gemv_q8(W_i8, scales, x):
+    """Test entry: y [rows] = scales * (W x) through the single-row Q8 GEMV (vox_hip_gemv_q8)"""
+    init()
+    W, sc, xv, rows, K = _q8_args(W_i8, scales, x)
+    assert xv.ndim == 1
+    y = np.empty(rows, np.float32)
+    if lib().vox_hip_gemv_q8(rows, K, W.ctypes.data, fptr(sc), fptr(xv), fptr(y)) < 0:
+        _err("gemv_q8")
+    return y
+
+
 # exported symbols, as declared in include/voxtral_hip.h
 EXPORTS = [
     "vox_hip_init", "vox_hip_available", "vox_hip_shutdown", "vox_hip_memory_used",
@@ -102,6 +135,7 @@ EXPORTS = [
     "vox_hip_batch_read_logits",
     "vox_hip_batch_stats", "vox_hip_batch_set_gemv_rows", "vox_hip_batch_gemv_stats", "vox_hip_gemv_rows",
     "vox_hip_batch_set_gemv_wmx4", "vox_hip_batch_gemv_wmx4_stats", "vox_hip_batch_set_prefill_kv",
+    "vox_hip_batch_set_gemv_rows_q8", "vox_hip_gemv_rows_q8", "vox_hip_gemv_q8",
     "vox_hip_stream_state", "vox_hip_stream_set_alt", "vox_hip_stream_read_alts", "vox_hip_sgemm_bf16", "vox_hip_sgemm_q8", "vox_hip_fused_qkv_bf16",
     "vox_hip_fused_ffn_bf16", "vox_hip_encoder_attention", "vox_hip_encoder_full_step",
     "vox_hip_decoder_prefill_step", "vox_hip_decoder_start", "vox_hip_decoder_end",
@@ -165,6 +199,9 @@ def lib():
         "vox_hip_batch_set_gemv_wmx4": (I, [P, I]),
         "vox_hip_batch_gemv_wmx4_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_batch_set_prefill_kv": (I, [P, I]),
+        "vox_hip_batch_set_gemv_rows_q8": (I, [P, I]),
+        "vox_hip_gemv_rows_q8": (I, [I, I, P, fp, fp, I, fp]),
+        "vox_hip_gemv_q8": (I, [I, I, P, fp, fp, fp]),
         "vox_hip_stream_set_alt": (I, [P, I, F]),
         "vox_hip_stream_read_alts": (I, [P, I, I, ip, fp]),
         "vox_hip_sgemm_bf16": (None, [I, I, I, fp, P, fp]),
@@ -759,6 +796,12 @@ class Batch:
         R-row GEMV step.  Returns 0, or -1 with last_error() set (another value, a Q8 model, a
         begun call)."""
         return lib().vox_hip_batch_set_gemv_rows(self.h, int(max_rows))
+
+    def set_gemv_rows_q8(self, max_rows: int) -> int:
+        """vox_hip_batch_set_gemv_rows_q8: the same switch for a model with Q8 step tensors (the
+        step streams their int8 rows).  Returns 0, or -1 with last_error() set (another value, a
+        model with no Q8 step tensor, a begun call)."""
+        return lib().vox_hip_batch_set_gemv_rows_q8(self.h, int(max_rows))
 
     def set_wmx4(self, on: bool) -> int:
         """vox_hip_batch_set_wmx4: the MFMA step streams the wmx4 fragment planes (on) or the bf16
