@@ -113,7 +113,8 @@ vh_ctx_t *vh_ctx_wrap(vox_hip_model_t *model, const vox_hip_config_t *cfg, int d
  * finish as audio arrives, and leave the decoder to vh_sched_run, which
  *   0. encodes the chunk every attached stream deferred since the last run (its feeds leave
  *      the chunk's frames in place) in one vox_hip_stream_encode_mel_batch pass: the encoder
- *      weights are read once for all streams (VOX_HIP_SCHED_BATCH_ENC=0: each chunk alone),
+ *      weights are read once for all streams (VOX_HIP_SCHED_BATCH_ENC=0: each chunk alone);
+ *      more than 32 streams with a chunk go in groups of 32, the library's per-pass limit,
  *   1-2. advances every stream whose decoder can run by batched greedy steps
  *      (vox_hip_batch_decode: one weight read per step for all of them, attention / KV /
  *      argmax per stream): streams whose prompt rows just completed are prefilled together
@@ -132,7 +133,12 @@ vh_ctx_t *vh_ctx_wrap(vox_hip_model_t *model, const vox_hip_config_t *cfg, int d
  * in the batch (the batched argmax keeps their candidates); a live-mode stream drains on its
  * own path inside vh_stream_flush (and so inside vh_stream_finish), where the reference's
  * restart checks run between the flush and the final chunk. */
-#define VH_SCHED_MAX 32
+/* VH_SCHED_MAX = the batch object's VOX_HIP_BATCH_MAX_SLOTS (voxtral_hip.h): up to 32 streams
+ * with rows take the skinny / GEMV batched steps, 33..128 the wide k_gemmf step (one weight read
+ * per step for all of them).  Decoder KV rings at 128 streams: ~225 GB f32, ~113 GB IEEE half,
+ * ~56 GB FP8 of the 288 GB (vh_set_kv_dtype before the streams are created); transcript quality
+ * on FP8 rings and MXFP4 weights remains unevaluated.  vh_sched_create refuses 129. */
+#define VH_SCHED_MAX 128
 typedef struct vh_sched vh_sched_t;
 typedef struct {
     int runs, prefills, batch_calls;

@@ -322,7 +322,16 @@ int vox_hip_stream_set_alt(vox_hip_stream_t *s, int n_alt, float cutoff);
 int vox_hip_stream_read_alts(vox_hip_stream_t *s, int first, int n, int *ids_out, float *probs_out);
 /* Cross-stream batched greedy decoding (C4; the reference decodes each
  * vox_stream_t separately, voxtral.c:1105-1145).  A batch object holds scratch for up to
- * max_streams (<= 32: two 16-row blocks) streams of one model.  vox_hip_batch_decode advances every listed
+ * max_streams (1..VOX_HIP_BATCH_MAX_SLOTS = 128) streams of one model; its slot-indexed buffers
+ * are sized for 32, 64 or 128 rows, whichever first holds max_streams (a batch of <= 32
+ * allocates what it always did).  Calls with up to 32 streams run the skinny MFMA step (two
+ * 16-row blocks; or the opt-in R-row GEMV step); calls with 33..64 and 65..128 streams run the
+ * wide step: the stacked prefill's k_gemmf layers over the bf16 fragment-major copies (the
+ * row-major GEMM where the model has Q8 step tensors), a slot-table decode attention and the LM
+ * head through k_gemmf, with step graphs of their own.  Per-stream decoder KV rings at 128
+ * streams take ~225 GB as f32, ~113 GB as IEEE half and ~56 GB as FP8 of the 288 GB
+ * (vox_hip_model_set_kv_dtype); transcript quality on FP8 rings and MXFP4 weights remains
+ * unevaluated.  vox_hip_batch_decode advances every listed
  * stream that has adapter rows left by one greedy token per step; the weights are streamed
  * once per step for all of them, attention / KV / argmax use each stream's own state.
  * Streams not started yet whose prompt is complete are prefilled first (several of them in
@@ -335,6 +344,7 @@ int vox_hip_stream_read_alts(vox_hip_stream_t *s, int first, int n, int *ids_out
  * Results and device state are those of vox_hip_stream_decode on each stream (up to f32
  * summation order of the shared GEMMs).  tokens_out: [n][max_steps]; counts_out[n].
  * Returns the total number of tokens, < 0 on error. */
+#define VOX_HIP_BATCH_MAX_SLOTS 128
 typedef struct vox_hip_batch vox_hip_batch_t;
 vox_hip_batch_t *vox_hip_batch_create(vox_hip_model_t *m, int max_streams);
 void vox_hip_batch_free(vox_hip_batch_t *b);
@@ -380,11 +390,15 @@ int vox_hip_batch_set_prefill_kv(vox_hip_batch_t *b, int on);
  * Steps whose slot bucket is <= max_rows (0 = off, the default; 1, 2, 4 or 8) take the R-row
  * GEMV path; larger buckets keep the MFMA step.  Tokens, logits (to f32 summation order),
  * alternatives, rings and stream state are those of the MFMA step, and the mode may change
- * between calls.  VOX_HIP_BATCH_GEMV=<0|1|2|4|8> sets the initial value at
- * vox_hip_batch_create (ignored for a Q8 model).  Returns 0; -1 (vox_hip_last_error) for
+ * between calls.  Like vox_hip_batch_set_gemv_rows_q8, vox_hip_batch_set_gemv_wmx4 and
+ * vox_hip_batch_set_wmx4 it acts on calls of <= 32 streams only: the wide step of 33..128
+ * streams always streams the bf16 fragment-major copies (on a wmx4-rounded model they hold the
+ * planes' values, so the tokens are the model's).  VOX_HIP_BATCH_GEMV=<0|1|2|4|8> sets the
+ * initial value at vox_hip_batch_create (ignored for a Q8 model).  Returns 0; -1 (vox_hip_last_error) for
  * another value, for a Q8 model, or between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
 int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
-/* The same opt-in for a model with Q8 step tensors (int8 rows and one f32 scale per row): the
+/* The same opt-in for a model with Q8 step tensors (int8 rows and one f32 scale per row; buckets
+ * <= 8 as above): the
  * step's k_gemvr launches stream each Q8 tensor's int8 rows once for the bucket, in the
  * single-stream Q8 GEMV's order per row -- exact int8 -> f32, f32 FMAs, the row's scale times
  * the reduced sum before the epilogue -- and a tensor without scales keeps its bf16 / wpack13
@@ -398,7 +412,8 @@ int vox_hip_batch_set_gemv_rows_q8(vox_hip_batch_t *b, int max_rows);
 /* [0] max_rows in effect, [1] step replays on the GEMV path, [2] live rows over those,
  * [3] GEMV step-graph captures.  ([1]..[3] are also counted in vox_hip_batch_stats.) */
 int vox_hip_batch_gemv_stats(const vox_hip_batch_t *b, long long *out4);
-/* The R-row GEMV step's weight source (opt-in, on top of wmx4 mode 1 or 2): on = 1 makes the
+/* The R-row GEMV step's weight source (opt-in, on top of wmx4 mode 1 or 2; buckets <= 8, so calls
+ * of <= 32 streams only): on = 1 makes the
  * step stream the wmx4 GEMV plane of every tensor that has one -- the plane the single-stream
  * step reads, 5 bits per weight, no second copy -- through k_gemvr's wmx4 instances, which
  * decode each weight once for the bucket's rows and run the bf16 instance's FMA chains: same
@@ -412,7 +427,7 @@ int vox_hip_batch_set_gemv_wmx4(vox_hip_batch_t *b, int on);
 /* [0] the flag in effect, [1] GEMV step replays that streamed at least one wmx4 plane,
  * [2] tensors of the step (4 per layer and the LM head) with a wmx4 GEMV plane, [3] without. */
 int vox_hip_batch_gemv_wmx4_stats(const vox_hip_batch_t *b, long long out4[4]);
-/* The batched MFMA step's weight source: on = 1 streams the wmx4 fragment plane of every tensor
+/* The batched MFMA step's weight source (calls of <= 32 streams): on = 1 streams the wmx4 fragment plane of every tensor
  * that has one (the bf16 fragment copy of the others), on = 0 the bf16 fragment copies.  Both
  * give the same bits.  A batch created on a model with fragment planes (vox_hip_set_wmx4_batch)
  * starts with it on; otherwise it is off and cannot be turned on.  The two modes keep step

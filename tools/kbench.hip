@@ -1682,6 +1682,34 @@ int main(int argc, char** argv) {
             }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemmfw")) {
+        // k_gemmf at the wide batched step's five shapes, 64 and 128 rows: three planes (64-row
+        // tiles only) and two planes with 64- and 128-row tiles (launch_gemmf's rb)
+        const size_t wsn = 2 * gemmf_ws_floats(gemmf_grid());
+        float* gws = (float*)dmalloc(wsn * 4, 0);
+        int* gfl = (int*)dmalloc(gemmf_flag_ints() * 4, 0);
+        uint16_t* gp = (uint16_t*)dmalloc((size_t)8 * 3 * 16 * 9216 * 2, 1);
+        uint16_t* go = (uint16_t*)dmalloc((size_t)8 * 3 * 16 * 9216 * 2, 0);
+        float* gc = (float*)dmalloc((size_t)128 * V * 4, 0);
+        int epoch = 0;
+        // a different layer's tensor per launch, as the step reads them (the LM head is one 805 MB tensor)
+        struct G { const char* n; int epi, N, K; uint16_t* const* W; };
+        uint16_t* const lm1[1] = {emb};
+        for (int M : {64, 128})
+            for (G g : {G{"dqkv", EPI_STORE, DQ + 2 * DKV, D, wqkv.data()}, G{"dwo", EPI_RESID, D, DQ, wo.data()},
+                        G{"dw13", EPI_SWIGLU, 2 * DH, D, w13.data()}, G{"dw2", EPI_RESID, D, DH, w2.data()},
+                        G{"lm", EPI_STORE, V, D, lm1}})
+                for (int cfg = 0; cfg < 3; cfg++) {
+                    const int np = cfg == 0 ? 3 : 2, rb = cfg == 0 ? 0 : cfg == 1 ? 4 : 8;
+                    double us = timeit([&] { CK(launch_gemmf(g.epi, np, gp, g.K, M, g.W[g.W == lm1 ? 0 : layer++ % NL], g.N, nullptr, gc,
+                                                             g.epi == EPI_SWIGLU ? g.N / 2 : g.N, g.epi == EPI_SWIGLU ? go : nullptr, gws, wsn, gfl,
+                                                             ++epoch, st, nullptr, rb)); }, 26, st);
+                    printf("gemmfw %-4s M=%3d %6dx%-4d planes %d tile rows %3d %9.2f us  %7.1f GB/s weights\n", g.n, M, g.N, g.K, np,
+                           np == 3 ? 64 : 16 * rb, us, 2.0 * g.N * g.K / us / 1e3);
+                    fflush(stdout);
+                }
+        return 0;
+    }
     if (only_gemmf) return 0;
     {
         // batched decode GEMMs (16 streams, fragment-major weights and planes); weights are

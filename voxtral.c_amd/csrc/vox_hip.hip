@@ -3143,6 +3143,10 @@ extern "C" int vox_hip_device_free(void* dev) {
 struct vox_hip_batch {
     vox_hip_model_t* m;
     int cap;
+    // rows of the slot-indexed buffers (slot table, token log, x, q, att, logits, pval / pidx /
+    // palt, attention partials): the capacity's bucket, 32 (cap <= 32), 64 or 128.  The skinny
+    // step's own buffers (part, planes xp_*) hold VOX_MAX_BATCH rows at any capacity.
+    int rows;
     hipStream_t st;
     float *x, *q, *att, *logits, *pval, *palt;
     float* part;     // split-K slabs of the current projection (k_skl), consumed by the next kernel
@@ -3152,7 +3156,7 @@ struct vox_hip_batch {
     uint16_t *xp_d, *xp_q, *xp_h;  // skinny-GEMM inputs: [3][16][K] bf16 planes of the rows (fragment order)
     float* apart;    // decode-attention partials + arrival counters, apart_n floats per slot
     size_t apart_n;
-    // the slot table (VOX_MAX_BATCH BatchSlot) followed by the token log [VOX_MAX_BATCH][BATCH_TOKLOG],
+    // the slot table (rows BatchSlot) followed by the token log [rows][BATCH_TOKLOG],
     // in device memory and mirrored in pinned host memory (one copy each way per step chunk)
     BatchSlot* slots;
     BatchSlot* hslots;
@@ -3181,9 +3185,19 @@ struct vox_hip_batch {
     // streams prefill one by one on their own queues, vox_hip_batch_set_prefill_kv)
     int prefill_kv;
     // rows of the last call (b->logits row i = stream luid[i], from its last step when llive[i])
-    unsigned long long luid[VOX_MAX_BATCH];
-    int llive[VOX_MAX_BATCH];
+    unsigned long long luid[VOX_MAX_SLOTS];
+    int llive[VOX_MAX_SLOTS];
     int lnb;
+    // the wide step (batch_step_wide: slot buckets 64 and 128, rows > VOX_MAX_BATCH only): QKV
+    // rows, k_gemmf input planes [row block][3][16][K] (wpa: dec_dim / heads*head_dim columns,
+    // wpc: dec_hidden), the row-major fallback's normalised and SwiGLU rows, hand-off flags of
+    // its own and the device epoch word its captured k_gemmf launches add to their epochs;
+    // graphs [ring element type][bucket 64, 128][attention splits bucket]
+    float *wqkv, *wxn, *whid;
+    uint16_t *wpa, *wpc;
+    int* wflags;
+    int* wepoch;
+    hipGraphExec_t gwexec[3][2][STEP_GRAPHS];
     long long n_calls, n_replays, n_rows, n_captures, n_prefill_passes, n_prefilled;
     // split-K workspace of the stacked prefills (not the lead stream's: with an encoder pass
     // running beside the batched steps, that stream's queue may be using its own), and the
@@ -3196,14 +3210,15 @@ struct vox_hip_batch {
     struct {
         int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kvt, done, k;
         int gemv;  // the call's steps take the GEMV path
-        vox_hip_stream_t* streams[VOX_MAX_BATCH];
+        vox_hip_stream_t* streams[VOX_MAX_SLOTS];
         int* tokens_out;
         int* counts_out;
     } call;
 };
 
-static int* slot_toklog(BatchSlot* slots) { return reinterpret_cast<int*>(slots + VOX_MAX_BATCH); }
-static const size_t SLOT_BYTES = sizeof(BatchSlot) * VOX_MAX_BATCH + sizeof(int) * VOX_MAX_BATCH * BATCH_TOKLOG;
+static_assert(VOX_MAX_SLOTS == VOX_HIP_BATCH_MAX_SLOTS, "the public bound of vox_hip_batch_create");
+static int* slot_toklog(BatchSlot* slots, int rows) { return reinterpret_cast<int*>(slots + rows); }
+static size_t slot_bytes(int rows) { return (sizeof(BatchSlot) + sizeof(int) * BATCH_TOKLOG) * (size_t)rows; }
 
 // pack one [N, K] matrix (bf16, or int8 when q8) into fragment order (k_frag_pack)
 static int frag_copy(uint8_t** dst, const uint8_t* src, int N, int K, int q8) {
@@ -3258,6 +3273,13 @@ static void batch_drop_graphs(vox_hip_batch_t* b) {
                     hipGraphExecDestroy(e);
                     e = nullptr;
                 }
+    for (auto& k : b->gwexec)
+        for (auto& g : k)
+            for (auto& e : g)
+                if (e) {
+                    hipGraphExecDestroy(e);
+                    e = nullptr;
+                }
 }
 
 extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
@@ -3266,6 +3288,7 @@ extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
     dfree(b->x); dfree(b->part); dfree(b->ssq); dfree(b->ticket); dfree(b->q); dfree(b->att);
     dfree(b->logits); dfree(b->pval); dfree(b->pidx); dfree(b->palt); dfree(b->apart);
     dfree(b->xp_d); dfree(b->xp_q); dfree(b->xp_h); dfree(b->pgws); dfree(b->gflags); dfree(b->hid);
+    dfree(b->wqkv); dfree(b->wxn); dfree(b->whid); dfree(b->wpa); dfree(b->wpc); dfree(b->wflags); dfree(b->wepoch);
     if (b->slots) hipFree(b->slots);
     if (b->hslots) hipHostFree(b->hslots);
     batch_drop_graphs(b);
@@ -3279,8 +3302,8 @@ static int model_gemv_q8_count(const vox_hip_model_t* m);
 static int batch_set_gemv_wmx4(vox_hip_batch_t* b, int on, bool quiet);
 
 extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_streams) {
-    if (!m || max_streams < 1 || max_streams > VOX_MAX_BATCH) {
-        set_err("batch size must be 1..%d", VOX_MAX_BATCH);
+    if (!m || max_streams < 1 || max_streams > VOX_MAX_SLOTS) {
+        set_err("batch size must be 1..%d", VOX_MAX_SLOTS);
         return nullptr;
     }
     const vox_hip_config_t& c = m->c;
@@ -3293,8 +3316,10 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
     memset((void*)b, 0, sizeof *b);
     b->m = m;
     b->cap = max_streams;
+    b->rows = max_streams <= VOX_MAX_BATCH ? VOX_MAX_BATCH : max_streams <= 64 ? 64 : VOX_MAX_SLOTS;
     const size_t D = c.dec_dim, QKV = c.dec_heads * c.dec_head_dim + 2 * c.dec_kv_heads * c.dec_head_dim;
-    const size_t S = VOX_MAX_BATCH;  // rows of the slot-indexed buffers (graphs of any bucket)
+    const size_t S = b->rows;         // rows of the slot-indexed buffers (graphs of any bucket)
+    const size_t SK = VOX_MAX_BATCH;  // rows of the skinny step's slabs and planes
     auto fail = [&]() -> vox_hip_batch_t* { vox_hip_batch_free(b); return nullptr; };
 #define TRYH(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_err("%s: %s", #x, hipGetErrorString(e__)); return fail(); } } while (0)
     TRYH(queue_high_priority(&b->st));
@@ -3307,7 +3332,7 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
             set_err("batched decode needs dec_dim, heads*head_dim and dec_hidden divisible by 256");
             return fail();
         }
-        TRYH(dalloc(&b->part, (size_t)S * n));  // [row block][split][16][N] for the S slot rows
+        TRYH(dalloc(&b->part, (size_t)SK * n));  // [row block][split][16][N] for the skinny step's rows
     }
     TRYH(dalloc(&b->ssq, (size_t)SK_ROWS * SKX_TICKETS));  // [slices][16], any slice count
     TRYH(dalloc(&b->ticket, (size_t)SKX_TICKETS));
@@ -3320,14 +3345,27 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
     // attention partials + one arrival count per kv head (zeroed; reset by the merging block)
     b->apart_n = (size_t)c.dec_heads * attn_maxch(c.dec_window) * (c.dec_head_dim + 2) + c.dec_kv_heads;
     TRYH(dalloc(&b->apart, S * b->apart_n));
-    TRYH(hipMalloc((void**)&b->slots, SLOT_BYTES));
-    TRYH(hipMemset(b->slots, 0, SLOT_BYTES));
-    TRYH(hipHostMalloc((void**)&b->hslots, SLOT_BYTES, hipHostMallocDefault));
-    memset((void*)b->hslots, 0, SLOT_BYTES);
+    TRYH(hipMalloc((void**)&b->slots, slot_bytes(b->rows)));
+    TRYH(hipMemset(b->slots, 0, slot_bytes(b->rows)));
+    TRYH(hipHostMalloc((void**)&b->hslots, slot_bytes(b->rows), hipHostMallocDefault));
+    memset((void*)b->hslots, 0, slot_bytes(b->rows));
     if (model_frag(m)) return fail();
-    TRYH(dalloc(&b->xp_d, (size_t)3 * S * D));  // [row block][3][16][K]
-    TRYH(dalloc(&b->xp_q, (size_t)3 * S * c.dec_heads * c.dec_head_dim));
-    TRYH(dalloc(&b->xp_h, (size_t)3 * S * c.dec_hidden));
+    TRYH(dalloc(&b->xp_d, (size_t)3 * SK * D));  // [row block][3][16][K]
+    TRYH(dalloc(&b->xp_q, (size_t)3 * SK * c.dec_heads * c.dec_head_dim));
+    TRYH(dalloc(&b->xp_h, (size_t)3 * SK * c.dec_hidden));
+    if (b->rows > VOX_MAX_BATCH) {
+        // the wide step's own rows, planes (whole 128-row tiles: k_gemmf reads every row block
+        // of a tile), split workspace, flags and epoch word
+        const size_t DQ = (size_t)c.dec_heads * c.dec_head_dim, R = VOX_MAX_SLOTS;
+        TRYH(dalloc(&b->wqkv, S * QKV));
+        TRYH(dalloc(&b->wxn, S * D));
+        TRYH(dalloc(&b->whid, S * c.dec_hidden));
+        TRYH(dalloc(&b->wpa, R * 3 * std::max(D, DQ)));
+        TRYH(dalloc(&b->wpc, R * 3 * c.dec_hidden));
+        TRYH(dalloc(&b->wflags, gemmf_flag_ints()));
+        TRYH(dalloc(&b->wepoch, (size_t)1));
+        TRYH(dalloc(&b->pgws, GEMM_WS_ELEMS));
+    }
 #undef TRYH
     // VOX_HIP_BATCH_GEMV=<0|1|2|4|8>: the initial max_rows of the R-row GEMV step (unset: 0;
     // a Q8 model keeps 0)
@@ -3437,7 +3475,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
         for (int r0 = 0; r0 < nb; r0 += SK_ROWS)
             CK(launch_gemm_skf(b->xp_d + (size_t)r0 * 3 * DD, DD, lmw, m->tok_emb_s, c.vocab,
                                std::min(SK_ROWS, nb - r0), b->logits + (size_t)r0 * c.vocab, c.vocab, st, mlm != nullptr));
-    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots),
+    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots, b->rows),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
 }
@@ -3512,7 +3550,7 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
     wpack_args(a.g, m->plm);
     mx(a.g, m->mlm);
     CK(launch_gemvr(PRO_NORM, EPI_STORE, nb, a, st));
-    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots),
+    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots, b->rows),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
 }
@@ -3664,7 +3702,85 @@ extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out
     return 0;
 }
 
-// slot bucket of n streams: 1, 2, 4, 8, 16 or 32 slots (graph g of the bucket)
+// The step for a bucket of 64 or 128 slots: the stacked prefill's arithmetic
+// (dec_layers_gemmf, or batch_prefill's launch_gemm layers where dec_gemmf_ok is false) on the
+// batch's own planes and scratch, with the slot-table decode attention in place of the prefill's
+// causal one.  Every weight byte is read once per step for the nb rows: the layers stream the
+// bf16 fragment-major copies (on a wmx4-rounded model they hold the planes' values), the
+// fallback the row-major tensors.  Rows are complete in b->x before and after, as in the other
+// two steps, so a batch moves between buckets from one call to the next.
+// k_gemmf's hand-off epochs are i + *b->wepoch for the step's i-th launch; the step's last
+// kernel advances the word past them, so the launches may be captured and replayed.
+static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
+    vox_hip_model_t* m = b->m;
+    const vox_hip_config_t& c = m->c;
+    const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
+    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden, QKV = DQ + 2 * DKV;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int cap = c.dec_window + DEC_SLACK;
+    const size_t ring_layer = (size_t)cap * DKV * kv_esize(kvt);
+    hipStream_t st = b->st;
+    const int np = gemm_planes_np();
+    const bool gf = dec_gemmf_ok(m, nb);
+    const bool lm_gf = !m->tok_emb_s && enc_gemmf_env() && dec_gemmf_env() && gemmf_ok(nb, c.vocab, DD);
+    int launches = 0;
+    auto gemmf_w = [&](int epi, const uint16_t* xs, int K, const uint8_t* W, int N, float* C, int ldc, uint16_t* xo) -> int {
+        CK(launch_gemmf(epi, np, xs, K, nb, W, N, nullptr, C, ldc, xo, b->pgws, GEMM_WS_ELEMS, b->wflags, ++launches, st,
+                        b->wepoch, gemmf_wide_rb(nb, N, K)));
+        return 0;
+    };
+    AttnSlots ap;
+    ap.q = nullptr; ap.q_ld = 0;
+    ap.part = b->apart; ap.part_ld = b->apart_n;
+    ap.out = gf ? nullptr : b->att; ap.out_ld = DQ;
+    ap.slots = b->slots;
+    AttnFuse af;
+    af.qkv = b->wqkv; af.S = 1; af.N = QKV; af.rope = m->rope_dec; af.xs = b->wpa;
+    for (int l = 0; l < c.dec_layers; l++) {
+        const DecLayerD& L = m->dec[l];
+        ap.ring_off = (size_t)l * ring_layer;
+        // RMSNorm, QKV rows (decoder.c:509-530)
+        if (gf) {
+            CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.attn_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
+            if (gemmf_w(EPI_STORE, b->wpa, DD, m->dfrag[l].wqkv, QKV, b->wqkv, QKV, nullptr)) return -1;
+        } else {
+            CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.attn_norm, nullptr, nb, DD, c.dec_eps, st));
+            CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, L.wqkv, L.sqkv, DD, nb, QKV, nullptr, b->wqkv, QKV, st, b->pgws, GEMM_WS_ELEMS));
+        }
+        // RoPE + K/V append at each live slot's own position + attention over its ring, the rows
+        // as the wo planes (and, for the fallback, as f32 rows in b->att)
+        CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
+        if (gf) {
+            const DecFragD& F = m->dfrag[l];
+            if (gemmf_w(EPI_RESID, b->wpa, DQ, F.wo, DD, b->x, DD, nullptr)) return -1;
+            CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, c.dec_eps, b->wpa, nullptr, 0, st));
+            if (gemmf_w(EPI_SWIGLU, b->wpa, DD, F.w13, 2 * DH, nullptr, DH, b->wpc)) return -1;
+            if (gemmf_w(EPI_RESID, b->wpc, DH, F.w2, DD, b->x, DD, nullptr)) return -1;
+        } else {
+            CK(launch_gemm(EPI_RESID, 3, b->att, DQ, L.wo, L.so, DQ, nb, DD, nullptr, b->x, DD, st, b->pgws, GEMM_WS_ELEMS));
+            CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, nb, DD, c.dec_eps, st));
+            CK(launch_gemm(EPI_SWIGLU, 3, b->wxn, DD, L.w13, L.s13, DD, nb, 2 * DH, nullptr, b->whid, DH, st, b->pgws, GEMM_WS_ELEMS));
+            CK(launch_gemm(EPI_RESID, 3, b->whid, DH, L.w2, L.s2, DH, nb, DD, nullptr, b->x, DD, st, b->pgws, GEMM_WS_ELEMS));
+        }
+    }
+    // final norm + LM head (tied embeddings) into b->logits, then the per-slot argmax, state,
+    // token log and next inputs (decoder.c:762-779)
+    if (lm_gf) {
+        CK(launch_rmsnorm_fplanes(b->x, nb, DD, m->dec_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
+        if (gemmf_w(EPI_STORE, b->wpa, DD, m->lm_frag, c.vocab, b->logits, c.vocab, nullptr)) return -1;
+    } else {
+        CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, m->dec_norm, nullptr, nb, DD, c.dec_eps, st));
+        CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, m->tok_emb, m->tok_emb_s, DD, nb, c.vocab, nullptr, b->logits, c.vocab, st,
+                       b->pgws, GEMM_WS_ELEMS));
+    }
+    CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots, b->rows),
+                           m->tok_emb, m->tok_emb_s, DD, b->x, st));
+    if (launches) CK(launch_gemmf_epoch_bump(b->wepoch, launches + 1, st));
+    return 0;
+}
+
+// slot bucket of n streams: 1, 2, 4, 8, 16 or 32 slots (graph g of the bucket); past 32 the wide
+// step's 64 or 128 (g = 6, 7)
 static int slot_bucket(int n, int* g) {
     int k = 0;
     while ((1 << k) < n) k++;
@@ -3677,7 +3793,11 @@ static int slot_bucket(int n, int* g) {
 static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
     const int gwmx4 = b->gemv_wmx4;  // likewise (vox_hip_batch_set_gemv_wmx4: on only with a plane to stream)
-    auto step = [&]() { return gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4); };
+    const bool wide = nb > VOX_MAX_BATCH;  // buckets 64 and 128 (gemv == 0 there)
+    auto step = [&]() {
+        return wide ? batch_step_wide(b, nb, splits, kvt)
+               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4);
+    };
     if (gemv) b->n_gemv_replays += steps;
     if (gemv && gwmx4) b->n_gemv_wmx4_replays += steps;
     if (!use_graphs()) {
@@ -3690,7 +3810,8 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
+    hipGraphExec_t& ge = wide ? b->gwexec[kvt][gb - 6][gi]
+                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
@@ -3834,7 +3955,7 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
 // the remaining chunks and fills the outputs.  batch_decode = both.
 static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, const int* rows, int max_steps,
                        int stop_at_eos, int* tokens_out, int* counts_out) {
-    if (!b || n < 1 || n > b->cap || max_steps < 0) return set_err("bad batch arguments");
+    if (!b || n < 1 || n > b->cap || n > VOX_MAX_SLOTS || max_steps < 0) return set_err("bad batch arguments");
     if (b->call.active) return set_err("batch: a begun call was not finished");
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
@@ -3853,7 +3974,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     // every member's queue is idle before the batch queue touches its buffers (adapter rows
     // of an async encoder pass, a realloc'ed adapter buffer) -- unless the caller bounded the
     // rows each stream may read
-    int avail[VOX_MAX_BATCH];
+    int avail[VOX_MAX_SLOTS];
     for (int i = 0; i < n; i++) {
         if (rows) {
             if (rows[i] < 0 || rows[i] > streams[i]->total_adapter) return set_err("batch rows[%d] out of range", i);
@@ -3867,7 +3988,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     // 1. streams whose prompt is complete and whose decoder has not started: their prefills
     //    in one stacked pass; they take their first token in the batched steps below
     {
-        vox_hip_stream_t* pre[VOX_MAX_BATCH];
+        vox_hip_stream_t* pre[VOX_MAX_SLOTS];
         int np = 0;
         for (int i = 0; i < n; i++) {
             vox_hip_stream_t* s = streams[i];
@@ -3921,7 +4042,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     // buckets of up to gemv_rows slots take the R-row GEMV step (vox_hip_batch_set_gemv_rows)
     const int gemv = b->gemv_rows && nb <= b->gemv_rows;
     if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv)) return -1;
-    CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
+    CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     auto& cl = b->call;
     cl.active = 1;
     cl.gemv = gemv;
@@ -3957,8 +4078,8 @@ static int batch_finish(vox_hip_batch_t* b) {
         return 0;
     }
     BatchSlot* hs = b->hslots;
-    int* htok = slot_toklog(hs);
-    int got[VOX_MAX_BATCH] = {0};
+    int* htok = slot_toklog(hs, b->rows);
+    int got[VOX_MAX_SLOTS] = {0};
     int done = 0, k = cl.k;
     for (;;) {
         // the chunk of k steps in flight (its slot table + token log copy queued behind it)
@@ -3974,7 +4095,7 @@ static int batch_finish(vox_hip_batch_t* b) {
         if (!any || done >= K) break;
         k = std::min(STEP_BATCH, K - done);
         if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv)) return -1;
-        CK(hipMemcpyAsync(hs, b->slots, SLOT_BYTES, hipMemcpyDeviceToHost, b->st));
+        CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     }
     // 4. host mirrors
     int total = 0;

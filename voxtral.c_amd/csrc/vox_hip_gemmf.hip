@@ -29,8 +29,10 @@
 // wait that times out (another kernel holding the CUs the publishing block needs) makes the
 // owner compute that stage range itself: the same code and summation order, the same bits
 // (tests/test_gpu_gemm_planes.py forces it); a device counter records each such recompute.
-// The epoch must be new for every launch, so a launch is never captured into a graph (the
-// engine refuses it while its stream is capturing).
+// The epoch must be new for every launch.  A launch with a host epoch alone is therefore never
+// captured into a graph (the engine refuses it while its stream is capturing); a captured one
+// adds a device word to its epoch (GemmfArgs::epoch_dev) that the graph's last kernel advances
+// past every epoch of the step (k_gemmf_epoch_bump), so each replay hands off under new epochs.
 #include "vox_hip_internal.h"
 #include "vox_hip_dev.h"
 
@@ -71,6 +73,7 @@ struct GemmfArgs {
     int* recomputes;     // count of stage ranges an owner computed itself (wait timed out)
     int wait_ticks;      // owner's bounded wait per partial (< 0: never wait, always recompute)
     int epoch;
+    const int* epoch_dev;  // null, or a device word added to epoch (captured launches: a new epoch per replay)
     int S, NT, T;        // K stages, column tiles, tiles
     long long U;         // T * S work units
     int MT;              // row tiles
@@ -287,6 +290,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wc = wave & 3, r0 = (wave >> 2) * RBW;
     const int G = gridDim.x, b = blockIdx.x;
+    const int epoch = a.epoch_dev ? a.epoch + *a.epoch_dev : a.epoch;  // uniform: a scalar load
     const long long u0 = gf_bound(a.U, G, b), u1 = gf_bound(a.U, G, b + 1);
     constexpr int TILE = C::NWV * RBW * NG * 256;  // floats of one partial tile (waves x RBW x NG x 64 lanes x 4)
     const int rbm = (a.M + 15) >> 4;                // row blocks holding rows
@@ -317,7 +321,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][g]), Ws, poff(b, i, g), 0, 16);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (tid == 0) __hip_atomic_store(&a.flags[b], a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) __hip_atomic_store(&a.flags[b], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
         }
         // stage 0 is ours: add the later parts in block order, then the epilogue.  The lanes of
@@ -333,7 +337,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
                 bool ok = !mine;
                 const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
                 while (a.wait_ticks >= 0) {
-                    if (!ok) ok = __hip_atomic_load(&a.flags[b + 1 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.epoch;
+                    if (!ok) ok = __hip_atomic_load(&a.flags[b + 1 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
                     if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
                     if (__builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)a.wait_ticks) break;
                     __builtin_amdgcn_s_sleep(2);
@@ -440,11 +444,32 @@ int set_gemmf_wait(int ticks) {
     return old;
 }
 
+// *w += by, back to 1 before a step's epochs could pass INT_MAX (the flags then hold larger
+// values than any epoch of the next ~2^30 launches, so none matches by accident)
+__global__ void k_gemmf_epoch_bump(int* w, int by) {
+    const int v = *w;
+    *w = v > (1 << 30) ? 1 : v + by;
+}
+
+hipError_t launch_gemmf_epoch_bump(int* epoch_dev, int by, hipStream_t st) {
+    if (!epoch_dev || by < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gemmf_epoch_bump, dim3(1), dim3(1), 0, st, epoch_dev, by);
+    return hipGetLastError();
+}
+
+// Two planes at M = 64 / 128 (the wide batched step), from tools/kbench VOX_KB_ONLY=gemmfw
+// (profiles/batch_wide_kbench.txt): 64-row tiles on every projection shape at both row counts
+// (17-29 us against 25-38 with 128-row tiles; W1|W3 at 128 rows equal), and on the LM head at 64
+// rows (168 against 202 us: a 128-row tile would be half padding); 128-row tiles only where 65+
+// rows meet an output wide enough to give every CU a tile of its own (the LM head at 128 rows:
+// 219 against 252 us).  Three planes always take 64-row tiles (launch_gemmf).
+int gemmf_wide_rb(int M, int N, int) { return (M > 64 && N / 128 >= gemmf_grid()) ? 8 : 4; }
+
 bool gemmf_ok(int M, int N, int K) { return M > 0 && M <= 1024 && K % 64 == 0 && N % 128 == 0; }
 
 hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const void* Wf, int N, const float* bias,
                         float* C, int ldc, uint16_t* xo, float* ws, size_t ws_floats, int* flags, int epoch,
-                        hipStream_t st) {
+                        hipStream_t st, const int* epoch_dev, int rb) {
     // tiles: 128 x 128 with two planes; 64 x 128 with three (a 3-slot ring of 8 row blocks'
     // three planes would not fit the 160 KB of LDS); 16 waves with two planes (g_gemmf_wr),
     // 8 with three
@@ -456,7 +481,8 @@ hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const
         const int v = e ? atoi(e) : 0;
         g_gemmf_rb = (v == 4 || v == 8) ? v : 0;
     }
-    if (!gemmf_ok(M, N, K) || (np != 2 && np != 3) || !ws || !flags || (g_gemmf_rb && g_gemmf_rb != 4 && g_gemmf_rb != 8))
+    if (!gemmf_ok(M, N, K) || (np != 2 && np != 3) || !ws || !flags || (g_gemmf_rb && g_gemmf_rb != 4 && g_gemmf_rb != 8) ||
+        (rb && rb != 4 && rb != 8))
         return hipErrorInvalidValue;
     // two planes: 128-row tiles while they alone give every CU a tile; narrower outputs (the
     // N = 1280 wo / W2 passes: 10 column tiles) take 64-row tiles -- a stream-K tile split over
@@ -465,10 +491,10 @@ hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const
     // encoder shape: DESIGN.md 14.2, profiles/r4_kbench_gemmf*.txt)
     const int NGx = NG;
     const int t8 = ((M + 127) / 128) * (N / (64 * NG));
-    const int RB = np == 3 ? 4 : g_gemmf_rb ? g_gemmf_rb : (t8 >= gemmf_grid() ? 8 : 4);
+    const int RB = np == 3 ? 4 : g_gemmf_rb ? g_gemmf_rb : rb ? rb : (t8 >= gemmf_grid() ? 8 : 4);
     GemmfArgs a;
     a.xs = xs; a.K = K; a.M = M; a.W = static_cast<const uint8_t*>(Wf); a.N = N; a.bias = bias; a.C = C; a.ldc = ldc;
-    a.xo = xo; a.ws = ws; a.flags = flags; a.epoch = epoch;
+    a.xo = xo; a.ws = ws; a.flags = flags; a.epoch = epoch; a.epoch_dev = epoch_dev;
     a.recomputes = flags + gemmf_grid();  // the counter past the flags (gemmf_flag_ints())
     a.wait_ticks = g_gemmf_wait;
     a.S = K / 64;

@@ -58,7 +58,9 @@ struct GemvArgs {
 enum { KV_F32 = 0, KV_F16 = 1, KV_FP8 = 2 };
 static inline size_t kv_esize(int kvt) { return kvt == KV_FP8 ? 1 : kvt == KV_F16 ? 2 : 4; }
 
-constexpr int VOX_MAX_BATCH = 32;    // streams per batched decode step (two 16-row blocks of the MFMA B operand)
+constexpr int VOX_MAX_BATCH = 32;    // streams per skinny batched decode step (two 16-row blocks of the MFMA B
+                                     // operand), per batched encoder pass (EncRows) and per vox_hip_skinny_wmx4 call
+constexpr int VOX_MAX_SLOTS = 128;   // slots of a batch object: buckets 64 and 128 take the k_gemmf step (batch_step_wide)
 
 // One row of a batched decode step, in device memory (the batch's slot table).  The step
 // graph's kernel arguments point at the table, never at a stream, so streams join and leave
@@ -104,6 +106,18 @@ struct AttnPtrs {
     // batched step: Kc / Vc / position / liveness from the slot table (layer base + ring_off)
     const BatchSlot* slots = nullptr;
     size_t ring_off = 0;
+};
+// The slot-table case of AttnPtrs in compact form (the wide batched step: up to VOX_MAX_SLOTS
+// rows, where six pointer arrays would be ~6 KB of kernel arguments): row z reads q at
+// q + z * q_ld (unused by the fused instances), keeps its partials at part + z * part_ld and
+// takes ring, position and liveness from slots[z]
+struct AttnSlots {
+    const float* q;
+    float* part;
+    float* out;              // f32 rows (unused by the fused instances: they write F.xs)
+    size_t q_ld, part_ld, out_ld;
+    const BatchSlot* slots;
+    size_t ring_off;
 };
 // Kc / Vc of the decoder rings point at f32 elements, at IEEE half ones in the 16-bit mode
 // (VOX_DECODER_KV_FP16) or at FP8 E4M3 bytes in the one-byte mode (VOX_HIP_KV_FP8, vox_kv8.h):
@@ -178,6 +192,13 @@ constexpr int ATT_BLOCK_KEYS = 256;  // keys one decode-attention block covers
 hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window,
                                    float scale, int H, int KVH, int splits, hipStream_t st, int kvt = 0);
 
+// the same for the wide step: nb <= VOX_MAX_SLOTS slots, f.qkv the QKV projection's f32 rows
+// (f.S = 1: [nb][N]), f.xs the wo input planes [row block][3][16][H * hd] that k_gemmf reads.
+// splits == 1: one 1024-thread block per (slot, kv head); > 1: the 128-key split grid, the last
+// block of a (slot, kv head) to arrive merging the partials
+hipError_t launch_attn_batch_wide(int hd, const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window,
+                                  float scale, int H, int KVH, int splits, hipStream_t st, int kvt = 0);
+
 // a batched encoder pass: rows [off[b], off[b] + nr[b]) of the stacked rows belong to stream
 // b, at logical positions pos0[b] + i, with its own K/V ring (layer base)
 struct EncRows {
@@ -216,7 +237,8 @@ hipError_t launch_embed_batch(const BatchSlot* slots, int nb, const void* emb, c
 // stream's ring and toklog[slot][produced % BATCH_TOKLOG], the stream state and the slot
 // advanced (the slot stops at stop_tok, after `left` steps or at its last adapter row), the
 // next input row (0 for a slot that stopped); slots with alts also get the step's
-// stream_fill_alts record (palt: [nb][ARGB][ALT_PART] scratch)
+// stream_fill_alts record (palt: [nb][ARGB][ALT_PART] scratch).  nb <= VOX_MAX_SLOTS (as
+// launch_embed_batch)
 hipError_t launch_argmax_batch(const float* logits, int nb, int V, float* pval, int* pidx, float* palt,
                                BatchSlot* slots, int tokens_cap, int* toklog, const void* emb, const float* esc, int D,
                                float* x, hipStream_t st);
@@ -317,9 +339,16 @@ int gemmf_grid();
 size_t gemmf_flag_ints();      // flags buffer: gemmf_grid() flags, then the recompute counter
 int set_gemmf_wait(int ticks); // owner's wait per partial in 100 MHz ticks (< 0: always recompute); returns the old
 size_t gemmf_ws_floats(int blocks);
+// epoch_dev (null: none): a device word added to `epoch` by the kernel, so that a captured launch
+// hands off under a new epoch at every replay (launch_gemmf_epoch_bump advances the word);
+// rb: row blocks per tile with two planes (0: by shape; 4 or 8)
 hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const void* Wf, int N, const float* bias,
                         float* C, int ldc, uint16_t* xo, float* ws, size_t ws_floats, int* flags, int epoch,
-                        hipStream_t st);
+                        hipStream_t st, const int* epoch_dev = nullptr, int rb = 0);
+// *epoch_dev += by (back to 1 before the sum could overflow): the last kernel of a captured step
+hipError_t launch_gemmf_epoch_bump(int* epoch_dev, int by, hipStream_t st);
+// row blocks per tile of the wide step's projections with two planes (profiles/batch_wide_kbench.txt)
+int gemmf_wide_rb(int M, int N, int K);
 int gemm_planes_np();  // activation planes of the M > 1 GEMMs (2, or 3 with VOX_HIP_GEMM_PLANES=3)
 int set_gemm_planes(int np);  // 2 or 3 (vox_hip_set_gemm_planes); -1 otherwise
 hipError_t launch_im2col3(const float* src, int C, int T, int stride, int off, float* A,

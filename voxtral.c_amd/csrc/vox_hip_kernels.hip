@@ -23,6 +23,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 #include <string.h>
 #include <stdlib.h>
 
@@ -1510,22 +1511,38 @@ constexpr int ATT_LBK = ATT_CH * ATT_LWAVES;  // keys per long-context block
 constexpr int ATT_MIN_BK = 64;      // smallest block (kbench variant): sizes the partials
 constexpr int ATT_MAX_PARTS = 128;  // partials per head the merging block combines
 
-template <int HD, int HPB, int DBG = 0, int FUSE = 0, int NWV = ATT_WAVES, class KT = float>
-__global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AttnPtrs P, int cap, int pos_host,
+// per-row operands of k_attn_decode by argument type: AttnPtrs (pointer arrays; rings from the
+// arrays or, with slots, from the slot table) or AttnSlots (slot table only, base + stride)
+__device__ __forceinline__ const float* attn_q(const AttnPtrs& P, int z) { return P.q[z]; }
+__device__ __forceinline__ float* attn_part(const AttnPtrs& P, int z) { return P.part[z]; }
+__device__ __forceinline__ float* attn_out(const AttnPtrs& P, int z) { return P.out[z]; }
+__device__ __forceinline__ const char* attn_k(const AttnPtrs& P, int z) { return (const char*)P.Kc[z]; }
+__device__ __forceinline__ const char* attn_v(const AttnPtrs& P, int z) { return (const char*)P.Vc[z]; }
+__device__ __forceinline__ const int* attn_state(const AttnPtrs& P, int z) { return P.state[z]; }
+__device__ __forceinline__ const float* attn_q(const AttnSlots& P, int z) { return P.q + (size_t)z * P.q_ld; }
+__device__ __forceinline__ float* attn_part(const AttnSlots& P, int z) { return P.part + (size_t)z * P.part_ld; }
+__device__ __forceinline__ float* attn_out(const AttnSlots& P, int z) { return P.out + (size_t)z * P.out_ld; }
+__device__ __forceinline__ const char* attn_k(const AttnSlots&, int) { return nullptr; }
+__device__ __forceinline__ const char* attn_v(const AttnSlots&, int) { return nullptr; }
+__device__ __forceinline__ const int* attn_state(const AttnSlots&, int) { return nullptr; }
+
+template <int HD, int HPB, int DBG = 0, int FUSE = 0, int NWV = ATT_WAVES, class KT = float, class AP = AttnPtrs>
+__global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AP P, int cap, int pos_host,
                                                           int window, float scale, int H, int KVH,
                                                           int maxs, const AttnFuse F = AttnFuse{}, int kvfast = 0) {
     constexpr int NT = NWV * 64, BK = NWV * ATT_CH;
+    constexpr bool ATTN_ROWS = std::is_same<AP, AttnSlots>::value;  // fused output also as f32 rows (out != null)
     const int zb = blockIdx.z;  // stream of a batched step (0 for a single stream)
     // batched step: ring, position and liveness from the slot table (a stopped slot's blocks
     // leave at once; uniform per block)
     const BatchSlot* __restrict__ sl = P.slots ? P.slots + zb : nullptr;
     if (sl && !sl->live) return;
-    const float* __restrict__ q = P.q[zb];
-    const KT* __restrict__ Kc = reinterpret_cast<const KT*>(sl ? sl->Kc + P.ring_off : (const char*)P.Kc[zb]);
-    const KT* __restrict__ Vc = reinterpret_cast<const KT*>(sl ? sl->Vc + P.ring_off : (const char*)P.Vc[zb]);
-    const int* __restrict__ state = sl ? nullptr : P.state[zb];
-    float* __restrict__ part = P.part[zb];
-    float* __restrict__ out = P.out[zb];
+    const float* __restrict__ q = attn_q(P, zb);
+    const KT* __restrict__ Kc = reinterpret_cast<const KT*>(sl ? sl->Kc + P.ring_off : attn_k(P, zb));
+    const KT* __restrict__ Vc = reinterpret_cast<const KT*>(sl ? sl->Vc + P.ring_off : attn_v(P, zb));
+    const int* __restrict__ state = sl ? nullptr : attn_state(P, zb);
+    float* __restrict__ part = attn_part(P, zb);
+    float* __restrict__ out = attn_out(P, zb);
     constexpr int DQ = HD / 4;   // dims per lane for Q.K
     constexpr int DPL = HD / 64; // dims per lane for P.V
     __shared__ __attribute__((aligned(16))) float sQ[HPB][HD];
@@ -1555,7 +1572,7 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AttnPtrs P, int 
             if (lane == 0) {
                 const size_t bi = P.slots ? (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NWV
                                           : (size_t)blockIdx.y * 16;
-                unsigned long long* d = reinterpret_cast<unsigned long long*>(FUSE ? P.out[0] : P.part[0]) + (bi + wave) * 10;
+                unsigned long long* d = reinterpret_cast<unsigned long long*>(FUSE ? attn_out(P, 0) : attn_part(P, 0)) + (bi + wave) * 10;
                 for (int i = 0; i < 10; i++) d[i] = ts[i];
             }
         }
@@ -1819,6 +1836,9 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AttnPtrs P, int 
                     for (int w = 0; w < NWV; w++) num = fmaf(fw[w], sO[w][h][d0 + i + u], num);
                     v2[u] = den > 0.f ? num * (1.0f / den) : 0.f;
                 }
+                // the wide step's row-major fallback (Q8 tensors) reads the f32 row as well
+                if constexpr (ATTN_ROWS)
+                    if (out) *reinterpret_cast<float2*>(out + (size_t)(h0 + h) * HD + d0 + i) = make_float2(v2[0], v2[1]);
                 uint16_t a0, b0, c0, a1, b1, c1;
                 split3(v2[0], a0, b0, c0);
                 split3(v2[1], a1, b1, c1);
@@ -1938,6 +1958,8 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AttnPtrs P, int 
             const float v = den > 0.f ? num * (1.0f / den) : 0.f;
             if (FUSE) sRow[h][d] = v;
             else out[(size_t)(h0 + h) * HD + d] = v;
+            if constexpr (ATTN_ROWS)
+                if (FUSE && out) out[(size_t)(h0 + h) * HD + d] = v;
         }
         if (FUSE) {
             // the attention row of stream zb into the wo input planes, 8 dims per thread
@@ -4205,6 +4227,36 @@ hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f,
            : kvt == KV_F16 ? attn_batch_fused<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
                            : attn_batch_fused<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
 }
+// the wide step's instances: the fused kernels over the compact slot-table argument (blockIdx.z
+// up to VOX_MAX_SLOTS).  64 slots x 8 kv heads already fill the chip, so <= 256 keys always
+// take the 1024-thread block (no bsplit rule); past 256 keys the 128-key grid of the <= 32 step
+template <class KT>
+static hipError_t attn_batch_wide(const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                                  int KVH, int splits, int maxs, hipStream_t st) {
+    if (splits == 1)
+        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AttnSlots>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
+                           cap, 0, window, scale, H, KVH, maxs, f, 0);
+    else
+        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AttnSlots>),
+                           dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb), dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window,
+                           scale, H, KVH, maxs, f, 1);
+    LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_attn_batch_wide(int hd, const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window,
+                                  float scale, int H, int KVH, int splits, hipStream_t st, int kvt) {
+    const int maxs = attn_maxch(window);
+    // part_ld: the partials of H heads, then one arrival count per kv head (attn_launch's layout)
+    if (kvt < KV_F32 || kvt > KV_FP8 || hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 ||
+        splits > attn_maxsplits(window) || nb < 1 || nb > VOX_MAX_SLOTS || !p.slots || !p.part ||
+        p.part_ld < (size_t)H * maxs * (hd + 2) + KVH || !f.qkv || !f.rope || !f.xs || f.S != 1 ||
+        f.N != (H + 2 * KVH) * hd)
+        return hipErrorInvalidValue;
+    return kvt == KV_FP8   ? attn_batch_wide<kv8_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
+           : kvt == KV_F16 ? attn_batch_wide<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
+                           : attn_batch_wide<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
+}
 // diagnostic variants for tools/kbench (not used by the engine)
 // the batched fused attention (128-key blocks, the bsplit grid) with per-wave phase stamps
 // to p.out[0] (10 u64 per wave: DBG 4 in k_attn_decode)
@@ -4257,7 +4309,7 @@ hipError_t launch_argmax_final(const float* pv, const int* pi, int n, int* state
 
 hipError_t launch_embed_batch(const BatchSlot* slots, int nb, const void* emb, const float* esc, int D, float* x,
                               hipStream_t st) {
-    if (nb < 1 || nb > VOX_MAX_BATCH || !slots) return hipErrorInvalidValue;
+    if (nb < 1 || nb > VOX_MAX_SLOTS || !slots) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_embed_batch, dim3((D + 255) / 256, nb), dim3(256), 0, st, slots, emb, esc, D, x);
     LAUNCH_CHECK();
     return hipSuccess;
@@ -4266,7 +4318,7 @@ hipError_t launch_embed_batch(const BatchSlot* slots, int nb, const void* emb, c
 hipError_t launch_argmax_batch(const float* logits, int nb, int V, float* pval, int* pidx, float* palt,
                                BatchSlot* slots, int tokens_cap, int* toklog, const void* emb, const float* esc, int D,
                                float* x, hipStream_t st) {
-    if (nb < 1 || nb > VOX_MAX_BATCH || !slots || !palt || !toklog) return hipErrorInvalidValue;
+    if (nb < 1 || nb > VOX_MAX_SLOTS || !slots || !palt || !toklog) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_argmax_rows, dim3(ARGB, nb), dim3(256), 0, st, logits, V, pval, pidx, slots, palt);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_argmax_batch_final, dim3(nb), dim3(256), 0, st, pval, pidx, palt, slots, tokens_cap, toklog,

@@ -971,6 +971,7 @@ void vh_stream_stats(const vh_stream_t *s, vh_stats_t *o) {
  * 1105-1145 turned into one batched step for every stream that has adapter rows)
  * ------------------------------------------------------------------------ */
 #define VH_SCHED_STEPS 4096   /* tokens per stream and vox_hip_batch_decode call */
+#define VH_ENC_PASS_MAX 32    /* streams per vox_hip_stream_encode_mel_batch call (the library's limit) */
 
 struct vh_sched {
     vh_ctx_t *ctx;
@@ -1282,8 +1283,14 @@ static int sched_encode(vh_sched_t *q, int overlap) {
         }
         if (nb) {
             const double t0 = now_ms();
-            if (vox_hip_stream_encode_mel_batch(hs, mp, nf, nb, 1, added) < 0)
-                return fail("batched encoder: %s", vox_hip_last_error());
+            /* the library takes at most VH_ENC_PASS_MAX streams per pass: more go in groups, each
+             * on its first stream's queue as a single pass is */
+            for (int g0 = 0; g0 < nb; g0 += VH_ENC_PASS_MAX) {
+                const int gn = nb - g0 < VH_ENC_PASS_MAX ? nb - g0 : VH_ENC_PASS_MAX;
+                if (vox_hip_stream_encode_mel_batch(hs + g0, mp + g0, nf + g0, gn, 1, added + g0) < 0)
+                    return fail("batched encoder: %s", vox_hip_last_error());
+                q->stats.enc_batches++;
+            }
             if (!overlap) {
                 /* the pass completes here (the batched decode would wait for it anyway), so its
                  * time is the encoder's, not the decoder's */
@@ -1298,7 +1305,6 @@ static int sched_encode(vh_sched_t *q, int overlap) {
                  * for, measured no faster: profiles/r4_serve_overlap_ab.txt.) */
                 q->stats.enc_ms += now_ms() - t0;
             }
-            q->stats.enc_batches++;
             for (int k = 0; k < nb; k++) {
                 vh_stream_t *s = q->s[idx[k]];
                 s->pend_n = 0;

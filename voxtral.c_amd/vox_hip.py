@@ -748,10 +748,21 @@ class DeviceArray:
 # ---------------------------------------------------------------------------
 # reference-boundary twins (voxtral_metal.h), host arrays in / out
 # ---------------------------------------------------------------------------
+BATCH_MAX_SLOTS = 128   # VOX_HIP_BATCH_MAX_SLOTS (voxtral_hip.h)
+SCHED_MAX = 128         # VH_SCHED_MAX (vox_hip_host.h)
+
+
 class Batch:
-    """Cross-stream batched greedy decoding (C4): one weight read per step for all streams."""
+    """Cross-stream batched greedy decoding (C4): one weight read per step for all streams.
+
+    max_streams: 1..BATCH_MAX_SLOTS (128).  Calls with up to 32 streams run the skinny MFMA step
+    (or the opt-in R-row GEMV step, which the set_gemv_* / set_wmx4 switches act on); calls with
+    33..128 streams run the wide k_gemmf step over the bf16 fragment-major copies.  Decoder KV
+    rings at 128 streams: ~225 GB f32, ~113 GB half, ~56 GB FP8 (Model.set_kv_dtype)."""
 
     def __init__(self, model: "Model", max_streams: int):
+        if not 1 <= int(max_streams) <= BATCH_MAX_SLOTS:
+            raise ValueError(f"Batch: max_streams must be 1..{BATCH_MAX_SLOTS}")
         self.h = lib().vox_hip_batch_create(model.h, max_streams)
         if not self.h:
             _err("vox_hip_batch_create")
@@ -1035,8 +1046,9 @@ class HostStream:
 
 
 class Scheduler:
-    """vh_sched_t: up to 32 HostStreams (VH_SCHED_MAX) of one model on this GPU; run() decodes every
-    attached stream's pending adapter rows with batched greedy steps."""
+    """vh_sched_t: up to 128 HostStreams (VH_SCHED_MAX) of one model on this GPU; run() decodes every
+    attached stream's pending adapter rows with batched greedy steps (more than 32 streams with
+    rows: the wide step; their deferred chunks are encoded in groups of 32)."""
 
     def __init__(self, ctx: HostCtx, max_streams: int):
         self.h = host_lib().vh_sched_create(ctx.h, max_streams)
