@@ -223,6 +223,38 @@ int vox_hip_gemm_planes(void);
  * (same code and order: same bits); ticks < 0 never waits, so the tests can force that
  * backstop.  Default 5000 (50 us).  Process-wide; returns the previous value. */
 int vox_hip_set_gemmf_wait(int ticks);
+/* Opt-in (no reference counterpart): the stream-K MFMA GEMM (k_gemmf) over the int8
+ * fragment-major copies of Q8 tensors, for models created from now on.  Off (the default), a
+ * model with a Q8 tensor in the encoder or decoder layers runs its M > 1 passes on the row-major
+ * GEMM: nothing changes.  On, such a model takes the k_gemmf paths of a bf16 model -- the
+ * encoder's long passes and the batched encoder pass, the single-stream and the stacked decoder
+ * prefill at every KV ring type, and the wide batched step (33..128 streams) with its LM head
+ * and step graphs -- each launch streaming its own tensor's copy: int8 blocks (half the bytes
+ * of the bf16 copy) with the tensor's row scales, or the bf16 copy of a tensor that is not Q8.
+ * The adapter and conv GEMMs stay on the row-major GEMM, and VOX_HIP_GEMMF=0 /
+ * VOX_HIP_PREFILL_GEMMF=0 keep their meaning.  Exact: int8 -> bf16, and with three planes every
+ * product; each finished f32 sum is multiplied once by its weight row's f32 scale, before bias,
+ * residual, GELU or SwiGLU (the scale * sum rule of the other Q8 kernels).  Against the
+ * row-major GEMM only the f32 summation order differs; against the bf16 k_gemmf instance of the
+ * same tile the accumulators are the same bits.  VOX_HIP_GEMMF_Q8=1 gives the initial value.
+ * vox_hip_set_gemmf_q8 returns 0. */
+int vox_hip_set_gemmf_q8(int on);
+int vox_hip_gemmf_q8(void);
+/* out4: [0] the switch the model took at creation, [1] k_gemmf launches issued on int8
+ * fragments for this model since creation (a launch captured into a wide step graph counts
+ * once at capture and once more at every replay of that graph), [2] Q8 matrices whose shape
+ * k_gemmf accepts (their int8 fragment copy is what it streams; merged Q|K|V and W1|W3 count
+ * once each, the LM head once), [3] Q8 matrices whose shape it refuses (N % 128 or K % 64). */
+int vox_hip_model_gemmf_q8_stats(const vox_hip_model_t *m, long long out4[4]);
+/* Test entry: y[M][N] = x[M][K] against one Q8 matrix (Wq int8 [N][K], scales [N]; host
+ * pointers) through the engine's plane writer and k_gemmf's launcher with the STORE epilogue,
+ * no bias, at the process's plane count.  fmt = 1 streams the int8 fragment copy and applies
+ * `scales`; fmt = 0 streams the bf16 fragment copy of the same integers through the bf16
+ * instance of the same tile configuration and applies no scale (`scales` may be null), so
+ * fmt 1 == f32(fmt 0) * scales[n], bit for bit.  Returns 0; -1 (vox_hip_last_error) for a shape
+ * k_gemmf refuses (M 1..1024, N % 128 == 0, K % 64 == 0). */
+int vox_hip_gemmf_q8_rows(int M, int N, int K, const float *x, const int8_t *Wq, const float *scales, float *y,
+                          int fmt);
 
 /* Per-stream device state: encoder/decoder rolling KV, conv-stem tails, adapter buffer,
  * scratch and a HIP stream.  One model serves many streams. */
@@ -326,8 +358,9 @@ int vox_hip_stream_read_alts(vox_hip_stream_t *s, int first, int n, int *ids_out
  * are sized for 32, 64 or 128 rows, whichever first holds max_streams (a batch of <= 32
  * allocates what it always did).  Calls with up to 32 streams run the skinny MFMA step (two
  * 16-row blocks; or the opt-in R-row GEMV step); calls with 33..64 and 65..128 streams run the
- * wide step: the stacked prefill's k_gemmf layers over the bf16 fragment-major copies (the
- * row-major GEMM where the model has Q8 step tensors), a slot-table decode attention and the LM
+ * wide step: the stacked prefill's k_gemmf layers over the fragment-major copies (bf16; the int8
+ * copies of Q8 step tensors with vox_hip_set_gemmf_q8, without it the row-major GEMM where the
+ * model has Q8 step tensors), a slot-table decode attention and the LM
  * head through k_gemmf, with step graphs of their own.  Per-stream decoder KV rings at 128
  * streams take ~225 GB as f32, ~113 GB as IEEE half and ~56 GB as FP8 of the 288 GB
  * (vox_hip_model_set_kv_dtype); transcript quality on FP8 rings and MXFP4 weights remains

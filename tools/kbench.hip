@@ -1556,6 +1556,52 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "gemmfq")) {
+        // A Q8 tensor's M > 1 GEMM three ways: the row-major GEMM over int8 rows
+        // (launch_gemm with scales: what a Q8 model runs by default), k_gemmf over a bf16 fragment
+        // copy (what a bf16 model runs) and k_gemmf over the int8 fragment copy with the scales;
+        // encoder shapes at 677 rows, decoder shapes at the 38-row prefill, the wide step's at 64
+        // and 128 rows.  A different layer's buffer per launch; the LM head is one tensor.
+        const size_t wsn = 2 * gemmf_ws_floats(gemmf_grid());
+        float* gws = (float*)dmalloc(wsn * 4, 0);
+        int* gfl = (int*)dmalloc(gemmf_flag_ints() * 4, 0);
+        float* ws2 = (float*)dmalloc((size_t)8 << 22, 0);
+        float* Am = (float*)dmalloc((size_t)1024 * 9216 * 4, 1);
+        uint16_t* gp = (uint16_t*)dmalloc((size_t)64 * 3 * 16 * 9216 * 2, 1);
+        uint16_t* go = (uint16_t*)dmalloc((size_t)64 * 3 * 16 * 9216 * 2, 0);
+        float* gc = (float*)dmalloc((size_t)1024 * 18432 * 4, 0);
+        int epoch = 0;
+        struct G { const char* n; int epi, M, N, K; uint16_t* const* W; };
+        uint16_t* const lm1[1] = {emb};
+        std::vector<G> gs = {G{"qkv", EPI_STORE, 677, 6144, 1280, wqkv.data()}, G{"w13", EPI_SWIGLU, 677, 10240, 1280, w13.data()},
+                             G{"wo", EPI_RESID, 677, 1280, 2048, wo.data()}, G{"w2", EPI_RESID, 677, 1280, 5120, w2.data()}};
+        for (int M : {38, 64, 128}) {
+            gs.push_back(G{"dqkv", EPI_STORE, M, DQ + 2 * DKV, D, wqkv.data()});
+            gs.push_back(G{"dwo", EPI_RESID, M, D, DQ, wo.data()});
+            gs.push_back(G{"dw13", EPI_SWIGLU, M, 2 * DH, D, w13.data()});
+            gs.push_back(G{"dw2", EPI_RESID, M, D, DH, w2.data()});
+            if (M != 38) gs.push_back(G{"lm", EPI_STORE, M, V, D, lm1});
+        }
+        for (const G& g : gs)
+            for (int np : {3, 2}) {
+                const int ldc = g.epi == EPI_SWIGLU ? g.N / 2 : g.N;
+                uint16_t* xo = g.epi == EPI_SWIGLU ? go : nullptr;
+                auto W = [&]() { return g.W[g.W == lm1 ? 0 : layer++ % NL]; };
+                // the wide step's tile rule at 64 / 128 rows, the shape rule elsewhere
+                const int rb = (np == 2 && g.M >= 64 && g.M <= 128) ? gemmf_wide_rb(g.M, g.N, g.K) : 0;
+                double rm = np == 3 ? timeit([&] { CK(launch_gemm(g.epi, 3, Am, g.K, W(), wsc, g.K, g.M, g.N, nullptr, gc, ldc, st, ws2,
+                                                                  (size_t)8 << 20)); }, 20, st)
+                                    : 0.0;
+                double bf = timeit([&] { CK(launch_gemmf(g.epi, np, gp, g.K, g.M, W(), g.N, nullptr, gc, ldc, xo, gws, wsn, gfl, ++epoch, st,
+                                                         nullptr, rb)); }, 20, st);
+                double q8 = timeit([&] { CK(launch_gemmf(g.epi, np, gp, g.K, g.M, W(), g.N, nullptr, gc, ldc, xo, gws, wsn, gfl, ++epoch, st,
+                                                         nullptr, rb, wsc)); }, 20, st);
+                printf("gemmfq %-4s M=%4d %6dx%-4d planes %d  row-major int8 %9.2f us  k_gemmf bf16 %9.2f us  k_gemmf int8 %9.2f us  "
+                       "%7.1f GB/s int8\n", g.n, g.M, g.N, g.K, np, rm, bf, q8, 1.0 * g.N * g.K / q8 / 1e3);
+                fflush(stdout);
+            }
+        return 0;
+    }
     if (!only_gemmf) {
     add("gemv qkv  (6144x3072, norm+rope)", timeit([&] { gemv(PRO_NORM, EPI_QKV, wqkv[layer++ % NL], D, DQ + 2 * DKV); }, iters, st), (DQ + 2.0 * DKV) * D * 2);
     add("gemv wo   (3072x4096, resid)", timeit([&] { gemv(PRO_NONE, EPI_RESID, wo[layer++ % NL], DQ, D); }, iters, st), (double)D * DQ * 2);

@@ -201,6 +201,8 @@ struct vox_hip_model {
     vox_hip_wmx4_stats_t mstats;
     int wmx4_batch;                // vox_hip_wmx4_batch() at creation: fragment planes beside the GEMV planes
     long long fstats[4];           // fragment planes: tensors, plane bytes, their bf16 bytes, host microseconds
+    int gemmf_q8;                  // vox_hip_gemmf_q8() at creation: k_gemmf streams the int8 fragment copies of Q8 tensors
+    long long n_gemmf_q8;          // k_gemmf launches on int8 fragments (vox_hip_model_gemmf_q8_stats)
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -361,6 +363,21 @@ extern "C" int vox_hip_set_wmx4_batch(int on) {
     return 0;
 }
 extern "C" int vox_hip_wmx4_batch(void) { return wmx4_batch_mode(); }
+// k_gemmf over the int8 fragment copies of Q8 tensors, for models created from now on
+// (include/voxtral_hip.h); VOX_HIP_GEMMF_Q8=1 gives the initial value
+static int g_gemmf_q8 = -1;
+static int gemmf_q8_mode() {
+    if (g_gemmf_q8 < 0) {
+        const char* e = getenv("VOX_HIP_GEMMF_Q8");
+        g_gemmf_q8 = e && atoi(e) == 1 ? 1 : 0;
+    }
+    return g_gemmf_q8;
+}
+extern "C" int vox_hip_set_gemmf_q8(int on) {
+    g_gemmf_q8 = on ? 1 : 0;
+    return 0;
+}
+extern "C" int vox_hip_gemmf_q8(void) { return gemmf_q8_mode(); }
 
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -537,6 +554,8 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     m->wmx4 = wmx4_mode();
     m->wmx4_batch = m->wmx4 ? wmx4_batch_mode() : 0;
     memset(m->fstats, 0, sizeof m->fstats);
+    m->gemmf_q8 = gemmf_q8_mode();
+    m->n_gemmf_q8 = 0;
     long long* const fst = m->wmx4_batch ? m->fstats : nullptr;
     {
         // VOX_HIP_WPACK=0: every GEMV weight stays raw bf16 (same-machine A/B runs)
@@ -716,6 +735,37 @@ extern "C" int vox_hip_model_wmx4_stats(const vox_hip_model_t* m, vox_hip_wmx4_s
 extern "C" int vox_hip_model_wmx4_batch_stats(const vox_hip_model_t* m, long long out4[4]) {
     if (!m || !out4) return set_err("wmx4_batch_stats: null argument");
     memcpy(out4, m->fstats, sizeof m->fstats);
+    return 0;
+}
+
+// [0] the switch the model took, [1] k_gemmf launches on int8 fragments, [2] / [3] Q8 matrices
+// (merged Q|K|V and W1|W3 count once each, the LM head once) whose shape k_gemmf takes / refuses
+extern "C" int vox_hip_model_gemmf_q8_stats(const vox_hip_model_t* m, long long out4[4]) {
+    if (!m || !out4) return set_err("gemmf_q8_stats: null argument");
+    const vox_hip_config_t& c = m->c;
+    const int ED = c.enc_dim, EQ = c.enc_heads * c.enc_head_dim, EKV = c.enc_kv_heads * c.enc_head_dim;
+    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim;
+    long long ok = 0, no = 0;
+    auto tensor = [&](const float* scale, int N, int K) {
+        if (scale) (gemmf_ok(1, N, K) ? ok : no)++;
+    };
+    for (const EncLayerD& L : m->enc) {
+        tensor(L.sqkv, EQ + 2 * EKV, ED);
+        tensor(L.so, ED, EQ);
+        tensor(L.s13, 2 * c.enc_hidden, ED);
+        tensor(L.s2, ED, c.enc_hidden);
+    }
+    for (const DecLayerD& L : m->dec) {
+        tensor(L.sqkv, DQ + 2 * DKV, DD);
+        tensor(L.so, DD, DQ);
+        tensor(L.s13, 2 * c.dec_hidden, DD);
+        tensor(L.s2, DD, c.dec_hidden);
+    }
+    tensor(m->tok_emb_s, c.vocab, DD);
+    out4[0] = m->gemmf_q8;
+    out4[1] = m->n_gemmf_q8;
+    out4[2] = ok;
+    out4[3] = no;
     return 0;
 }
 
@@ -1425,10 +1475,20 @@ static int enc_gemmf_env() {
     return v;
 }
 
+// Q8 tensors among a pass's layers: k_gemmf takes them only where the model took the
+// vox_hip_set_gemmf_q8 switch (their int8 fragment copies, each launch by its own tensor's format)
+template <class Layer>
+static bool gemmf_fmt_ok(const vox_hip_model_t* m, const std::vector<Layer>& layers) {
+    if (m->gemmf_q8) return true;
+    for (const Layer& L : layers)
+        if (L.sqkv || L.so || L.s13 || L.s2) return false;
+    return true;
+}
+
 static bool enc_gemmf_ok(const vox_hip_model_t* m, int n) {
     const vox_hip_config_t& c = m->c;
     const int ED = c.enc_dim, EQ = c.enc_heads * c.enc_head_dim, EKV = c.enc_kv_heads * c.enc_head_dim;
-    return enc_gemmf_env() && !m->enc[0].sqkv && gemmf_ok(n, EQ + 2 * EKV, ED) && gemmf_ok(n, ED, EQ) &&
+    return enc_gemmf_env() && gemmf_fmt_ok(m, m->enc) && gemmf_ok(n, EQ + 2 * EKV, ED) && gemmf_ok(n, ED, EQ) &&
            gemmf_ok(n, 2 * c.enc_hidden, ED) && gemmf_ok(n, ED, c.enc_hidden) && c.enc_hidden % 64 == 0 &&
            ED <= 4 * 512;
 }
@@ -1441,10 +1501,12 @@ struct GemmfQ {
     size_t ws_n;
     int* flags;
     int* epoch;
+    long long* n_q8;  // the model's count of launches on int8 fragments
 };
 
-static int gemmf_on(const GemmfQ& q, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, int N,
-                    const float* bias, float* C, int ldc, uint16_t* xo) {
+// W: the tensor's fragment-major copy, int8 where wscale (its Q8 row scales) is set
+static int gemmf_on(const GemmfQ& q, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, const float* wscale,
+                    int N, const float* bias, float* C, int ldc, uint16_t* xo) {
     // the hand-off epoch is a host counter baked into the launch: a captured (replayed)
     // k_gemmf would reuse it and read stale partial tiles, so capture is refused
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1460,14 +1522,16 @@ static int gemmf_on(const GemmfQ& q, int epi, const uint16_t* xs, int K, int n, 
         const hipError_t pend = hipGetLastError();
         if (pend != hipSuccess) return set_err("k_gemmf: HIP error pending before the launch: %s", hipGetErrorString(pend));
     }
-    CK(launch_gemmf(epi, gemm_planes_np(), xs, K, n, W, N, bias, C, ldc, xo, q.ws, q.ws_n, q.flags, *q.epoch, q.st));
+    CK(launch_gemmf(epi, gemm_planes_np(), xs, K, n, W, N, bias, C, ldc, xo, q.ws, q.ws_n, q.flags, *q.epoch, q.st,
+                    nullptr, 0, wscale));
+    if (wscale) ++*q.n_q8;
     return 0;
 }
 
-static int gemmf(vox_hip_stream_t* s, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, int N,
-                 const float* bias, float* C, int ldc, uint16_t* xo) {
-    return gemmf_on(GemmfQ{s->st, s->gws, s->gws_n, s->gflags, &s->gepoch}, epi, xs, K, n, W, N, bias, C, ldc,
-                    xo);
+static int gemmf(vox_hip_stream_t* s, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, const float* wscale,
+                 int N, const float* bias, float* C, int ldc, uint16_t* xo) {
+    return gemmf_on(GemmfQ{s->st, s->gws, s->gws_n, s->gflags, &s->gepoch, &s->m->n_gemmf_q8}, epi, xs, K, n, W, wscale,
+                    N, bias, C, ldc, xo);
 }
 
 static int run_encoder_rows_gemmf(vox_hip_stream_t* s, float* x, int n, long long pos0, const float* rope) {
@@ -1491,17 +1555,17 @@ static int run_encoder_rows_gemmf(vox_hip_stream_t* s, float* x, int n, long lon
         float* Vc = s->ev + (size_t)l * s->ecap * EKV;
         // RMSNorm -> planes, QKV (+ bias), RoPE + K/V append (encoder.c:562-607)
         CK(launch_rmsnorm_fplanes(x, n, ED, L.attn_norm, nullptr, c.enc_eps, s->gpa, nullptr, 0, st));
-        if (gemmf(s, EPI_STORE, s->gpa, ED, n, F.wqkv, NQKV, L.bqkv, s->qkv, NQKV, nullptr)) return -1;
+        if (gemmf(s, EPI_STORE, s->gpa, ED, n, F.wqkv, L.sqkv, NQKV, L.bqkv, s->qkv, NQKV, nullptr)) return -1;
         CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
         // windowed attention, output as the wo input planes (encoder.c:609-638)
         CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale, st,
                              s->gws, s->gws_n, s->gpa));
         // wo + bias residual (encoder.c:640-644)
-        if (gemmf(s, EPI_RESID, s->gpa, EQ, n, F.wo, ED, L.bo, x, ED, nullptr)) return -1;
+        if (gemmf(s, EPI_RESID, s->gpa, EQ, n, F.wo, L.so, ED, L.bo, x, ED, nullptr)) return -1;
         // FFN RMSNorm -> planes, W1|W3 with SwiGLU into the w2 planes, w2 + bias residual (:646-684)
         CK(launch_rmsnorm_fplanes(x, n, ED, L.ffn_norm, nullptr, c.enc_eps, s->gpa, nullptr, 0, st));
-        if (gemmf(s, EPI_SWIGLU, s->gpa, ED, n, F.w13, 2 * EH, nullptr, nullptr, EH, s->gpc)) return -1;
-        if (gemmf(s, EPI_RESID, s->gpc, EH, n, F.w2, ED, L.b2, x, ED, nullptr)) return -1;
+        if (gemmf(s, EPI_SWIGLU, s->gpa, ED, n, F.w13, L.s13, 2 * EH, nullptr, nullptr, EH, s->gpc)) return -1;
+        if (gemmf(s, EPI_RESID, s->gpc, EH, n, F.w2, L.s2, ED, L.b2, x, ED, nullptr)) return -1;
     }
     CK(launch_rmsnorm_rows(x, ED, x, ED, m->enc_norm, nullptr, n, ED, c.enc_eps, st));
     return 0;
@@ -1878,7 +1942,7 @@ static int run_encoder_rows_batch(vox_hip_stream_t* lead, float* X, int N, vox_h
         if (gf) {
             const DecFragD& F = m->efrag[l];
             CK(launch_rmsnorm_fplanes(X, N, ED, L.attn_norm, nullptr, c.enc_eps, lead->gpa, nullptr, 0, st));
-            if (gemmf(lead, EPI_STORE, lead->gpa, ED, N, F.wqkv, NQKV, L.bqkv, lead->qkv, NQKV, nullptr)) return -1;
+            if (gemmf(lead, EPI_STORE, lead->gpa, ED, N, F.wqkv, L.sqkv, NQKV, L.bqkv, lead->qkv, NQKV, nullptr)) return -1;
         } else {
             CK(launch_rmsnorm_rows(X, ED, lead->xn, ED, L.attn_norm, nullptr, N, ED, c.enc_eps, st));
             CK(launch_gemm(EPI_STORE, 3, lead->xn, ED, L.wqkv, L.sqkv, ED, N, NQKV, L.bqkv, lead->qkv, NQKV, st,
@@ -1901,10 +1965,10 @@ static int run_encoder_rows_batch(vox_hip_stream_t* lead, float* X, int N, vox_h
                             lead->gws_n, st, gf ? lead->gpa : nullptr));
         if (gf) {
             const DecFragD& F = m->efrag[l];
-            if (gemmf(lead, EPI_RESID, lead->gpa, EQ, N, F.wo, ED, L.bo, X, ED, nullptr)) return -1;
+            if (gemmf(lead, EPI_RESID, lead->gpa, EQ, N, F.wo, L.so, ED, L.bo, X, ED, nullptr)) return -1;
             CK(launch_rmsnorm_fplanes(X, N, ED, L.ffn_norm, nullptr, c.enc_eps, lead->gpa, nullptr, 0, st));
-            if (gemmf(lead, EPI_SWIGLU, lead->gpa, ED, N, F.w13, 2 * EH, nullptr, nullptr, EH, lead->gpc)) return -1;
-            if (gemmf(lead, EPI_RESID, lead->gpc, EH, N, F.w2, ED, L.b2, X, ED, nullptr)) return -1;
+            if (gemmf(lead, EPI_SWIGLU, lead->gpa, ED, N, F.w13, L.s13, 2 * EH, nullptr, nullptr, EH, lead->gpc)) return -1;
+            if (gemmf(lead, EPI_RESID, lead->gpc, EH, N, F.w2, L.s2, ED, L.b2, X, ED, nullptr)) return -1;
         } else {
             CK(launch_gemm(EPI_RESID, 3, lead->att, EQ, L.wo, L.so, EQ, N, ED, L.bo, X, ED, st, lead->gws, lead->gws_n));
             CK(launch_rmsnorm_rows(X, ED, lead->xn, ED, L.ffn_norm, nullptr, N, ED, c.enc_eps, st));
@@ -2093,7 +2157,7 @@ static int dec_gemmf_env() {
 static bool dec_gemmf_ok(const vox_hip_model_t* m, int n) {
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim;
-    return enc_gemmf_env() && dec_gemmf_env() && !m->dec[0].sqkv && n >= 1 && n <= PLANE_MAX_ROWS && gemmf_ok(n, DQ + 2 * DKV, DD) &&
+    return enc_gemmf_env() && dec_gemmf_env() && gemmf_fmt_ok(m, m->dec) && n >= 1 && n <= PLANE_MAX_ROWS && gemmf_ok(n, DQ + 2 * DKV, DD) &&
            gemmf_ok(n, DD, DQ) && gemmf_ok(n, 2 * c.dec_hidden, DD) && gemmf_ok(n, DD, c.dec_hidden) &&
            c.dec_hidden % 64 == 0;
 }
@@ -2129,16 +2193,16 @@ static int dec_layers_gemmf(vox_hip_stream_t* s, const GemmfQ& q, float* x, int 
         const DecFragD& F = m->dfrag[l];
         // RMSNorm -> planes, QKV (decoder.c:509-530)
         CK(launch_rmsnorm_fplanes(x, n, DD, L.attn_norm, nullptr, c.dec_eps, s->dpa, nullptr, 0, q.st));
-        if (gemmf_on(q, EPI_STORE, s->dpa, DD, n, F.wqkv, DQ + 2 * DKV, nullptr, s->qkvd, DQ + 2 * DKV, nullptr)) return -1;
+        if (gemmf_on(q, EPI_STORE, s->dpa, DD, n, F.wqkv, L.sqkv, DQ + 2 * DKV, nullptr, s->qkvd, DQ + 2 * DKV, nullptr)) return -1;
         // RoPE + K/V append + attention, its rows as the wo planes in s->dpa (attn's job)
         if (attn(l)) return -1;
         // wo + residual (decoder.c:552-560)
-        if (gemmf_on(q, EPI_RESID, s->dpa, DQ, n, F.wo, DD, nullptr, x, DD, nullptr)) return -1;
+        if (gemmf_on(q, EPI_RESID, s->dpa, DQ, n, F.wo, L.so, DD, nullptr, x, DD, nullptr)) return -1;
         // RMSNorm * (1 + ada) -> planes, W1|W3 with SwiGLU into the w2 planes, w2 + residual (:562-606)
         CK(launch_rmsnorm_fplanes(x, n, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, c.dec_eps, s->dpa, nullptr, 0,
                                   q.st));
-        if (gemmf_on(q, EPI_SWIGLU, s->dpa, DD, n, F.w13, 2 * DH, nullptr, nullptr, DH, s->dpc)) return -1;
-        if (gemmf_on(q, EPI_RESID, s->dpc, DH, n, F.w2, DD, nullptr, x, DD, nullptr)) return -1;
+        if (gemmf_on(q, EPI_SWIGLU, s->dpa, DD, n, F.w13, L.s13, 2 * DH, nullptr, nullptr, DH, s->dpc)) return -1;
+        if (gemmf_on(q, EPI_RESID, s->dpc, DH, n, F.w2, L.s2, DD, nullptr, x, DD, nullptr)) return -1;
     }
     return 0;
 }
@@ -2166,7 +2230,7 @@ static int run_decoder_rows(vox_hip_stream_t* s, float* x, int n, int pos0, cons
         // the hand-off flags before the queue descriptor copies the pointer (a stream whose
         // encoder never ran a k_gemmf pass has none yet)
         if (!s->gflags) CK(dalloc(&s->gflags, gemmf_flag_ints()));
-        return dec_layers_gemmf(s, GemmfQ{st, s->gws, s->gws_n, s->gflags, &s->gepoch}, x, n, [&](int l) -> int {
+        return dec_layers_gemmf(s, GemmfQ{st, s->gws, s->gws_n, s->gflags, &s->gepoch, &m->n_gemmf_q8}, x, n, [&](int l) -> int {
             float* Kc = dec_ring(s, s->dk, l);
             float* Vc = dec_ring(s, s->dv, l);
             CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kvt));
@@ -2941,6 +3005,60 @@ extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float*
     return 0;
 }
 
+// Test entry: M rows x [M][K] against one Q8 matrix (Wq [N][K] int8, scales [N]) through the
+// engine's plane writer (launch_split_fplanes) and launch_gemmf with EPI_STORE, no bias, at the
+// process's plane count (include/voxtral_hip.h).  fmt = 1: the int8 fragment copy with the
+// scales; fmt = 0: the bf16 fragment copy of the same integers, no scale.
+extern "C" int vox_hip_gemmf_q8_rows(int M, int N, int K, const float* x, const int8_t* Wq, const float* scales, float* y,
+                                     int fmt) {
+    std::lock_guard<std::mutex> lk(g_twin_mu);
+    if (!x || !Wq || !y || (fmt && !scales)) return set_err("gemmf_q8_rows: null argument");
+    if (fmt != 0 && fmt != 1) return set_err("gemmf_q8_rows: fmt is 0 or 1");
+    if (!gemmf_ok(M, N, K) || M > PLANE_MAX_ROWS)
+        return set_err("gemmf_q8_rows: k_gemmf does not take M %d N %d K %d (M 1..1024, N %% 128, K %% 64)", M, N, K);
+    if (twin_init()) return -1;
+    uint8_t *dW = nullptr, *dF = nullptr;
+    float *dx = nullptr, *dy = nullptr, *ds = nullptr, *dws = nullptr;
+    uint16_t* dxs = nullptr;
+    int* dflags = nullptr;
+    auto run = [&]() -> int {
+        const size_t n = (size_t)N * K;
+        if (fmt) {
+            CK(dalloc(&dW, n));
+            CK(dalloc(&ds, (size_t)N));
+            if (upload(dW, Wq, n) || upload(ds, scales, (size_t)N * 4) || frag_copy(&dF, dW, N, K, 1)) return -1;
+        } else {
+            // every int8 is a bf16: the high half of its f32
+            std::vector<uint16_t> wb(n);
+            for (size_t i = 0; i < n; i++) {
+                const float f = (float)Wq[i];
+                uint32_t u;
+                memcpy(&u, &f, 4);
+                wb[i] = (uint16_t)(u >> 16);
+            }
+            CK(dalloc(&dW, n * 2));
+            if (upload(dW, wb.data(), n * 2) || frag_copy(&dF, dW, N, K, 0)) return -1;
+        }
+        const size_t rows = (size_t)(M + 127) / 128 * 128;  // whole tiles (dalloc zeroes: rows past M are 0)
+        const size_t ws_n = gemmf_ws_floats(gemmf_grid());
+        CK(dalloc(&dx, (size_t)M * K));
+        CK(dalloc(&dxs, rows * 3 * K));
+        CK(dalloc(&dy, (size_t)M * N));
+        CK(dalloc(&dws, ws_n));
+        CK(dalloc(&dflags, gemmf_flag_ints()));
+        if (upload(dx, x, (size_t)M * K * 4)) return -1;
+        CK(launch_split_fplanes(dx, M, K, dxs, g_twin_st));
+        CK(launch_gemmf(EPI_STORE, gemm_planes_np(), dxs, K, M, dF, N, nullptr, dy, N, nullptr, dws, ws_n, dflags, 1,
+                        g_twin_st, nullptr, 0, fmt ? ds : nullptr));
+        CK(hipStreamSynchronize(g_twin_st));
+        CK(hipMemcpy(y, dy, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    dfree(dW); dfree(dF); dfree(dx); dfree(dxs); dfree(dy); dfree(ds); dfree(dws); dfree(dflags);
+    return rc ? -1 : 0;
+}
+
 extern "C" void vox_hip_sgemm_bf16(int M, int N, int K, const float* A, const uint16_t* B, float* C) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
     twin_sgemm(M, N, K, A, B, nullptr, C);
@@ -3198,6 +3316,7 @@ struct vox_hip_batch {
     int* wflags;
     int* wepoch;
     hipGraphExec_t gwexec[3][2][STEP_GRAPHS];
+    int wide_q8;  // k_gemmf launches on int8 fragments in one wide step (set by batch_step_wide)
     long long n_calls, n_replays, n_rows, n_captures, n_prefill_passes, n_prefilled;
     // split-K workspace of the stacked prefills (not the lead stream's: with an encoder pass
     // running beside the batched steps, that stream's queue may be using its own), and the
@@ -3722,11 +3841,17 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     hipStream_t st = b->st;
     const int np = gemm_planes_np();
     const bool gf = dec_gemmf_ok(m, nb);
-    const bool lm_gf = !m->tok_emb_s && enc_gemmf_env() && dec_gemmf_env() && gemmf_ok(nb, c.vocab, DD);
+    const bool lm_gf = (!m->tok_emb_s || m->gemmf_q8) && enc_gemmf_env() && dec_gemmf_env() && gemmf_ok(nb, c.vocab, DD);
     int launches = 0;
-    auto gemmf_w = [&](int epi, const uint16_t* xs, int K, const uint8_t* W, int N, float* C, int ldc, uint16_t* xo) -> int {
+    b->wide_q8 = 0;  // this step's launches on int8 fragments (batch_run counts them again per replay)
+    auto gemmf_w = [&](int epi, const uint16_t* xs, int K, const uint8_t* W, const float* wscale, int N, float* C, int ldc,
+                       uint16_t* xo) -> int {
         CK(launch_gemmf(epi, np, xs, K, nb, W, N, nullptr, C, ldc, xo, b->pgws, GEMM_WS_ELEMS, b->wflags, ++launches, st,
-                        b->wepoch, gemmf_wide_rb(nb, N, K)));
+                        b->wepoch, gemmf_wide_rb(nb, N, K), wscale));
+        if (wscale) {
+            b->wide_q8++;
+            m->n_gemmf_q8++;
+        }
         return 0;
     };
     AttnSlots ap;
@@ -3742,7 +3867,7 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
         // RMSNorm, QKV rows (decoder.c:509-530)
         if (gf) {
             CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.attn_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
-            if (gemmf_w(EPI_STORE, b->wpa, DD, m->dfrag[l].wqkv, QKV, b->wqkv, QKV, nullptr)) return -1;
+            if (gemmf_w(EPI_STORE, b->wpa, DD, m->dfrag[l].wqkv, L.sqkv, QKV, b->wqkv, QKV, nullptr)) return -1;
         } else {
             CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.attn_norm, nullptr, nb, DD, c.dec_eps, st));
             CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, L.wqkv, L.sqkv, DD, nb, QKV, nullptr, b->wqkv, QKV, st, b->pgws, GEMM_WS_ELEMS));
@@ -3752,10 +3877,10 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
         CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         if (gf) {
             const DecFragD& F = m->dfrag[l];
-            if (gemmf_w(EPI_RESID, b->wpa, DQ, F.wo, DD, b->x, DD, nullptr)) return -1;
+            if (gemmf_w(EPI_RESID, b->wpa, DQ, F.wo, L.so, DD, b->x, DD, nullptr)) return -1;
             CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, c.dec_eps, b->wpa, nullptr, 0, st));
-            if (gemmf_w(EPI_SWIGLU, b->wpa, DD, F.w13, 2 * DH, nullptr, DH, b->wpc)) return -1;
-            if (gemmf_w(EPI_RESID, b->wpc, DH, F.w2, DD, b->x, DD, nullptr)) return -1;
+            if (gemmf_w(EPI_SWIGLU, b->wpa, DD, F.w13, L.s13, 2 * DH, nullptr, DH, b->wpc)) return -1;
+            if (gemmf_w(EPI_RESID, b->wpc, DH, F.w2, L.s2, DD, b->x, DD, nullptr)) return -1;
         } else {
             CK(launch_gemm(EPI_RESID, 3, b->att, DQ, L.wo, L.so, DQ, nb, DD, nullptr, b->x, DD, st, b->pgws, GEMM_WS_ELEMS));
             CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, nb, DD, c.dec_eps, st));
@@ -3767,7 +3892,7 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     // token log and next inputs (decoder.c:762-779)
     if (lm_gf) {
         CK(launch_rmsnorm_fplanes(b->x, nb, DD, m->dec_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
-        if (gemmf_w(EPI_STORE, b->wpa, DD, m->lm_frag, c.vocab, b->logits, c.vocab, nullptr)) return -1;
+        if (gemmf_w(EPI_STORE, b->wpa, DD, m->lm_frag, m->tok_emb_s, c.vocab, b->logits, c.vocab, nullptr)) return -1;
     } else {
         CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, m->dec_norm, nullptr, nb, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, m->tok_emb, m->tok_emb_s, DD, nb, c.vocab, nullptr, b->logits, c.vocab, st,
@@ -3831,6 +3956,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         if (gemv) b->n_gemv_captures++;
     }
     for (int k = 0; k < steps; k++) CK(hipGraphLaunch(ge, b->st));
+    if (wide) b->m->n_gemmf_q8 += (long long)steps * b->wide_q8;  // each replay, beside the capture's own count
     b->n_replays += steps;
     return 0;
 }
@@ -3905,7 +4031,7 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
     }
     if (dec_gemmf_ok(m, N)) {
         if (!b->gflags) CK(dalloc(&b->gflags, gemmf_flag_ints()));
-        if (dec_layers_gemmf(lead, GemmfQ{st, gws, gws_n, b->gflags, &b->gepoch}, X, N, [&](int l) -> int {
+        if (dec_layers_gemmf(lead, GemmfQ{st, gws, gws_n, b->gflags, &b->gepoch, &m->n_gemmf_q8}, X, N, [&](int l) -> int {
                 for (int i = 0; i < B; i++) {
                     er.Kc[i] = dec_ring(ss[i], ss[i]->dk, l);
                     er.Vc[i] = dec_ring(ss[i], ss[i]->dv, l);

@@ -251,4 +251,16 @@ __device__ __forceinline__ float dot16q(uint4 w, const float4 (&x)[4], float acc
     return acc;
 }
 
+// 8 int8 (two dwords, k ascending) as the 8 bf16 of an MFMA operand: every int8 is a bf16, so
+// the f32 conversion's high half is the value itself (k_skf / k_skl / k_gemmf, WF_Q8)
+__device__ __forceinline__ bf16x8 i8x8_bf16(uint32_t lo, uint32_t hi) {
+    uint32_t h[8];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        h[b] = __float_as_uint(i8f(lo, b)) >> 16;
+        h[4 + b] = __float_as_uint(i8f(hi, b)) >> 16;
+    }
+    return __builtin_bit_cast(bf16x8, make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)));
+}
+
 }  // namespace vox

@@ -33,6 +33,9 @@
 // captured into a graph (the engine refuses it while its stream is capturing); a captured one
 // adds a device word to its epoch (GemmfArgs::epoch_dev) that the graph's last kernel advances
 // past every epoch of the step (k_gemmf_epoch_bump), so each replay hands off under new epochs.
+// The WF_Q8 instances (vox_hip_set_gemmf_q8) stream a Q8 tensor's int8 fragment
+// copy -- half the weight chunks per stage, converted to the same bf16 fragments in registers --
+// and apply the row scales to the finished sums; everything above is shared with WF_BF16.
 #include "vox_hip_internal.h"
 #include "vox_hip_dev.h"
 
@@ -62,8 +65,9 @@ __device__ __forceinline__ void wait_vm() {
 struct GemmfArgs {
     const uint16_t* xs;  // planes [rb][3][16][K] (frag_at)
     int K, M;
-    const uint8_t* W;    // fragment-major bf16 [N / 16][K / 64][2][1 KiB]
+    const uint8_t* W;    // fragment-major bf16 [N / 16][K / 64][2][1 KiB], or int8 [N / 16][K / 64][1 KiB] (wscale)
     int N;
+    const float* wscale; // [N] row scales of the int8 copy (WF_Q8 instances), null for bf16
     const float* bias;   // [N] or null
     float* C;            // f32 output [M][ldc] (SWIGLU: [M][N / 2]) unless xo
     int ldc;
@@ -87,12 +91,19 @@ static int g_gemmf_wait = GF_TIMEOUT_TICKS;  // vox_hip_set_gemmf_wait (tests fo
 // NWV = 4 WR waves: wave w takes column slot w % 4 (NG groups) and row share w / 4 (RB / WR
 // row blocks); with WR = 2 two waves share each SIMD, so one's fragment reads overlap the
 // other's MFMAs
-template <int NP, int RB, int NG, int WR>
+//
+// WF = WF_Q8 streams the int8 fragment copy (k_frag_pack<1>): one 1-KiB block per column group
+// and stage, lane l's 16 B = half 0 (first 8 B) and half 1 (last 8 B) of the bf16 copy's two
+// chunks, so a stage carries 4 NG weight chunks instead of 8 NG; the lane converts its 8 int8
+// of a half to the bf16 fragment the bf16 copy holds (i8x8_bf16, exact) once per half stage,
+// and the row scale meets the finished sum in the epilogue (gf_out).
+template <int NP, int RB, int NG, int WR, int WF = WF_BF16>
 struct GfCfg {
+    static_assert(WF == WF_BF16 || WF == WF_Q8, "k_gemmf streams bf16 or int8 fragments");
     static constexpr int NWV = 4 * WR;              // waves per block
     static constexpr int RBW = RB / WR;             // row blocks per wave
     static constexpr int CH = RB * NP * 2;          // 1 KiB plane chunks per stage
-    static constexpr int CW = 4 * NG * 2;           // 1 KiB weight chunks per stage (4 column slots)
+    static constexpr int CW = 4 * NG * (WF == WF_Q8 ? 1 : 2);  // 1 KiB weight chunks per stage (4 column slots)
     static constexpr int NA = CH / NWV;             // plane chunks per wave
     static constexpr int NB = CW / NWV;             // weight chunks per wave
     static constexpr int SLOT = (CH + CW) * 512;    // bf16 elements per LDS slot: planes, then weights
@@ -101,10 +112,10 @@ struct GfCfg {
 
 // one stage's loads into ring slot SL, all LDS-DMA (no VGPR-destination load in the loop:
 // hipcc waits vmcnt(0) at the use of one, which would drain the DMA ring every stage)
-template <int NP, int RB, int NG, int WR, int SL>
+template <int NP, int RB, int NG, int WR, int SL, int WF = WF_BF16>
 __device__ __forceinline__ void gf_issue(const uint16_t* xb, size_t plane, const uint8_t* wt, int KB, int s,
                                          uint16_t* lds, int wave, int lane) {
-    using C = GfCfg<NP, RB, NG, WR>;
+    using C = GfCfg<NP, RB, NG, WR, WF>;
     if (VOX_GF_DIAG == 2) return;
     uint16_t* dst = lds + SL * C::SLOT;
 #pragma unroll
@@ -116,8 +127,10 @@ __device__ __forceinline__ void gf_issue(const uint16_t* xb, size_t plane, const
     }
 #pragma unroll
     for (int i = 0; i < C::NB; i++) {
-        const int j = wave + C::NWV * i;  // weight chunk: column group j / 2 of the tile, half j % 2
-        const uint8_t* src = wt + ((size_t)(j >> 1) * KB + s) * 2048 + (j & 1) * 1024 + lane * 16;
+        // weight chunk: column group j / 2 of the tile, half j % 2 (int8: group j's whole block)
+        const int j = wave + C::NWV * i;
+        const uint8_t* src = WF == WF_Q8 ? wt + ((size_t)j * KB + s) * 1024 + lane * 16
+                                         : wt + ((size_t)(j >> 1) * KB + s) * 2048 + (j & 1) * 1024 + lane * 16;
         __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)(dst + (C::CH + j) * 512), 16, 0, 0);
     }
 }
@@ -125,21 +138,38 @@ __device__ __forceinline__ void gf_issue(const uint16_t* xb, size_t plane, const
 // The fragments of one half stage (32 of the 64 k) in registers (every row block of the
 // wave's share: rows past M are computed and discarded, which keeps the reads and MFMAs
 // branch-free).
-template <int NP, int RB, int NG, int WR>
+template <int NP, int RB, int NG, int WR, int WF = WF_BF16>
 struct GfHalf {
     bf16x8 w[NG];
     bf16x8 x[RB / WR][NP];
 };
 
-// read half T of ring slot SL's fragments (10 ds_read_b128 for 128 x 128 tiles, two planes)
-template <int NP, int RB, int NG, int WR, int SL, int T>
-__device__ __forceinline__ void gf_read(const uint16_t* lds, int wave, int lane, GfHalf<NP, RB, NG, WR>& f) {
-    using C = GfCfg<NP, RB, NG, WR>;
+// WF_Q8: a stage's int8 blocks as read from the ring (both halves: one ds_read_b128 per column
+// group and stage, with the half-0 read), kept until gf_cvt has made the second half of them
+template <int NG, int WF>
+struct GfRaw {
+    u32x4 q[WF == WF_Q8 ? NG : 1];
+};
+
+// read half T of ring slot SL's fragments (10 ds_read_b128 for 128 x 128 tiles, two planes).
+// WF_Q8: the weight blocks come with half 0 only (into raw); gf_cvt makes f.w of either half
+template <int NP, int RB, int NG, int WR, int SL, int T, int WF = WF_BF16>
+__device__ __forceinline__ void gf_read(const uint16_t* lds, int wave, int lane, GfHalf<NP, RB, NG, WR, WF>& f,
+                                        GfRaw<NG, WF>& raw) {
+    using C = GfCfg<NP, RB, NG, WR, WF>;
     const uint16_t* src = lds + SL * C::SLOT;
     const int wc = wave & 3, r0 = (wave >> 2) * C::RBW;
+    if constexpr (WF == WF_Q8) {
+        if (T == 0) {
 #pragma unroll
-    for (int g = 0; g < NG; g++)
-        f.w[g] = *reinterpret_cast<const bf16x8*>(src + (C::CH + (wc * NG + g) * 2 + T) * 512 + lane * 8);
+            for (int g = 0; g < NG; g++)
+                raw.q[g] = *reinterpret_cast<const u32x4*>(src + (C::CH + wc * NG + g) * 512 + lane * 8);
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < NG; g++)
+            f.w[g] = *reinterpret_cast<const bf16x8*>(src + (C::CH + (wc * NG + g) * 2 + T) * 512 + lane * 8);
+    }
 #pragma unroll
     for (int i = 0; i < C::RBW; i++)
 #pragma unroll
@@ -147,8 +177,18 @@ __device__ __forceinline__ void gf_read(const uint16_t* lds, int wave, int lane,
             f.x[i][p] = *reinterpret_cast<const bf16x8*>(src + (((r0 + i) * NP + p) * 2 + T) * 512 + lane * 8);
 }
 
-template <int NP, int RB, int NG, int WR>
-__device__ __forceinline__ void gf_mma(const GfHalf<NP, RB, NG, WR>& f, f32x4 (&acc)[RB / WR][NG]) {
+// WF_Q8: half T of the stage's int8 blocks as the bf16 fragments of the bf16 copy (exact: every
+// int8 is a bf16), once per wave and half stage; all RBW NP MFMAs of the half reuse them
+template <int NP, int RB, int NG, int WR, int T, int WF>
+__device__ __forceinline__ void gf_cvt(const GfRaw<NG, WF>& raw, GfHalf<NP, RB, NG, WR, WF>& f) {
+    if constexpr (WF == WF_Q8) {
+#pragma unroll
+        for (int g = 0; g < NG; g++) f.w[g] = T ? i8x8_bf16(raw.q[g][2], raw.q[g][3]) : i8x8_bf16(raw.q[g][0], raw.q[g][1]);
+    }
+}
+
+template <int NP, int RB, int NG, int WR, int WF = WF_BF16>
+__device__ __forceinline__ void gf_mma(const GfHalf<NP, RB, NG, WR, WF>& f, f32x4 (&acc)[RB / WR][NG]) {
     if (VOX_GF_DIAG == 1) {
         acc[0][0][0] += __builtin_bit_cast(float, (uint32_t)f.x[0][0][0] & 0x3f00u);  // keep the reads live
         return;
@@ -175,19 +215,24 @@ __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(15 | (
 //   wait for stage s + 1's DMA (stage s + 2's may stay in flight) -> barrier (every wave's DMA
 //   landed; every wave done reading stage s's slot) -> DMA stage s + 3 into stage s's slot ->
 //   read H0(s + 1) | MFMAs H1(s) | lgkmcnt(0)
-template <int NP, int RB, int NG, int WR>
+// WF_Q8: the H0 read brings the stage's whole int8 blocks; their second half is converted
+// beside the MFMAs of H0 (no LDS read behind it), their first half after the lgkmcnt(0) that
+// ends the iteration.
+template <int NP, int RB, int NG, int WR, int WF = WF_BF16>
 __device__ __forceinline__ void gf_stages(const GemmfArgs& a, uint16_t* lds, int mt, int nt, int s0, int s1,
                                           f32x4 (&acc)[RB / WR][NG]) {
-    using C = GfCfg<NP, RB, NG, WR>;
+    using C = GfCfg<NP, RB, NG, WR, WF>;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int KB = a.K >> 6;
     const size_t plane = (size_t)SK_ROWS * a.K;                 // elements per plane of a row block
     const uint16_t* xb = a.xs + (size_t)(mt * RB) * 3 * plane;  // this row tile's planes
-    const uint8_t* wt = a.W + (size_t)nt * 4 * NG * KB * 2048;  // this column tile's weight groups
-    GfHalf<NP, RB, NG, WR> H0, H1;
-    gf_issue<NP, RB, NG, WR, 0>(xb, plane, wt, KB, s0, lds, wave, lane);
-    if (s0 + 1 < s1) gf_issue<NP, RB, NG, WR, 1>(xb, plane, wt, KB, s0 + 1, lds, wave, lane);
-    if (s0 + 2 < s1) gf_issue<NP, RB, NG, WR, 2>(xb, plane, wt, KB, s0 + 2, lds, wave, lane);
+    // this column tile's weight groups
+    const uint8_t* wt = a.W + (size_t)nt * 4 * NG * KB * (WF == WF_Q8 ? 1024 : 2048);
+    GfHalf<NP, RB, NG, WR, WF> H0, H1;
+    GfRaw<NG, WF> raw;
+    gf_issue<NP, RB, NG, WR, 0, WF>(xb, plane, wt, KB, s0, lds, wave, lane);
+    if (s0 + 1 < s1) gf_issue<NP, RB, NG, WR, 1, WF>(xb, plane, wt, KB, s0 + 1, lds, wave, lane);
+    if (s0 + 2 < s1) gf_issue<NP, RB, NG, WR, 2, WF>(xb, plane, wt, KB, s0 + 2, lds, wave, lane);
     // stage s0's DMA landed (stages s0 + 1, s0 + 2 may stay in flight)
     if (VOX_GF_DIAG == 2) {
     } else if (s0 + 2 < s1) wait_vm<2 * (C::NA + C::NB)>();
@@ -196,13 +241,15 @@ __device__ __forceinline__ void gf_stages(const GemmfArgs& a, uint16_t* lds, int
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    gf_read<NP, RB, NG, WR, 0, 0>(lds, wave, lane, H0);
+    gf_read<NP, RB, NG, WR, 0, 0, WF>(lds, wave, lane, H0, raw);
     wait_lgkm0();
+    gf_cvt<NP, RB, NG, WR, 0, WF>(raw, H0);
 #define GF_STAGE(J)                                                                                              \
     if (s + J < s1) {                                                                                            \
-        gf_read<NP, RB, NG, WR, J, 1>(lds, wave, lane, H1);                                                      \
+        gf_read<NP, RB, NG, WR, J, 1, WF>(lds, wave, lane, H1, raw);                                             \
+        gf_cvt<NP, RB, NG, WR, 1, WF>(raw, H1);                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        gf_mma<NP, RB, NG, WR>(H0, acc);                                                                         \
+        gf_mma<NP, RB, NG, WR, WF>(H0, acc);                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         wait_lgkm0();                                                                                            \
         if (s + J + 1 < s1) {                                                                                    \
@@ -212,13 +259,14 @@ __device__ __forceinline__ void gf_stages(const GemmfArgs& a, uint16_t* lds, int
             asm volatile("" ::: "memory");                                                                       \
             __builtin_amdgcn_s_barrier();                                                                        \
             asm volatile("" ::: "memory");                                                                       \
-            if (s + J + 3 < s1) gf_issue<NP, RB, NG, WR, J>(xb, plane, wt, KB, s + J + 3, lds, wave, lane);      \
-            gf_read<NP, RB, NG, WR, (J + 1) % 3, 0>(lds, wave, lane, H0);                                        \
+            if (s + J + 3 < s1) gf_issue<NP, RB, NG, WR, J, WF>(xb, plane, wt, KB, s + J + 3, lds, wave, lane);  \
+            gf_read<NP, RB, NG, WR, (J + 1) % 3, 0, WF>(lds, wave, lane, H0, raw);                               \
         }                                                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        gf_mma<NP, RB, NG, WR>(H1, acc);                                                                         \
+        gf_mma<NP, RB, NG, WR, WF>(H1, acc);                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         wait_lgkm0();                                                                                            \
+        if (s + J + 1 < s1) gf_cvt<NP, RB, NG, WR, 0, WF>(raw, H0);                                              \
     }
     for (int s = s0; s < s1; s += 3) {
         GF_STAGE(0)
@@ -235,9 +283,26 @@ __device__ __forceinline__ long long gf_bound(long long U, int G, int b) { retur
 // epilogue of one 16 x 16 output fragment of weight group gg for row m (lane & 15 of its row
 // block): columns n = gg * 16 + (lane >> 4) * 4 + e.  EPI_SWIGLU: groups (gg, gg + 1) = the
 // (w1, w3) rows of 16 hidden units (upload_w13 interleave; gg even), v1 = group gg + 1.
-template <int EPI>
-__device__ __forceinline__ void gf_out(const GemmfArgs& a, int m, int gg, int lane, const f32x4& v0, const f32x4& v1) {
+// WF_Q8: each accumulator first times its own weight row's scale (the scale * sum rule of the
+// other Q8 kernels), as one rounded f32 multiply that no later add may fuse with.
+__device__ __forceinline__ f32x4 gf_scaled(const f32x4& v, const float* sc) {
+    const float4 s = *reinterpret_cast<const float4*>(sc);
+    f32x4 r = {v[0] * s.x, v[1] * s.y, v[2] * s.z, v[3] * s.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        float t = r[e];
+        asm volatile("" : "+v"(t));  // the product is rounded here: no fma with the bias or residual
+        r[e] = t;
+    }
+    return r;
+}
+
+template <int EPI, int WF = WF_BF16>
+__device__ __forceinline__ void gf_out(const GemmfArgs& a, int m, int gg, int lane, const f32x4& w0, const f32x4& w1) {
+    const int nq = gg * 16 + (lane >> 4) * 4;
+    const f32x4 v0 = WF == WF_Q8 ? gf_scaled(w0, a.wscale + nq) : w0;
     if (EPI == EPI_SWIGLU) {
+        const f32x4 v1 = WF == WF_Q8 ? gf_scaled(w1, a.wscale + nq + 16) : w1;
         const int h0 = (gg >> 1) * 16 + (lane >> 4) * 4;
         float v[4];
 #pragma unroll
@@ -280,9 +345,9 @@ __device__ __forceinline__ void gf_out(const GemmfArgs& a, int m, int gg, int la
     *cp = v;
 }
 
-template <int EPI, int NP, int RB, int NG, int WR>
+template <int EPI, int NP, int RB, int NG, int WR, int WF = WF_BF16>
 __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
-    using C = GfCfg<NP, RB, NG, WR>;
+    using C = GfCfg<NP, RB, NG, WR, WF>;
     constexpr int RBW = C::RBW;
     extern __shared__ __attribute__((aligned(16))) uint16_t gf_lds[];
     // the owner's flag mask, one 8-byte word past the ring (the same array)
@@ -309,7 +374,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
         for (int i = 0; i < RBW; i++)
 #pragma unroll
             for (int g = 0; g < NG; g++) acc[i][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gf_stages<NP, RB, NG, WR>(a, gf_lds, mt, nt, s0, s1, acc);
+        gf_stages<NP, RB, NG, WR, WF>(a, gf_lds, mt, nt, s0, s1, acc);
         u += s1 - s0;
         if (s0 > 0) {
             // a later part of tile t: publish it for the tile's owner (write-through stores,
@@ -368,7 +433,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
                         for (int g = 0; g < NG; g++) part[i][g] = f32x4{0.f, 0.f, 0.f, 0.f};
                     const int q0 = (int)(gf_bound(a.U, G, pb) - (long long)t * a.S);
                     const int q1 = (int)(min(gf_bound(a.U, G, pb + 1), tend) - (long long)t * a.S);
-                    gf_stages<NP, RB, NG, WR>(a, gf_lds, mt, nt, q0, q1, part);
+                    gf_stages<NP, RB, NG, WR, WF>(a, gf_lds, mt, nt, q0, q1, part);
                 }
 #pragma unroll
                 for (int i = 0; i < RBW; i++)
@@ -385,7 +450,7 @@ __global__ __launch_bounds__(256 * WR, 1) void k_gemmf(const GemmfArgs a) {
             if (m >= a.M) continue;
 #pragma unroll
             for (int g = 0; g < NG; g += (EPI == EPI_SWIGLU ? 2 : 1))
-                gf_out<EPI>(a, m, (nt * 4 + wc) * NG + g, lane, acc[i][g], acc[i][EPI == EPI_SWIGLU ? g + 1 : g]);
+                gf_out<EPI, WF>(a, m, (nt * 4 + wc) * NG + g, lane, acc[i][g], acc[i][EPI == EPI_SWIGLU ? g + 1 : g]);
         }
     }
 }
@@ -403,18 +468,18 @@ int g_gemmf_order = -1;  // 1 = column-tile-major unit order (a weight tile's ro
 // QKV / wo equal; M = 1024 W1|W3 54.5 -> 48.4 us.  Three planes keep 8 (24 chunks a stage).
 int g_gemmf_wr = -1;
 
-template <int EPI, int NP, int RB, int NG, int WR>
+template <int EPI, int NP, int RB, int NG, int WR, int WF = WF_BF16>
 static hipError_t gemmf_launch(const GemmfArgs& a, int G, hipStream_t st) {
-    using C = GfCfg<NP, RB, NG, WR>;
+    using C = GfCfg<NP, RB, NG, WR, WF>;
     static bool attr = false;
     const size_t lds = (size_t)3 * C::SLOT * 2 + 16;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemmf<EPI, NP, RB, NG, WR>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemmf<EPI, NP, RB, NG, WR, WF>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    hipLaunchKernelGGL((k_gemmf<EPI, NP, RB, NG, WR>), dim3(G), dim3(256 * WR), lds, st, a);
+    hipLaunchKernelGGL((k_gemmf<EPI, NP, RB, NG, WR, WF>), dim3(G), dim3(256 * WR), lds, st, a);
     return hipGetLastError();
 }
 
@@ -469,7 +534,7 @@ bool gemmf_ok(int M, int N, int K) { return M > 0 && M <= 1024 && K % 64 == 0 &&
 
 hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const void* Wf, int N, const float* bias,
                         float* C, int ldc, uint16_t* xo, float* ws, size_t ws_floats, int* flags, int epoch,
-                        hipStream_t st, const int* epoch_dev, int rb) {
+                        hipStream_t st, const int* epoch_dev, int rb, const float* wscale) {
     // tiles: 128 x 128 with two planes; 64 x 128 with three (a 3-slot ring of 8 row blocks'
     // three planes would not fit the 160 KB of LDS); 16 waves with two planes (g_gemmf_wr),
     // 8 with three
@@ -493,7 +558,7 @@ hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const
     const int t8 = ((M + 127) / 128) * (N / (64 * NG));
     const int RB = np == 3 ? 4 : g_gemmf_rb ? g_gemmf_rb : rb ? rb : (t8 >= gemmf_grid() ? 8 : 4);
     GemmfArgs a;
-    a.xs = xs; a.K = K; a.M = M; a.W = static_cast<const uint8_t*>(Wf); a.N = N; a.bias = bias; a.C = C; a.ldc = ldc;
+    a.xs = xs; a.K = K; a.M = M; a.W = static_cast<const uint8_t*>(Wf); a.N = N; a.wscale = wscale; a.bias = bias; a.C = C; a.ldc = ldc;
     a.xo = xo; a.ws = ws; a.flags = flags; a.epoch = epoch; a.epoch_dev = epoch_dev;
     a.recomputes = flags + gemmf_grid();  // the counter past the flags (gemmf_flag_ints())
     a.wait_ticks = g_gemmf_wait;
@@ -530,9 +595,14 @@ hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const
     if ((long long)G * minu > a.U) G = (int)std::max(1LL, a.U / minu);
     // one partial tile per block: (4 WR waves) x (RB / WR) x NGx x 64 lanes x 4 floats
     if ((size_t)G * 4 * RB * NGx * 256 > ws_floats) return hipErrorInvalidConfiguration;  // workspace too small
+    // int8 fragments (wscale): 8 waves with either plane count -- a stage's 8 weight chunks do not
+    // split over 16 (WR does not change a bit: the same unit ranges and summation order)
 #define GF_EPI(E)                                                                               \
     if (epi == E)                                                                               \
-        return np == 3 ? gemmf_launch<E, 3, 4, NG, WR>(a, G, st)                                \
+        return wscale ? (np == 3   ? gemmf_launch<E, 3, 4, NG, WR, WF_Q8>(a, G, st)             \
+                         : RB == 8 ? gemmf_launch<E, 2, 8, NG, WR, WF_Q8>(a, G, st)             \
+                                   : gemmf_launch<E, 2, 4, NG, WR, WF_Q8>(a, G, st))            \
+               : np == 3 ? gemmf_launch<E, 3, 4, NG, WR>(a, G, st)                              \
                : g_gemmf_wr == 4 ? (RB == 8 ? gemmf_launch<E, 2, 8, NG, 4>(a, G, st)             \
                                             : gemmf_launch<E, 2, 4, NG, 4>(a, G, st))            \
                : RB == 8 ? gemmf_launch<E, 2, 8, NG, WR>(a, G, st) : gemmf_launch<E, 2, 4, NG, WR>(a, G, st);

@@ -330,7 +330,7 @@ constexpr int SKX_TICKETS = 4 * 1024;
 // mx4: SKX_PRO_SCALE / SKX_EPI_SWIGLU only (the batched decode step's W1|W3)
 hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const void* Wf, int N, int nb,
                             const SklFused& f, hipStream_t st, int mx4 = 0);
-// k_gemmf (vox_hip_gemmf.hip): stream-K MFMA GEMM, planes x fragment-major bf16 weights;
+// k_gemmf (vox_hip_gemmf.hip): stream-K MFMA GEMM, planes x fragment-major bf16 (or int8) weights;
 // epi in {STORE, RESID, GELU, GELU_ERF, SWIGLU}; SWIGLU with xo writes the gate rows as
 // planes [rb][3][16][N / 2].  ws: gemmf_ws_floats(gemmf_grid()) floats of partial tiles,
 // flags: gemmf_grid() ints (zeroed once), epoch: > 0, new for every launch on the stream.
@@ -341,10 +341,12 @@ int set_gemmf_wait(int ticks); // owner's wait per partial in 100 MHz ticks (< 0
 size_t gemmf_ws_floats(int blocks);
 // epoch_dev (null: none): a device word added to `epoch` by the kernel, so that a captured launch
 // hands off under a new epoch at every replay (launch_gemmf_epoch_bump advances the word);
-// rb: row blocks per tile with two planes (0: by shape; 4 or 8)
+// rb: row blocks per tile with two planes (0: by shape; 4 or 8); wscale (null: Wf is the bf16
+// fragment copy): the [N] row scales of Wf = the int8 fragment copy (k_frag_pack<1>), applied
+// to the finished sums before the epilogue (the WF_Q8 instances; same tiles, grid and order)
 hipError_t launch_gemmf(int epi, int np, const uint16_t* xs, int K, int M, const void* Wf, int N, const float* bias,
                         float* C, int ldc, uint16_t* xo, float* ws, size_t ws_floats, int* flags, int epoch,
-                        hipStream_t st, const int* epoch_dev = nullptr, int rb = 0);
+                        hipStream_t st, const int* epoch_dev = nullptr, int rb = 0, const float* wscale = nullptr);
 // *epoch_dev += by (back to 1 before the sum could overflow): the last kernel of a captured step
 hipError_t launch_gemmf_epoch_bump(int* epoch_dev, int by, hipStream_t st);
 // row blocks per tile of the wide step's projections with two planes (profiles/batch_wide_kbench.txt)

@@ -2704,16 +2704,6 @@ __global__ __launch_bounds__(256) void k_split_fplanes(const float* __restrict__
     *reinterpret_cast<uint4*>(xs + frag_at(j, K, 2, k)) = make_uint4(lp[0], lp[1], lp[2], lp[3]);
 }
 
-__device__ __forceinline__ bf16x8 i8x8_bf16(uint32_t lo, uint32_t hi) {
-    uint32_t h[8];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        h[b] = __float_as_uint(i8f(lo, b)) >> 16;
-        h[4 + b] = __float_as_uint(i8f(hi, b)) >> 16;
-    }
-    return __builtin_bit_cast(bf16x8, make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)));
-}
-
 // e2m1 nibbles of one dword (weight k in bits 4k .. 4k + 3, vox_wmx4.h) times the block scale
 // 2^(byte - 127), given as the f32 byte << 23: four v_cvt_scalef32_pk_bf16_fp4, one per byte.
 // An e2m1 value times a power of two inside the wmx4 window is exactly a bf16, so the result

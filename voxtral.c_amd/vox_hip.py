@@ -127,6 +127,7 @@ EXPORTS = [
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
     "vox_hip_skinny_wmx4",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
+    "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
     "vox_hip_stream_adapter_tokens", "vox_hip_stream_read_adapter", "vox_hip_stream_decode",
@@ -179,6 +180,9 @@ def lib():
         "vox_hip_skinny_wmx4": (I, [I, I, P, fp, I, fp, I, I]),
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
+        "vox_hip_set_gemmf_q8": (I, [I]), "vox_hip_gemmf_q8": (I, []),
+        "vox_hip_model_gemmf_q8_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_gemmf_q8_rows": (I, [I, I, I, fp, P, fp, fp, I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
         "vox_hip_stream_reset": (I, [P]), "vox_hip_stream_reset_decoder": (I, [P]),
         "vox_hip_stream_encode_mel": (I, [P, P, I, I]),
@@ -323,6 +327,31 @@ def set_gemmf_wait(ticks: int) -> int:
     return lib().vox_hip_set_gemmf_wait(int(ticks))
 
 
+def set_gemmf_q8(on: bool):
+    """k_gemmf over the int8 fragment copies of Q8 tensors, for models created from now on
+    (vox_hip_set_gemmf_q8; off by default, VOX_HIP_GEMMF_Q8=1 gives the initial value)"""
+    if lib().vox_hip_set_gemmf_q8(int(bool(on))) != 0:
+        _err("set_gemmf_q8")
+
+
+def gemmf_q8() -> int:
+    return lib().vox_hip_gemmf_q8()
+
+
+def gemmf_q8_rows(x, W_i8, scales, fmt: int) -> np.ndarray:
+    """Test entry: y [M, N] = x [M, K] against the Q8 matrix (W int8 [N, K], scales f32 [N])
+    through the plane writer and k_gemmf (vox_hip_gemmf_q8_rows).  fmt 1: the int8 fragment copy
+    with the scales; fmt 0: the bf16 fragment copy of the same integers, unscaled"""
+    init()
+    W, sc, xv, N, K = _q8_args(W_i8, scales, x)
+    assert xv.ndim == 2
+    M = xv.shape[0]
+    y = np.empty((M, N), np.float32)
+    if lib().vox_hip_gemmf_q8_rows(M, N, K, fptr(xv), W.ctypes.data, fptr(sc), fptr(y), int(fmt)) != 0:
+        _err("gemmf_q8_rows")
+    return y
+
+
 def init(device: int | None = None):
     L = lib()
     if device is not None and L.vox_hip_set_device(device) != 0:
@@ -387,6 +416,15 @@ class Model:
         if lib().vox_hip_model_wmx4_batch_stats(self.h, out) != 0:
             _err("wmx4_batch_stats")
         return dict(zip(("tensors", "plane_bytes", "bf16_bytes", "host_us"), (int(v) for v in out)))
+
+    def gemmf_q8_stats(self) -> list:
+        """vox_hip_model_gemmf_q8_stats: [the switch the model took, k_gemmf launches on int8
+        fragments since creation (captured ones once at capture and once per replay), Q8 matrices
+        k_gemmf accepts, Q8 matrices whose shape it refuses]"""
+        out = (ctypes.c_longlong * 4)()
+        if lib().vox_hip_model_gemmf_q8_stats(self.h, out) != 0:
+            _err("gemmf_q8_stats")
+        return [int(v) for v in out]
 
     def ada_scale(self):
         c = self.cfg
