@@ -48,6 +48,12 @@ static int set_err(const char* fmt, ...) {
     return -1;
 }
 
+// a switch of the form "unset or anything but 0 means on"; the callers read theirs once per process
+static int env_on(const char* name) {
+    const char* e = getenv(name);
+    return (e && atoi(e) == 0) ? 0 : 1;
+}
+
 #define CK(expr)                                                                          \
     do {                                                                                  \
         hipError_t e__ = (expr);                                                          \
@@ -1344,11 +1350,7 @@ static bool enc_skinny_ok(const vox_hip_config_t& c) {
 }
 
 static int enc_fused_env() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VOX_HIP_ENC_FUSED");
-        v = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v = env_on("VOX_HIP_ENC_FUSED");
     return v;
 }
 
@@ -1467,11 +1469,7 @@ static int run_encoder_rows_skinny(vox_hip_stream_t* s, float* x, int n, long lo
 // inputs written as planes by the producers (RMSNorm rows, the attention output, the W1|W3
 // SwiGLU epilogue), so no GEMM re-splits f32 activations per column tile.
 static int enc_gemmf_env() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VOX_HIP_GEMMF");
-        v = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v = env_on("VOX_HIP_GEMMF");
     return v;
 }
 
@@ -1493,8 +1491,16 @@ static bool enc_gemmf_ok(const vox_hip_model_t* m, int n) {
            ED <= 4 * 512;
 }
 
-// one k_gemmf launch on queue st with its split workspace, partial-tile flags and epoch
-// counter (a queue's own: two k_gemmf launches in flight on two queues must not share flags)
+// k_gemmf launches on queue st with their split workspace, partial-tile flags and hand-off
+// epochs (a queue's own: two k_gemmf launches in flight on two queues must not share flags).
+// Two epoch disciplines:
+//   epoch_dev == null: *epoch is a host counter baked into each launch.  A captured (replayed)
+//     k_gemmf would reuse it and read stale partial tiles, so capture is refused.
+//   epoch_dev != null (the wide batched step): *epoch is the launch's index within the step, the
+//     kernel adds the device word, and the step's last kernel advances the word past the indices
+//     (launch_gemmf_epoch_bump), so the launches may be captured and replayed.  Tiles by
+//     gemmf_wide_rb; step_q8 counts the step's launches on int8 fragments (batch_run multiplies
+//     it by the replays).
 struct GemmfQ {
     hipStream_t st;
     float* ws;
@@ -1502,73 +1508,145 @@ struct GemmfQ {
     int* flags;
     int* epoch;
     long long* n_q8;  // the model's count of launches on int8 fragments
+    const int* epoch_dev;
+    int* step_q8;
 };
 
 // W: the tensor's fragment-major copy, int8 where wscale (its Q8 row scales) is set
 static int gemmf_on(const GemmfQ& q, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, const float* wscale,
                     int N, const float* bias, float* C, int ldc, uint16_t* xo) {
-    // the hand-off epoch is a host counter baked into the launch: a captured (replayed)
-    // k_gemmf would reuse it and read stale partial tiles, so capture is refused
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    CK(hipStreamIsCapturing(q.st, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err("k_gemmf launch while the stream is capturing");
+    if (!q.epoch_dev) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        CK(hipStreamIsCapturing(q.st, &cs));
+        if (cs != hipStreamCaptureStatusNone) return set_err("k_gemmf launch while the stream is capturing");
+    }
     if (++*q.epoch <= 0) *q.epoch = 1;
     // the launcher's shape / workspace checks, reported with the shape (launch_gemmf has one
-    // error code for all of them), and an error an earlier unchecked call left pending (the
-    // launcher's hipGetLastError would report it as this launch's)
+    // error code for all of them)
     if (!gemmf_ok(n, N, K) || !q.ws || !q.flags)
         return set_err("k_gemmf: unsupported shape M %d N %d K %d (ws %p flags %p)", n, N, K, (void*)q.ws, (void*)q.flags);
-    {
+    if (!q.epoch_dev) {
+        // an error an earlier unchecked call left pending (the launcher's hipGetLastError would
+        // report it as this launch's); not where the launch may be inside a capture, which gets
+        // no HIP call but the launch itself
         const hipError_t pend = hipGetLastError();
         if (pend != hipSuccess) return set_err("k_gemmf: HIP error pending before the launch: %s", hipGetErrorString(pend));
     }
     CK(launch_gemmf(epi, gemm_planes_np(), xs, K, n, W, N, bias, C, ldc, xo, q.ws, q.ws_n, q.flags, *q.epoch, q.st,
-                    nullptr, 0, wscale));
-    if (wscale) ++*q.n_q8;
+                    q.epoch_dev, q.epoch_dev ? gemmf_wide_rb(n, N, K) : 0, wscale));
+    if (wscale) {
+        ++*q.n_q8;
+        if (q.step_q8) ++*q.step_q8;
+    }
     return 0;
 }
 
-static int gemmf(vox_hip_stream_t* s, int epi, const uint16_t* xs, int K, int n, const uint8_t* W, const float* wscale,
-                 int N, const float* bias, float* C, int ldc, uint16_t* xo) {
-    return gemmf_on(GemmfQ{s->st, s->gws, s->gws_n, s->gflags, &s->gepoch, &s->m->n_gemmf_q8}, epi, xs, K, n, W, wscale,
-                    N, bias, C, ldc, xo);
+// a stream's own queue, workspace, flags and host epoch counter
+static GemmfQ stream_gemmfq(vox_hip_stream_t* s) {
+    return GemmfQ{s->st, s->gws, s->gws_n, s->gflags, &s->gepoch, &s->m->n_gemmf_q8, nullptr, nullptr};
 }
 
-static int run_encoder_rows_gemmf(vox_hip_stream_t* s, float* x, int n, long long pos0, const float* rope) {
-    vox_hip_model_t* m = s->m;
-    const vox_hip_config_t& c = m->c;
-    const int ED = c.enc_dim, H = c.enc_heads, KVH = c.enc_kv_heads, hd = c.enc_head_dim;
-    const int EQ = H * hd, EKV = KVH * hd, EH = c.enc_hidden, NQKV = EQ + 2 * EKV;
-    const float scale = 1.0f / sqrtf((float)hd);
-    hipStream_t st = s->st;
-    if (model_enc_frag(m)) return -1;
+// ---------------------------------------------------------------------------
+// The transformer layers of a pass of M > 1 rows, for every caller: encoder
+// passes of one stream and of several, decoder prefills of one stream and of several, and the
+// wide batched step.  rows_layers is the one place the launch sequence is written.
+// ---------------------------------------------------------------------------
+// One layer's tensors.  f*: the fragment-major copies (null until model_enc_frag / model_frag);
+// s*: Q8 row scales (null: bf16); b*: biases (encoder; null in the decoder); ada: the layer's
+// ada scale row (decoder; null in the encoder).
+struct RowsLayer {
+    const uint8_t *wqkv, *wo, *w13, *w2;
+    const uint8_t *fqkv, *fo, *f13, *f2;
+    const float *sqkv, *so, *s13, *s2;
+    const float *bqkv, *bo, *b2;
+    const float *attn_norm, *ffn_norm, *ada;
+};
+struct RowsStack {
+    int D, Q, KV, hidden, layers;  // Q = heads x head_dim, KV = kv heads x head_dim
+    float eps;
+    RowsLayer (*layer)(const vox_hip_model_t* m, int l);
+};
+// The rows between the launches; the caller owns them.  xn, att, hid: the row-major form's
+// normalised rows, wo input and w2 input; pa, pc: the plane form's two plane buffers.
+struct RowsScratch {
+    float *x, *qkv, *xn, *att, *hid;
+    uint16_t *pa, *pc;
+};
+
+static RowsLayer enc_rows_layer(const vox_hip_model_t* m, int l) {
+    const EncLayerD& L = m->enc[l];
+    const DecFragD F = m->efrag.empty() ? DecFragD{} : m->efrag[l];
+    return RowsLayer{L.wqkv, L.wo, L.w13, L.w2, F.wqkv, F.wo, F.w13, F.w2, L.sqkv, L.so, L.s13, L.s2,
+                     L.bqkv, L.bo, L.b2, L.attn_norm, L.ffn_norm, nullptr};
+}
+static RowsLayer dec_rows_layer(const vox_hip_model_t* m, int l) {
+    const DecLayerD& L = m->dec[l];
+    const DecFragD F = m->dfrag.empty() ? DecFragD{} : m->dfrag[l];
+    return RowsLayer{L.wqkv, L.wo, L.w13, L.w2, F.wqkv, F.wo, F.w13, F.w2, L.sqkv, L.so, L.s13, L.s2,
+                     nullptr, nullptr, nullptr, L.attn_norm, L.ffn_norm, m->ada_scale + (size_t)l * m->c.dec_dim};
+}
+static RowsStack enc_rows_stack(const vox_hip_config_t& c) {
+    return RowsStack{c.enc_dim, c.enc_heads * c.enc_head_dim, c.enc_kv_heads * c.enc_head_dim, c.enc_hidden, c.enc_layers,
+                     c.enc_eps, enc_rows_layer};
+}
+static RowsStack dec_rows_stack(const vox_hip_config_t& c) {
+    return RowsStack{c.dec_dim, c.dec_heads * c.dec_head_dim, c.dec_kv_heads * c.dec_head_dim, c.dec_hidden, c.dec_layers,
+                     c.dec_eps, dec_rows_layer};
+}
+
+// Rows B.x[0..n) through the stack's layers in place, on queue q.st (encoder.c:562-684,
+// decoder.c:509-606).  gf: the projections on k_gemmf over the fragment-major copies, their inputs
+// written as planes by the producers (RMSNorm rows, the attention output, the W1|W3 SwiGLU
+// epilogue); otherwise on launch_gemm (k_gemm2) over the row-major tensors, the same arithmetic.
+// attn(l, planes): layer l's RoPE + K/V append + attention from B.qkv, its rows into B.att and /
+// or, planes != null, as the wo input planes.
+template <class Attn>
+static int rows_layers(const vox_hip_model_t* m, const RowsStack& S, const RowsScratch& B, const GemmfQ& q, bool gf, int n,
+                       Attn attn) {
+    const int D = S.D, NQKV = S.Q + 2 * S.KV, HID = S.hidden;
+    hipStream_t st = q.st;
+    for (int l = 0; l < S.layers; l++) {
+        const RowsLayer L = S.layer(m, l);
+        // RMSNorm, QKV (+ bias)
+        if (gf) {
+            CK(launch_rmsnorm_fplanes(B.x, n, D, L.attn_norm, nullptr, S.eps, B.pa, nullptr, 0, st));
+            if (gemmf_on(q, EPI_STORE, B.pa, D, n, L.fqkv, L.sqkv, NQKV, L.bqkv, B.qkv, NQKV, nullptr)) return -1;
+        } else {
+            CK(launch_rmsnorm_rows(B.x, D, B.xn, D, L.attn_norm, nullptr, n, D, S.eps, st));
+            CK(launch_gemm(EPI_STORE, 3, B.xn, D, L.wqkv, L.sqkv, D, n, NQKV, L.bqkv, B.qkv, NQKV, st, q.ws, q.ws_n));
+        }
+        if (attn(l, gf ? B.pa : nullptr)) return -1;
+        // wo (+ bias) residual; RMSNorm (x (1 + ada)), W1|W3 with SwiGLU, w2 (+ bias) residual
+        if (gf) {
+            if (gemmf_on(q, EPI_RESID, B.pa, S.Q, n, L.fo, L.so, D, L.bo, B.x, D, nullptr)) return -1;
+            CK(launch_rmsnorm_fplanes(B.x, n, D, L.ffn_norm, L.ada, S.eps, B.pa, nullptr, 0, st));
+            if (gemmf_on(q, EPI_SWIGLU, B.pa, D, n, L.f13, L.s13, 2 * HID, nullptr, nullptr, HID, B.pc)) return -1;
+            if (gemmf_on(q, EPI_RESID, B.pc, HID, n, L.f2, L.s2, D, L.b2, B.x, D, nullptr)) return -1;
+        } else {
+            CK(launch_gemm(EPI_RESID, 3, B.att, S.Q, L.wo, L.so, S.Q, n, D, L.bo, B.x, D, st, q.ws, q.ws_n));
+            CK(launch_rmsnorm_rows(B.x, D, B.xn, D, L.ffn_norm, L.ada, n, D, S.eps, st));
+            CK(launch_gemm(EPI_SWIGLU, 3, B.xn, D, L.w13, L.s13, D, n, 2 * HID, nullptr, B.hid, HID, st, q.ws, q.ws_n));
+            CK(launch_gemm(EPI_RESID, 3, B.hid, HID, L.w2, L.s2, HID, n, D, L.b2, B.x, D, st, q.ws, q.ws_n));
+        }
+    }
+    return 0;
+}
+
+// What a k_gemmf encoder pass on s's queue needs besides its row buffers: the fragment-major
+// encoder copies, the stream's plane buffers (one pass of ENC_SUB rows) and hand-off flags
+static int stream_enc_planes(vox_hip_stream_t* s) {
+    const vox_hip_config_t& c = s->m->c;
+    if (model_enc_frag(s->m)) return -1;
     if (!s->gpa) {
         const size_t rb = PLANE_MAX_ROWS / SK_ROWS;
-        CK(dalloc(&s->gpa, rb * 3 * SK_ROWS * std::max(ED, EQ)));
-        CK(dalloc(&s->gpc, rb * 3 * SK_ROWS * EH));
+        CK(dalloc(&s->gpa, rb * 3 * SK_ROWS * std::max(c.enc_dim, c.enc_heads * c.enc_head_dim)));
+        CK(dalloc(&s->gpc, rb * 3 * SK_ROWS * c.enc_hidden));
     }
     if (!s->gflags) CK(dalloc(&s->gflags, gemmf_flag_ints()));
-    for (int l = 0; l < c.enc_layers; l++) {
-        const EncLayerD& L = m->enc[l];
-        const DecFragD& F = m->efrag[l];
-        float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-        float* Vc = s->ev + (size_t)l * s->ecap * EKV;
-        // RMSNorm -> planes, QKV (+ bias), RoPE + K/V append (encoder.c:562-607)
-        CK(launch_rmsnorm_fplanes(x, n, ED, L.attn_norm, nullptr, c.enc_eps, s->gpa, nullptr, 0, st));
-        if (gemmf(s, EPI_STORE, s->gpa, ED, n, F.wqkv, L.sqkv, NQKV, L.bqkv, s->qkv, NQKV, nullptr)) return -1;
-        CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
-        // windowed attention, output as the wo input planes (encoder.c:609-638)
-        CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale, st,
-                             s->gws, s->gws_n, s->gpa));
-        // wo + bias residual (encoder.c:640-644)
-        if (gemmf(s, EPI_RESID, s->gpa, EQ, n, F.wo, L.so, ED, L.bo, x, ED, nullptr)) return -1;
-        // FFN RMSNorm -> planes, W1|W3 with SwiGLU into the w2 planes, w2 + bias residual (:646-684)
-        CK(launch_rmsnorm_fplanes(x, n, ED, L.ffn_norm, nullptr, c.enc_eps, s->gpa, nullptr, 0, st));
-        if (gemmf(s, EPI_SWIGLU, s->gpa, ED, n, F.w13, L.s13, 2 * EH, nullptr, nullptr, EH, s->gpc)) return -1;
-        if (gemmf(s, EPI_RESID, s->gpc, EH, n, F.w2, L.s2, ED, L.b2, x, ED, nullptr)) return -1;
-    }
-    CK(launch_rmsnorm_rows(x, ED, x, ED, m->enc_norm, nullptr, n, ED, c.enc_eps, st));
     return 0;
+}
+static RowsScratch enc_rows_scratch(vox_hip_stream_t* s, float* x) {
+    return RowsScratch{x, s->qkv, s->xn, s->att, s->gate, s->gpa, s->gpc};
 }
 
 // A single new encoder row (the 1-frame final chunk of a one-shot clip, a live stream's odd
@@ -1625,11 +1703,7 @@ static int run_encoder_row_gemv(vox_hip_stream_t* s, float* x, long long pos0, c
 }
 
 static int enc_skinny_env() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VOX_HIP_ENC_SKINNY");
-        v = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v = env_on("VOX_HIP_ENC_SKINNY");
     return v;
 }
 
@@ -1637,27 +1711,24 @@ static int run_encoder_rows(vox_hip_stream_t* s, float* x, int n, long long pos0
     vox_hip_model_t* m = s->m;
     const vox_hip_config_t& c = m->c;
     const int ED = c.enc_dim, H = c.enc_heads, KVH = c.enc_kv_heads, hd = c.enc_head_dim;
-    const int EQ = H * hd, EKV = KVH * hd, EH = c.enc_hidden;
+    const int EQ = H * hd, EKV = KVH * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = s->st;
     if (n > ENC_SUB) return set_err("encoder pass of %d rows > %d", n, ENC_SUB);
     if (n == 1 && enc_gemv_ok(m)) return run_encoder_row_gemv(s, x, pos0, rope);
     if (n <= enc_skinny_rows() && enc_skinny_env() && enc_skinny_ok(c)) return run_encoder_rows_skinny(s, x, n, pos0, rope);
-    if (enc_gemmf_ok(m, n)) return run_encoder_rows_gemmf(s, x, n, pos0, rope);
-    for (int l = 0; l < c.enc_layers; l++) {
-        const EncLayerD& L = m->enc[l];
-        float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-        float* Vc = s->ev + (size_t)l * s->ecap * EKV;
-        CK(launch_rmsnorm_rows(x, ED, s->xn, ED, L.attn_norm, nullptr, n, ED, c.enc_eps, st));
-        CK(launch_gemm(EPI_STORE, 3, s->xn, ED, L.wqkv, L.sqkv, ED, n, EQ + 2 * EKV, L.bqkv, s->qkv, EQ + 2 * EKV, st, s->gws, s->gws_n));
-        CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
-        CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale, st,
-                             s->gws, s->gws_n));
-        CK(launch_gemm(EPI_RESID, 3, s->att, EQ, L.wo, L.so, EQ, n, ED, L.bo, x, ED, st, s->gws, s->gws_n));
-        CK(launch_rmsnorm_rows(x, ED, s->xn, ED, L.ffn_norm, nullptr, n, ED, c.enc_eps, st));
-        CK(launch_gemm(EPI_SWIGLU, 3, s->xn, ED, L.w13, L.s13, ED, n, 2 * EH, nullptr, s->gate, EH, st, s->gws, s->gws_n));
-        CK(launch_gemm(EPI_RESID, 3, s->gate, EH, L.w2, L.s2, EH, n, ED, L.b2, x, ED, st, s->gws, s->gws_n));
-    }
+    const bool gf = enc_gemmf_ok(m, n);
+    if (gf && stream_enc_planes(s)) return -1;
+    // RoPE + K/V append (encoder.c:562-607), windowed attention (:609-638)
+    if (rows_layers(m, enc_rows_stack(c), enc_rows_scratch(s, x), stream_gemmfq(s), gf, n, [&](int l, uint16_t* planes) -> int {
+            float* Kc = s->ek + (size_t)l * s->ecap * EKV;
+            float* Vc = s->ev + (size_t)l * s->ecap * EKV;
+            CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
+            CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale,
+                                   st, s->gws, s->gws_n, planes));
+            return 0;
+        }))
+        return -1;
     CK(launch_rmsnorm_rows(x, ED, x, ED, m->enc_norm, nullptr, n, ED, c.enc_eps, st));
     return 0;
 }
@@ -1915,68 +1986,40 @@ static int enc_suffix_batch(vox_hip_stream_t* lead, const float* X, vox_hip_stre
 }
 
 // The 32 encoder layers over the stacked new rows of several streams (row block b = rows
-// [off[b], off[b] + nr[b]) of X belongs to ss[b], at its logical positions from pos0[b]):
-// RMSNorm and the four projections run once over all rows (every weight byte read once for
-// the batch), RoPE + K/V append and the windowed attention per stream against its own ring.
+// [off[b], off[b] + nr[b]) of X belongs to ss[b], at its logical positions from pos0[b]): one
+// rows_layers call over all rows (every weight byte read once for the batch) whose attention
+// step runs RoPE + K/V append and the windowed attention per stream against its own ring.
 // Launched on lead->st with lead's scratch (ENC_SUB rows); the caller orders the streams.
 static int run_encoder_rows_batch(vox_hip_stream_t* lead, float* X, int N, vox_hip_stream_t* const* ss,
                                   const int* off, const int* nr, const long long* pos0, int B) {
     vox_hip_model_t* m = lead->m;
     const vox_hip_config_t& c = m->c;
     const int ED = c.enc_dim, H = c.enc_heads, KVH = c.enc_kv_heads, hd = c.enc_head_dim;
-    const int EQ = H * hd, EKV = KVH * hd, EH = c.enc_hidden, NQKV = EQ + 2 * EKV;
+    const int EQ = H * hd, EKV = KVH * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = lead->st;
     const bool gf = enc_gemmf_ok(m, N);
-    if (gf) {
-        if (model_enc_frag(m)) return -1;
-        if (!lead->gpa) {
-            const size_t rb = PLANE_MAX_ROWS / SK_ROWS;
-            CK(dalloc(&lead->gpa, rb * 3 * SK_ROWS * std::max(ED, EQ)));
-            CK(dalloc(&lead->gpc, rb * 3 * SK_ROWS * EH));
-        }
-        if (!lead->gflags) CK(dalloc(&lead->gflags, gemmf_flag_ints()));
+    if (gf && stream_enc_planes(lead)) return -1;
+    EncRows er;
+    memset(&er, 0, sizeof er);
+    er.B = B;
+    for (int b = 0; b < B; b++) {
+        er.off[b] = off[b];
+        er.nr[b] = nr[b];
+        er.pos0[b] = (int)pos0[b];
     }
-    for (int l = 0; l < c.enc_layers; l++) {
-        const EncLayerD& L = m->enc[l];
-        if (gf) {
-            const DecFragD& F = m->efrag[l];
-            CK(launch_rmsnorm_fplanes(X, N, ED, L.attn_norm, nullptr, c.enc_eps, lead->gpa, nullptr, 0, st));
-            if (gemmf(lead, EPI_STORE, lead->gpa, ED, N, F.wqkv, L.sqkv, NQKV, L.bqkv, lead->qkv, NQKV, nullptr)) return -1;
-        } else {
-            CK(launch_rmsnorm_rows(X, ED, lead->xn, ED, L.attn_norm, nullptr, N, ED, c.enc_eps, st));
-            CK(launch_gemm(EPI_STORE, 3, lead->xn, ED, L.wqkv, L.sqkv, ED, N, NQKV, L.bqkv, lead->qkv, NQKV, st,
-                           lead->gws, lead->gws_n));
-        }
-        // every stream's RoPE + K/V append and attention in one launch each (row offsets)
-        EncRows er;
-        memset(&er, 0, sizeof er);
-        er.B = B;
-        for (int b = 0; b < B; b++) {
-            er.off[b] = off[b];
-            er.nr[b] = nr[b];
-            er.pos0[b] = (int)pos0[b];
-            er.Kc[b] = ss[b]->ek + (size_t)l * ss[b]->ecap * EKV;
-            er.Vc[b] = ss[b]->ev + (size_t)l * ss[b]->ecap * EKV;
-        }
-        CK(launch_rope_kv_rows(lead->qkv, N, EQ, EKV, hd, m->rope_enc, er, lead->q, lead->ecap, st));
-        // (k_gemmf's wo reads planes: the attention writes them itself)
-        CK(launch_attn_rows(hd, lead->q, er, N, lead->ecap, lead->att, H, KVH, c.enc_window, scale, lead->gws,
-                            lead->gws_n, st, gf ? lead->gpa : nullptr));
-        if (gf) {
-            const DecFragD& F = m->efrag[l];
-            if (gemmf(lead, EPI_RESID, lead->gpa, EQ, N, F.wo, L.so, ED, L.bo, X, ED, nullptr)) return -1;
-            CK(launch_rmsnorm_fplanes(X, N, ED, L.ffn_norm, nullptr, c.enc_eps, lead->gpa, nullptr, 0, st));
-            if (gemmf(lead, EPI_SWIGLU, lead->gpa, ED, N, F.w13, L.s13, 2 * EH, nullptr, nullptr, EH, lead->gpc)) return -1;
-            if (gemmf(lead, EPI_RESID, lead->gpc, EH, N, F.w2, L.s2, ED, L.b2, X, ED, nullptr)) return -1;
-        } else {
-            CK(launch_gemm(EPI_RESID, 3, lead->att, EQ, L.wo, L.so, EQ, N, ED, L.bo, X, ED, st, lead->gws, lead->gws_n));
-            CK(launch_rmsnorm_rows(X, ED, lead->xn, ED, L.ffn_norm, nullptr, N, ED, c.enc_eps, st));
-            CK(launch_gemm(EPI_SWIGLU, 3, lead->xn, ED, L.w13, L.s13, ED, N, 2 * EH, nullptr, lead->gate, EH, st,
-                           lead->gws, lead->gws_n));
-            CK(launch_gemm(EPI_RESID, 3, lead->gate, EH, L.w2, L.s2, EH, N, ED, L.b2, X, ED, st, lead->gws, lead->gws_n));
-        }
-    }
+    // every stream's RoPE + K/V append and attention in one launch each (row offsets)
+    if (rows_layers(m, enc_rows_stack(c), enc_rows_scratch(lead, X), stream_gemmfq(lead), gf, N, [&](int l, uint16_t* planes) -> int {
+            for (int b = 0; b < B; b++) {
+                er.Kc[b] = ss[b]->ek + (size_t)l * ss[b]->ecap * EKV;
+                er.Vc[b] = ss[b]->ev + (size_t)l * ss[b]->ecap * EKV;
+            }
+            CK(launch_rope_kv_rows(lead->qkv, N, EQ, EKV, hd, m->rope_enc, er, lead->q, lead->ecap, st));
+            CK(launch_attn_rows(hd, lead->q, er, N, lead->ecap, lead->att, H, KVH, c.enc_window, scale, lead->gws,
+                                lead->gws_n, st, planes));
+            return 0;
+        }))
+        return -1;
     CK(launch_rmsnorm_rows(X, ED, X, ED, m->enc_norm, nullptr, N, ED, c.enc_eps, st));
     return 0;
 }
@@ -2017,11 +2060,7 @@ extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, cons
     // several streams with rows: the conv stems stacked on the lead's queue (one GEMM per
     // conv for all of them, VOX_HIP_ENC_STEM_BATCH=0: one stream at a time), rows straight
     // into the stacked layer input
-    static int stem_batch = -1;
-    if (stem_batch < 0) {
-        const char* e = getenv("VOX_HIP_ENC_STEM_BATCH");
-        stem_batch = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int stem_batch = env_on("VOX_HIP_ENC_STEM_BATCH");
     const bool stacked = stem_batch && active > 1 && enc_prefix_batch_fits(ss, n, B);
     if (stacked) {
         if (!lead->xbatch) CK(dalloc(&lead->xbatch, (size_t)ENC_SUB * ED));
@@ -2146,11 +2185,7 @@ static int stream_prefilled(vox_hip_stream_t* s, hipStream_t q) {
 static int dec_gemmf_env() {
     // VOX_HIP_PREFILL_GEMMF=0: decoder prefills on k_gemm2 over the row-major weights (A/B, and
     // no fragment-major copies for a process that never batches)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VOX_HIP_PREFILL_GEMMF");
-        v = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v = env_on("VOX_HIP_PREFILL_GEMMF");
     return v;
 }
 
@@ -2179,81 +2214,86 @@ static int stream_dec_planes(vox_hip_stream_t* s, int rows) {
     return 0;
 }
 
-// the prefill layers of rows x[0..n) with planes / scratch of s on queue q; attn(l) runs the
-// layer's RoPE + K/V append + attention into s->attd
-template <class Attn>
-static int dec_layers_gemmf(vox_hip_stream_t* s, const GemmfQ& q, float* x, int n, Attn attn) {
-    vox_hip_model_t* m = s->m;
-    const vox_hip_config_t& c = m->c;
-    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim;
-    const int DH = c.dec_hidden;
-    if (model_frag(m) || stream_dec_planes(s, n)) return -1;
-    for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
-        const DecFragD& F = m->dfrag[l];
-        // RMSNorm -> planes, QKV (decoder.c:509-530)
-        CK(launch_rmsnorm_fplanes(x, n, DD, L.attn_norm, nullptr, c.dec_eps, s->dpa, nullptr, 0, q.st));
-        if (gemmf_on(q, EPI_STORE, s->dpa, DD, n, F.wqkv, L.sqkv, DQ + 2 * DKV, nullptr, s->qkvd, DQ + 2 * DKV, nullptr)) return -1;
-        // RoPE + K/V append + attention, its rows as the wo planes in s->dpa (attn's job)
-        if (attn(l)) return -1;
-        // wo + residual (decoder.c:552-560)
-        if (gemmf_on(q, EPI_RESID, s->dpa, DQ, n, F.wo, L.so, DD, nullptr, x, DD, nullptr)) return -1;
-        // RMSNorm * (1 + ada) -> planes, W1|W3 with SwiGLU into the w2 planes, w2 + residual (:562-606)
-        CK(launch_rmsnorm_fplanes(x, n, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, c.dec_eps, s->dpa, nullptr, 0,
-                                  q.st));
-        if (gemmf_on(q, EPI_SWIGLU, s->dpa, DD, n, F.w13, L.s13, 2 * DH, nullptr, nullptr, DH, s->dpc)) return -1;
-        if (gemmf_on(q, EPI_RESID, s->dpc, DH, n, F.w2, L.s2, DD, nullptr, x, DD, nullptr)) return -1;
-    }
-    return 0;
+// the decoder rows of a pass led by s (its prefill scratch and planes), residual rows x
+static RowsScratch dec_rows_scratch(vox_hip_stream_t* s, float* x) {
+    return RowsScratch{x, s->qkvd, s->xnd, s->attd, s->gated, s->dpa, s->dpc};
 }
 
 // M>1 rows (prefill) at logical positions pos0.. (voxtral_decoder.c:496-606)
 static int run_decoder_rows(vox_hip_stream_t* s, float* x, int n, int pos0, const float* rope) {
     vox_hip_model_t* m = s->m;
     const vox_hip_config_t& c = m->c;
-    const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
-    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
+    const int H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
+    const int DQ = H * hd, DKV = KVH * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = s->st;
     if (stream_alloc_dec_rows(s, n)) return -1;
     if (n > DEC_SLACK + 1 && pos0 > 0) return set_err("prefill of %d rows on a non-empty cache", n);
     // k_gemmf needs the fragment-major decoder copies (6.86 GB, made here on the first
     // prefill unless a batch made them) and the stream's plane buffers; when either cannot be
-    // allocated the prefill takes the k_gemm2 layers below (same arithmetic, row-major weights)
+    // allocated the prefill takes the k_gemm2 form (same arithmetic, row-major weights)
     bool gf = n > 1 && dec_gemmf_ok(m, n);
     if (gf && (model_frag(m) || stream_dec_planes(s, n))) {
         vox_hip_clear_error();
         (void)hipGetLastError();  // the failed hipMalloc, so no later launch check reports it
         gf = false;
     }
-    if (gf) {
-        // the hand-off flags before the queue descriptor copies the pointer (a stream whose
-        // encoder never ran a k_gemmf pass has none yet)
-        if (!s->gflags) CK(dalloc(&s->gflags, gemmf_flag_ints()));
-        return dec_layers_gemmf(s, GemmfQ{st, s->gws, s->gws_n, s->gflags, &s->gepoch, &m->n_gemmf_q8}, x, n, [&](int l) -> int {
-            float* Kc = dec_ring(s, s->dk, l);
-            float* Vc = dec_ring(s, s->dv, l);
-            CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kvt));
-            CK(launch_attn_rows_mf(hd, s->qd_, DQ, Kc, Vc, s->dcap, s->attd, DQ, n, H, KVH, pos0, 0, c.dec_window, scale,
-                                   st, s->gws, s->gws_n, s->dpa, s->kvt));
-            return 0;
-        });
-    }
-    for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
+    // (stream_dec_planes made the hand-off flags before the queue descriptor copies the pointer)
+    return rows_layers(m, dec_rows_stack(c), dec_rows_scratch(s, x), stream_gemmfq(s), gf, n, [&](int l, uint16_t* planes) -> int {
         float* Kc = dec_ring(s, s->dk, l);
         float* Vc = dec_ring(s, s->dv, l);
-        CK(launch_rmsnorm_rows(x, DD, s->xnd, DD, L.attn_norm, nullptr, n, DD, c.dec_eps, st));
-        CK(launch_gemm(EPI_STORE, 3, s->xnd, DD, L.wqkv, L.sqkv, DD, n, DQ + 2 * DKV, nullptr, s->qkvd, DQ + 2 * DKV, st, s->gws, s->gws_n));
         CK(launch_rope_kv(s->qkvd, n, DQ, DKV, hd, rope, pos0, s->qd_, Kc, Vc, s->dcap, st, s->kvt));
         CK(launch_attn_rows_mf(hd, s->qd_, DQ, Kc, Vc, s->dcap, s->attd, DQ, n, H, KVH, pos0, 0, c.dec_window, scale, st,
-                             s->gws, s->gws_n, nullptr, s->kvt));
-        CK(launch_gemm(EPI_RESID, 3, s->attd, DQ, L.wo, L.so, DQ, n, DD, nullptr, x, DD, st, s->gws, s->gws_n));
-        CK(launch_rmsnorm_rows(x, DD, s->xnd, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, n, DD, c.dec_eps, st));
-        CK(launch_gemm(EPI_SWIGLU, 3, s->xnd, DD, L.w13, L.s13, DD, n, 2 * DH, nullptr, s->gated, DH, st, s->gws, s->gws_n));
-        CK(launch_gemm(EPI_RESID, 3, s->gated, DH, L.w2, L.s2, DH, n, DD, nullptr, x, DD, st, s->gws, s->gws_n));
+                               s->gws, s->gws_n, planes, s->kvt));
+        return 0;
+    });
+}
+
+// The tensors a decode step streams (single-stream k_gemv and the R-row k_gemvr step): QKV, wo,
+// W1|W3 and W2 of layer l, and the LM head (tied embeddings) as l == layers.  The one place that
+// says what each is: matrix and Q8 scales, (rows, K), prologue / epilogue, norm weight and ada
+// row, wpack13 and wmx4 planes.  The LM head's epilogue here is the batched steps' EPI_STORE; the
+// single-stream step launches it with EPI_LOGITS[_ALT].
+enum { T_QKV, T_WO, T_W13, T_W2 };
+struct StepTensor {
+    const uint8_t* W;
+    const float* wscale;
+    int rows, K, pro, epi;
+    const float *norm_w, *ada;
+    const WPackD* pack;
+    const WMx4D* mx;
+};
+static StepTensor dec_step_tensor(const vox_hip_model_t* m, int l, int which) {
+    const vox_hip_config_t& c = m->c;
+    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
+    if (l == (int)m->dec.size())
+        return StepTensor{m->tok_emb, m->tok_emb_s, c.vocab, DD, PRO_NORM, EPI_STORE, m->dec_norm, nullptr, &m->plm, &m->mlm};
+    const DecLayerD& L = m->dec[l];
+    switch (which) {
+    case T_QKV: return StepTensor{L.wqkv, L.sqkv, DQ + 2 * DKV, DD, PRO_NORM, EPI_QKV, L.attn_norm, nullptr, &L.pqkv, &L.mqkv};
+    case T_WO: return StepTensor{L.wo, L.so, DD, DQ, PRO_NONE, EPI_RESID, nullptr, nullptr, &L.po, &L.mo};
+    case T_W13:
+        return StepTensor{L.w13, L.s13, 2 * DH, DD, PRO_NORM_ADA, EPI_SWIGLU, L.ffn_norm, m->ada_scale + (size_t)l * DD,
+                          &L.p13, &L.m13};
+    default: return StepTensor{L.w2, L.s2, DD, DH, PRO_NONE, EPI_RESID, nullptr, nullptr, &L.p2, &L.m2};
     }
-    return 0;
+}
+// f(tensor) over the 4 tensors of every layer and the LM head, until one returns false
+template <class F>
+static bool all_step_tensors(const vox_hip_model_t* m, F f) {
+    const int nl = (int)m->dec.size();
+    for (int l = 0; l <= nl; l++)
+        for (int w = 0; w < (l < nl ? 4 : 1); w++)
+            if (!f(dec_step_tensor(m, l, w))) return false;
+    return true;
+}
+// a zeroed GemvArgs with the tensor's own fields: y = epi(W pro(x)); wmx4: its wmx4 plane, if any
+static void step_tensor_args(GemvArgs& a, const StepTensor& t, const float* x, float* y, float eps, int wmx4) {
+    memset(&a, 0, sizeof a);
+    a.x = x; a.K = t.K; a.W = t.W; a.wscale = t.wscale; a.rows = t.rows; a.y = y;
+    a.norm_w = t.norm_w; a.ada = t.ada; a.eps = t.norm_w ? eps : 0.f;
+    wpack_args(a, *t.pack);
+    if (wmx4) wmx4_args(a, *t.mx);
 }
 
 // One decoder step for the token whose input is already in s->xd[0..D).
@@ -2265,51 +2305,39 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
                                int splits) {
     vox_hip_model_t* m = s->m;
     const vox_hip_config_t& c = m->c;
-    const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
-    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
+    const int H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = s->st;
     for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
         float* Kc = dec_ring(s, s->dk, l);
         float* Vc = dec_ring(s, s->dv, l);
         GemvArgs a;
-        memset(&a, 0, sizeof a);
         // norm -> QKV -> RoPE -> KV append (decoder.c:709-722)
-        a.x = s->xd; a.K = DD; a.W = L.wqkv; a.wscale = L.sqkv; a.rows = DQ + 2 * DKV;
-        a.norm_w = L.attn_norm; a.eps = c.dec_eps; a.y = s->qd_;
-        a.qd = DQ; a.kvd = DKV; a.hd = hd;
+        StepTensor t = dec_step_tensor(m, l, T_QKV);
+        step_tensor_args(a, t, s->xd, s->qd_, c.dec_eps, 1);
+        a.qd = H * hd; a.kvd = KVH * hd; a.hd = hd;
         a.state = state; a.pos = pos;
         a.rope = state ? m->rope_dec : rope_row - (size_t)pos * hd;
         a.Kc = Kc; a.Vc = Vc; a.cap = s->dcap; a.kvt = s->kvt;
-        wpack_args(a, L.pqkv);
-        wmx4_args(a, L.mqkv);
-        CK(launch_gemv(PRO_NORM, EPI_QKV, a, st));
+        CK(launch_gemv(t.pro, t.epi, a, st));
         // attention over the last min(pos+1, window) keys (decoder.c:724-733)
         CK(launch_attn_decode(hd, s->qd_, Kc, Vc, s->dcap, state, pos, c.dec_window, scale, H, KVH,
                               s->part, s->attd, splits, st, s->kvt));
         // wo + residual (decoder.c:735-740)
-        memset(&a, 0, sizeof a);
-        a.x = s->attd; a.K = DQ; a.W = L.wo; a.wscale = L.so; a.rows = DD; a.y = s->xd;
-        wpack_args(a, L.po);
-        wmx4_args(a, L.mo);
-        CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
+        t = dec_step_tensor(m, l, T_WO);
+        step_tensor_args(a, t, s->attd, s->xd, c.dec_eps, 1);
+        CK(launch_gemv(t.pro, t.epi, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up (decoder.c:742-758)
-        memset(&a, 0, sizeof a);
-        a.x = s->xd; a.K = DD; a.W = L.w13; a.wscale = L.s13; a.rows = 2 * DH; a.norm_w = L.ffn_norm;
-        a.ada = m->ada_scale + (size_t)l * DD; a.eps = c.dec_eps; a.y = s->gated;
-        wpack_args(a, L.p13);
-        wmx4_args(a, L.m13);
+        t = dec_step_tensor(m, l, T_W13);
+        step_tensor_args(a, t, s->xd, s->gated, c.dec_eps, 1);
         // profiling: HIP events recorded by the W1|W3 launch's own dispatch (eager steps)
         const bool gprof = s->profiling && state && !s->capturing && (int)s->pev.size() == 2 * c.dec_layers;
-        if (gprof) CK(launch_gemv_timed(PRO_NORM_ADA, EPI_SWIGLU, a, s->pev[2 * l], s->pev[2 * l + 1], st));
-        else CK(launch_gemv(PRO_NORM_ADA, EPI_SWIGLU, a, st));
+        if (gprof) CK(launch_gemv_timed(t.pro, t.epi, a, s->pev[2 * l], s->pev[2 * l + 1], st));
+        else CK(launch_gemv(t.pro, t.epi, a, st));
         // W2 + residual (decoder.c:758-760)
-        memset(&a, 0, sizeof a);
-        a.x = s->gated; a.K = DH; a.W = L.w2; a.wscale = L.s2; a.rows = DD; a.y = s->xd;
-        wpack_args(a, L.p2);
-        wmx4_args(a, L.m2);
-        CK(launch_gemv(PRO_NONE, EPI_RESID, a, st));
+        t = dec_step_tensor(m, l, T_W2);
+        step_tensor_args(a, t, s->gated, s->xd, c.dec_eps, 1);
+        CK(launch_gemv(t.pro, t.epi, a, st));
     }
     return enqueue_lm_head(s, state);
 }
@@ -2317,16 +2345,12 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
 // final norm + LM head (tied embeddings) + argmax partials (decoder.c:762-779)
 static int enqueue_lm_head(vox_hip_stream_t* s, const int* state) {
     vox_hip_model_t* m = s->m;
-    const vox_hip_config_t& c = m->c;
-    hipStream_t st = s->st;
+    const StepTensor t = dec_step_tensor(m, m->c.dec_layers, 0);
     GemvArgs a;
-    memset(&a, 0, sizeof a);
-    a.x = s->xd; a.K = c.dec_dim; a.W = m->tok_emb; a.wscale = m->tok_emb_s; a.rows = c.vocab; a.norm_w = m->dec_norm;
-    a.eps = c.dec_eps; a.y = s->logits; a.part_val = s->pval; a.part_idx = s->pidx;
+    step_tensor_args(a, t, s->xd, s->logits, m->c.dec_eps, 1);
+    a.part_val = s->pval; a.part_idx = s->pidx;
     a.part_alt = s->part_alt;
-    wpack_args(a, m->plm);
-    wmx4_args(a, m->mlm);
-    CK(launch_gemv(PRO_NORM, (state && s->n_alt > 1) ? EPI_LOGITS_ALT : EPI_LOGITS, a, st));
+    CK(launch_gemv(t.pro, (state && s->n_alt > 1) ? EPI_LOGITS_ALT : EPI_LOGITS, a, s->st));
     return 0;
 }
 
@@ -2392,11 +2416,7 @@ static int collect_graph_profile(vox_hip_stream_t* s) {
 }
 
 static int use_graphs() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VOX_HIP_GRAPH");
-        v = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v = env_on("VOX_HIP_GRAPH");
     return v;
 }
 
@@ -3581,11 +3601,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
     CK(launch_rmsnorm_fplanes(b->x, nb, DD, m->dec_norm, nullptr, c.dec_eps, b->xp_d, b->part, Sres, st));
     // 17..32 rows: both 16-row blocks in one k_skf launch (the embeddings read once;
     // VOX_HIP_SKF2=0: one launch per 16-row block)
-    static int skf2 = -1;
-    if (skf2 < 0) {
-        const char* e = getenv("VOX_HIP_SKF2");
-        skf2 = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int skf2 = env_on("VOX_HIP_SKF2");
     const uint8_t* mlm = mx(m->mlm);
     const void* lmw = mlm ? mlm : m->lm_frag;
     if (skf2 && nb > SK_ROWS)
@@ -3609,7 +3625,6 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
 // before and after either step, so the two may alternate from one call to the next.
 static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4) {
     vox_hip_model_t* m = b->m;
-    auto mx = [&](GemvArgs& g, const WMx4D& M) { if (wmx4) wmx4_args(g, M); };
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
@@ -3626,81 +3641,58 @@ static int batch_step_gemv(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
         ap.out[i] = b->att + (size_t)i * DQ;
     }
     GemvRArgs a;
+    // a = tensor t over the nb rows x (row stride ldx) into y (ldy)
+    auto fill = [&](const StepTensor& t, const float* x, int ldx, float* y, int ldy) {
+        memset(&a, 0, sizeof a);
+        step_tensor_args(a.g, t, x, y, c.dec_eps, wmx4);
+        a.ldx = ldx; a.ldy = ldy;
+    };
     for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
         ap.ring_off = (size_t)l * ring_layer;
         // norm -> QKV -> RoPE -> KV append of every live slot
-        memset(&a, 0, sizeof a);
-        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.wqkv; a.g.wscale = L.sqkv; a.g.rows = DQ + 2 * DKV;
-        a.g.norm_w = L.attn_norm; a.g.eps = c.dec_eps; a.g.y = b->q; a.ldy = DQ;
+        StepTensor t = dec_step_tensor(m, l, T_QKV);
+        fill(t, b->x, DD, b->q, DQ);
         a.g.qd = DQ; a.g.kvd = DKV; a.g.hd = hd; a.g.rope = m->rope_dec; a.g.cap = cap; a.g.kvt = kvt;
         a.slots = b->slots; a.ring_off = ap.ring_off;
-        wpack_args(a.g, L.pqkv);
-        mx(a.g, L.mqkv);
-        CK(launch_gemvr(PRO_NORM, EPI_QKV, nb, a, st));
+        CK(launch_gemvr(t.pro, t.epi, nb, a, st));
         CK(launch_attn_decode_batch(hd, ap, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         // wo + residual
-        memset(&a, 0, sizeof a);
-        a.g.x = b->att; a.ldx = DQ; a.g.K = DQ; a.g.W = L.wo; a.g.wscale = L.so; a.g.rows = DD; a.g.y = b->x;
-        a.ldy = DD;
-        wpack_args(a.g, L.po);
-        mx(a.g, L.mo);
-        CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
+        t = dec_step_tensor(m, l, T_WO);
+        fill(t, b->att, DQ, b->x, DD);
+        CK(launch_gemvr(t.pro, t.epi, nb, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up
-        memset(&a, 0, sizeof a);
-        a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = L.w13; a.g.wscale = L.s13; a.g.rows = 2 * DH;
-        a.g.norm_w = L.ffn_norm; a.g.ada = m->ada_scale + (size_t)l * DD; a.g.eps = c.dec_eps; a.g.y = b->hid; a.ldy = DH;
-        wpack_args(a.g, L.p13);
-        mx(a.g, L.m13);
-        CK(launch_gemvr(PRO_NORM_ADA, EPI_SWIGLU, nb, a, st));
+        t = dec_step_tensor(m, l, T_W13);
+        fill(t, b->x, DD, b->hid, DH);
+        CK(launch_gemvr(t.pro, t.epi, nb, a, st));
         // W2 + residual
-        memset(&a, 0, sizeof a);
-        a.g.x = b->hid; a.ldx = DH; a.g.K = DH; a.g.W = L.w2; a.g.wscale = L.s2; a.g.rows = DD; a.g.y = b->x;
-        a.ldy = DD;
-        wpack_args(a.g, L.p2);
-        mx(a.g, L.m2);
-        CK(launch_gemvr(PRO_NONE, EPI_RESID, nb, a, st));
+        t = dec_step_tensor(m, l, T_W2);
+        fill(t, b->hid, DH, b->x, DD);
+        CK(launch_gemvr(t.pro, t.epi, nb, a, st));
     }
     // final norm + LM head rows, then the batched step's own end (argmax, alternatives, token
     // log, state, next inputs)
-    memset(&a, 0, sizeof a);
-    a.g.x = b->x; a.ldx = DD; a.g.K = DD; a.g.W = m->tok_emb; a.g.wscale = m->tok_emb_s; a.g.rows = c.vocab;
-    a.g.norm_w = m->dec_norm; a.g.eps = c.dec_eps; a.g.y = b->logits; a.ldy = c.vocab;
-    wpack_args(a.g, m->plm);
-    mx(a.g, m->mlm);
-    CK(launch_gemvr(PRO_NORM, EPI_STORE, nb, a, st));
+    const StepTensor t = dec_step_tensor(m, c.dec_layers, 0);
+    fill(t, b->x, DD, b->logits, c.vocab);
+    CK(launch_gemvr(t.pro, t.epi, nb, a, st));
     CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots, b->rows),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
 }
 
-// the shapes of the model all have k_gemvr instances; wmx4: the tensors that have a wmx4 GEMV
-// plane have wmx4 instances too
+// the tensors of the step all have k_gemvr instances; wmx4: those that have a wmx4 GEMV plane
+// have wmx4 instances too
 static bool model_gemvr_ok(const vox_hip_model_t* m, int wmx4 = 0) {
-    const vox_hip_config_t& c = m->c;
-    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
-    if (!(gemvr_ok(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DQ) &&
-          gemvr_ok(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && gemvr_ok(PRO_NONE, EPI_RESID, DD, DH) &&
-          gemvr_ok(PRO_NORM, EPI_STORE, c.vocab, DD)))
-        return false;
-    if (!wmx4) return true;
-    for (const DecLayerD& L : m->dec)
-        if ((L.mqkv.plane && !gemvr_ok_mx4(PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD)) ||
-            (L.mo.plane && !gemvr_ok_mx4(PRO_NONE, EPI_RESID, DD, DQ)) ||
-            (L.m13.plane && !gemvr_ok_mx4(PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD)) ||
-            (L.m2.plane && !gemvr_ok_mx4(PRO_NONE, EPI_RESID, DD, DH)))
-            return false;
-    return !m->mlm.plane || gemvr_ok_mx4(PRO_NORM, EPI_STORE, c.vocab, DD);
+    return all_step_tensors(m, [&](const StepTensor& t) {
+        return gemvr_ok(t.pro, t.epi, t.rows, t.K) && (!wmx4 || !t.mx->plane || gemvr_ok_mx4(t.pro, t.epi, t.rows, t.K));
+    });
 }
 
 // tensors of the GEMV step (4 per layer and the LM head) with / without a wmx4 GEMV plane
 static void model_gemv_wmx4_count(const vox_hip_model_t* m, long long* with, long long* without) {
-    long long n = 0;
-    for (const DecLayerD& L : m->dec)
-        for (const WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) n += M->plane != nullptr;
-    n += m->mlm.plane != nullptr;
+    long long n = 0, all = 0;
+    all_step_tensors(m, [&](const StepTensor& t) { n += t.mx->plane != nullptr; all++; return true; });
     *with = n;
-    *without = 4LL * (long long)m->dec.size() + 1 - n;
+    *without = all - n;
 }
 
 static int batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
@@ -3724,24 +3716,17 @@ extern "C" int vox_hip_batch_set_gemv_rows(vox_hip_batch_t* b, int max_rows) {
 
 // Q8 step tensors of the model (4 per layer and the LM head: those with a scale vector)
 static int model_gemv_q8_count(const vox_hip_model_t* m) {
-    int n = m->tok_emb_s != nullptr;
-    for (const DecLayerD& L : m->dec) n += (L.sqkv != nullptr) + (L.so != nullptr) + (L.s13 != nullptr) + (L.s2 != nullptr);
+    int n = 0;
+    all_step_tensors(m, [&](const StepTensor& t) { n += t.wscale != nullptr; return true; });
     return n;
 }
 
 // every step tensor has a k_gemvr instance in its own format: the Q8 one where it has scales,
 // the bf16 / wpack13 one otherwise (a checkpoint may quantise only some tensors)
 static bool model_gemvr_ok_q8(const vox_hip_model_t* m) {
-    const vox_hip_config_t& c = m->c;
-    const int DD = c.dec_dim, DQ = c.dec_heads * c.dec_head_dim, DKV = c.dec_kv_heads * c.dec_head_dim, DH = c.dec_hidden;
-    auto ok = [](const float* s, int pro, int epi, int rows, int K) {
-        return s ? gemvr_ok_q8(pro, epi, rows, K) : gemvr_ok(pro, epi, rows, K);
-    };
-    for (const DecLayerD& L : m->dec)
-        if (!(ok(L.sqkv, PRO_NORM, EPI_QKV, DQ + 2 * DKV, DD) && ok(L.so, PRO_NONE, EPI_RESID, DD, DQ) &&
-              ok(L.s13, PRO_NORM_ADA, EPI_SWIGLU, 2 * DH, DD) && ok(L.s2, PRO_NONE, EPI_RESID, DD, DH)))
-            return false;
-    return ok(m->tok_emb_s, PRO_NORM, EPI_STORE, c.vocab, DD);
+    return all_step_tensors(m, [](const StepTensor& t) {
+        return t.wscale ? gemvr_ok_q8(t.pro, t.epi, t.rows, t.K) : gemvr_ok(t.pro, t.epi, t.rows, t.K);
+    });
 }
 
 // The Q8 model's opt-in of its own: the same gemv_rows field, so the bucket
@@ -3821,39 +3806,30 @@ extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out
     return 0;
 }
 
-// The step for a bucket of 64 or 128 slots: the stacked prefill's arithmetic
-// (dec_layers_gemmf, or batch_prefill's launch_gemm layers where dec_gemmf_ok is false) on the
-// batch's own planes and scratch, with the slot-table decode attention in place of the prefill's
-// causal one.  Every weight byte is read once per step for the nb rows: the layers stream the
-// bf16 fragment-major copies (on a wmx4-rounded model they hold the planes' values), the
+// The step for a bucket of 64 or 128 slots: a rows_layers call, as the stacked
+// prefill makes (k_gemmf, or the launch_gemm form where dec_gemmf_ok is false), on the batch's own
+// planes and scratch, with the slot-table decode attention as its attention step in place of the
+// prefill's causal one.  Every weight byte is read once per step for the nb rows: the layers stream
+// the bf16 fragment-major copies (on a wmx4-rounded model they hold the planes' values), the
 // fallback the row-major tensors.  Rows are complete in b->x before and after, as in the other
 // two steps, so a batch moves between buckets from one call to the next.
-// k_gemmf's hand-off epochs are i + *b->wepoch for the step's i-th launch; the step's last
-// kernel advances the word past them, so the launches may be captured and replayed.
+// k_gemmf's hand-off epochs are i + *b->wepoch for the step's i-th launch (GemmfQ's device-word
+// discipline); the step's last kernel advances the word past them, so the launches may be
+// captured and replayed.
 static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
-    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden, QKV = DQ + 2 * DKV;
+    const int DQ = H * hd, DKV = KVH * hd, QKV = DQ + 2 * DKV;
     const float scale = 1.0f / sqrtf((float)hd);
     const int cap = c.dec_window + DEC_SLACK;
     const size_t ring_layer = (size_t)cap * DKV * kv_esize(kvt);
     hipStream_t st = b->st;
-    const int np = gemm_planes_np();
     const bool gf = dec_gemmf_ok(m, nb);
     const bool lm_gf = (!m->tok_emb_s || m->gemmf_q8) && enc_gemmf_env() && dec_gemmf_env() && gemmf_ok(nb, c.vocab, DD);
     int launches = 0;
     b->wide_q8 = 0;  // this step's launches on int8 fragments (batch_run counts them again per replay)
-    auto gemmf_w = [&](int epi, const uint16_t* xs, int K, const uint8_t* W, const float* wscale, int N, float* C, int ldc,
-                       uint16_t* xo) -> int {
-        CK(launch_gemmf(epi, np, xs, K, nb, W, N, nullptr, C, ldc, xo, b->pgws, GEMM_WS_ELEMS, b->wflags, ++launches, st,
-                        b->wepoch, gemmf_wide_rb(nb, N, K), wscale));
-        if (wscale) {
-            b->wide_q8++;
-            m->n_gemmf_q8++;
-        }
-        return 0;
-    };
+    const GemmfQ q{st, b->pgws, GEMM_WS_ELEMS, b->wflags, &launches, &m->n_gemmf_q8, b->wepoch, &b->wide_q8};
     AttnSlots ap;
     ap.q = nullptr; ap.q_ld = 0;
     ap.part = b->apart; ap.part_ld = b->apart_n;
@@ -3861,38 +3837,20 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     ap.slots = b->slots;
     AttnFuse af;
     af.qkv = b->wqkv; af.S = 1; af.N = QKV; af.rope = m->rope_dec; af.xs = b->wpa;
-    for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
-        ap.ring_off = (size_t)l * ring_layer;
-        // RMSNorm, QKV rows (decoder.c:509-530)
-        if (gf) {
-            CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.attn_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
-            if (gemmf_w(EPI_STORE, b->wpa, DD, m->dfrag[l].wqkv, L.sqkv, QKV, b->wqkv, QKV, nullptr)) return -1;
-        } else {
-            CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.attn_norm, nullptr, nb, DD, c.dec_eps, st));
-            CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, L.wqkv, L.sqkv, DD, nb, QKV, nullptr, b->wqkv, QKV, st, b->pgws, GEMM_WS_ELEMS));
-        }
-        // RoPE + K/V append at each live slot's own position + attention over its ring, the rows
-        // as the wo planes (and, for the fallback, as f32 rows in b->att)
-        CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
-        if (gf) {
-            const DecFragD& F = m->dfrag[l];
-            if (gemmf_w(EPI_RESID, b->wpa, DQ, F.wo, L.so, DD, b->x, DD, nullptr)) return -1;
-            CK(launch_rmsnorm_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, c.dec_eps, b->wpa, nullptr, 0, st));
-            if (gemmf_w(EPI_SWIGLU, b->wpa, DD, F.w13, L.s13, 2 * DH, nullptr, DH, b->wpc)) return -1;
-            if (gemmf_w(EPI_RESID, b->wpc, DH, F.w2, L.s2, DD, b->x, DD, nullptr)) return -1;
-        } else {
-            CK(launch_gemm(EPI_RESID, 3, b->att, DQ, L.wo, L.so, DQ, nb, DD, nullptr, b->x, DD, st, b->pgws, GEMM_WS_ELEMS));
-            CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, nb, DD, c.dec_eps, st));
-            CK(launch_gemm(EPI_SWIGLU, 3, b->wxn, DD, L.w13, L.s13, DD, nb, 2 * DH, nullptr, b->whid, DH, st, b->pgws, GEMM_WS_ELEMS));
-            CK(launch_gemm(EPI_RESID, 3, b->whid, DH, L.w2, L.s2, DH, nb, DD, nullptr, b->x, DD, st, b->pgws, GEMM_WS_ELEMS));
-        }
-    }
+    // RoPE + K/V append at each live slot's own position + attention over its ring, the rows
+    // as the wo planes (and, for the fallback, as f32 rows in b->att)
+    if (rows_layers(m, dec_rows_stack(c), RowsScratch{b->x, b->wqkv, b->wxn, b->att, b->whid, b->wpa, b->wpc}, q, gf, nb,
+                    [&](int l, uint16_t*) -> int {
+                        ap.ring_off = (size_t)l * ring_layer;
+                        CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
+                        return 0;
+                    }))
+        return -1;
     // final norm + LM head (tied embeddings) into b->logits, then the per-slot argmax, state,
     // token log and next inputs (decoder.c:762-779)
     if (lm_gf) {
         CK(launch_rmsnorm_fplanes(b->x, nb, DD, m->dec_norm, nullptr, c.dec_eps, b->wpa, nullptr, 0, st));
-        if (gemmf_w(EPI_STORE, b->wpa, DD, m->lm_frag, m->tok_emb_s, c.vocab, b->logits, c.vocab, nullptr)) return -1;
+        if (gemmf_on(q, EPI_STORE, b->wpa, DD, nb, m->lm_frag, m->tok_emb_s, c.vocab, nullptr, b->logits, c.vocab, nullptr)) return -1;
     } else {
         CK(launch_rmsnorm_rows(b->x, DD, b->wxn, DD, m->dec_norm, nullptr, nb, DD, c.dec_eps, st));
         CK(launch_gemm(EPI_STORE, 3, b->wxn, DD, m->tok_emb, m->tok_emb_s, DD, nb, c.vocab, nullptr, b->logits, c.vocab, st,
@@ -3903,6 +3861,7 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
     if (launches) CK(launch_gemmf_epoch_bump(b->wepoch, launches + 1, st));
     return 0;
 }
+
 
 // slot bucket of n streams: 1, 2, 4, 8, 16 or 32 slots (graph g of the bucket); past 32 the wide
 // step's 64 or 128 (g = 6, 7)
@@ -4007,7 +3966,7 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
         return 0;
     }
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
-    const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
+    const int DQ = H * hd, DKV = KVH * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     vox_hip_stream_t* lead = ss[0];
     const int N = B * np, cap = lead->dcap;
@@ -4029,42 +3988,25 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
         er.nr[i] = np;
         er.pos0[i] = 0;
     }
-    if (dec_gemmf_ok(m, N)) {
+    // the layers with the lead's scratch and planes on the batch queue (its own flags and epoch)
+    const bool gf = dec_gemmf_ok(m, N);
+    if (gf) {
         if (!b->gflags) CK(dalloc(&b->gflags, gemmf_flag_ints()));
-        if (dec_layers_gemmf(lead, GemmfQ{st, gws, gws_n, b->gflags, &b->gepoch, &m->n_gemmf_q8}, X, N, [&](int l) -> int {
-                for (int i = 0; i < B; i++) {
-                    er.Kc[i] = dec_ring(ss[i], ss[i]->dk, l);
-                    er.Vc[i] = dec_ring(ss[i], ss[i]->dv, l);
-                }
-                CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st, kvt));
-                CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
-                                    lead->dpa, kvt));
-                return 0;
-            }))
-            return -1;
-        for (int i = 0; i < B; i++)
-            if (stream_prefilled(ss[i], st)) return -1;
-        b->n_prefill_passes++;
-        b->n_prefilled += B;
-        return 0;
+        if (model_frag(m) || stream_dec_planes(lead, N)) return -1;
     }
-    for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayerD& L = m->dec[l];
-        for (int i = 0; i < B; i++) {
-            er.Kc[i] = dec_ring(ss[i], ss[i]->dk, l);
-            er.Vc[i] = dec_ring(ss[i], ss[i]->dv, l);
-        }
-        CK(launch_rmsnorm_rows(X, DD, lead->xnd, DD, L.attn_norm, nullptr, N, DD, c.dec_eps, st));
-        CK(launch_gemm(EPI_STORE, 3, lead->xnd, DD, L.wqkv, L.sqkv, DD, N, DQ + 2 * DKV, nullptr, lead->qkvd, DQ + 2 * DKV,
-                       st, gws, gws_n));
-        CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st, kvt));
-        CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
-                            nullptr, kvt));
-        CK(launch_gemm(EPI_RESID, 3, lead->attd, DQ, L.wo, L.so, DQ, N, DD, nullptr, X, DD, st, gws, gws_n));
-        CK(launch_rmsnorm_rows(X, DD, lead->xnd, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, N, DD, c.dec_eps, st));
-        CK(launch_gemm(EPI_SWIGLU, 3, lead->xnd, DD, L.w13, L.s13, DD, N, 2 * DH, nullptr, lead->gated, DH, st, gws, gws_n));
-        CK(launch_gemm(EPI_RESID, 3, lead->gated, DH, L.w2, L.s2, DH, N, DD, nullptr, X, DD, st, gws, gws_n));
-    }
+    if (rows_layers(m, dec_rows_stack(c), dec_rows_scratch(lead, X),
+                    GemmfQ{st, gws, gws_n, b->gflags, &b->gepoch, &m->n_gemmf_q8, nullptr, nullptr}, gf, N,
+                    [&](int l, uint16_t* planes) -> int {
+                        for (int i = 0; i < B; i++) {
+                            er.Kc[i] = dec_ring(ss[i], ss[i]->dk, l);
+                            er.Vc[i] = dec_ring(ss[i], ss[i]->dv, l);
+                        }
+                        CK(launch_rope_kv_rows(lead->qkvd, N, DQ, DKV, hd, m->rope_dec, er, lead->qd_, cap, st, kvt));
+                        CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
+                                            planes, kvt));
+                        return 0;
+                    }))
+        return -1;
     for (int i = 0; i < B; i++)
         if (stream_prefilled(ss[i], st)) return -1;
     b->n_prefill_passes++;
