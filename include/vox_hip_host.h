@@ -69,6 +69,16 @@ int vh_stream_get(vh_stream_t *s, int *ids, int max);
  * reset the whole stream (mel, conv stem, encoder, decoder; voxtral.c:410-420, 1189-1239). */
 void vh_stream_set_continuous(vh_stream_t *s, int on);
 
+/* The stream's own transcription delay (vox_hip_stream_set_delay, voxtral_hip.h): vh_set_delay's
+ * clamp to 80..2400 ms and 80 ms per token, for this stream only, so the streams of one context --
+ * and of one scheduler -- may serve different latencies.  A stream never given one follows
+ * vh_set_delay.  Its prompt length, the finish right-pad, vh_stream_pending and the scheduler's
+ * readiness test use it.  0, or -1 (vh_last_error) once the stream's decoder has started;
+ * vh_stream_reset keeps the delay and allows a new one (a pooled stream's next client). */
+int vh_stream_set_delay(vh_stream_t *s, int delay_ms);
+/* the delay in effect, in ms */
+int vh_stream_delay_ms(const vh_stream_t *s);
+
 /* vox_stream_set_alt (voxtral.c:1329-1337): n_alt clamped to 1..VH_MAX_ALT, cutoff to
  * [0, 1]; candidates are kept on the device per step (stream_fill_alts, voxtral.c:955-1010) */
 #define VH_MAX_ALT 4

@@ -277,6 +277,27 @@ int vox_hip_kv8_convert(const float *x, int n, uint8_t *codes, float *back);
 /* stream_reset_full_state (voxtral.c:786-814) / stream_reset_decoder_state (:766-783) */
 int vox_hip_stream_reset(vox_hip_stream_t *s);
 int vox_hip_stream_reset_decoder(vox_hip_stream_t *s);
+/* A stream's own transcription delay, so streams of one model (one copy of the weights, one batch,
+ * one scheduler) serve clients at different latencies.  delay_tokens 0..VOX_HIP_MAX_DELAY_TOKENS
+ * (80 ms per token; 30 is the host's 2400 ms clamp), or -1: follow the model (the default: the
+ * model's delay and table are read at every use, as before).  The delay sets the stream's prompt
+ * length (1 + 32 + delay_tokens) and the ada table of its FFN norms; the model keeps one table per
+ * delay, built on first use by vox_hip_model_set_delay's host arithmetic (bit-equal to it) and
+ * kept at one address until vox_hip_model_free.  Refused (-1, vox_hip_last_error) outside that
+ * range and once the stream's decoder has started; allowed again after vox_hip_stream_reset /
+ * _reset_decoder, which keep the stream's delay.  Drops the stream's own step graphs.
+ * A batched call (vox_hip_batch_decode and kin) in which no stream has a delay of its own is a
+ * plain call and runs exactly what it ran before.  Any other call is mixed: its steps take per-slot
+ * instances of the FFN norm kernels (same products in the same order, the ada row fetched through
+ * the slot table) with step graphs of their own, its new streams are prefilled in one stacked pass
+ * per distinct delay, and it never takes the R-row GEMV step (below).  Transcript quality at each
+ * delay is the model's property; it is not evaluated on synthetic weights. */
+#define VOX_HIP_MAX_DELAY_TOKENS 30
+int vox_hip_stream_set_delay(vox_hip_stream_t *s, int delay_tokens);
+/* the delay in effect, in tokens (the stream's own, or the model's) */
+int vox_hip_stream_delay(const vox_hip_stream_t *s);
+/* the stream's ada table [dec_layers*dec_dim] as computed on the host (vox_hip_model_ada_scale's twin) */
+int vox_hip_stream_ada_scale(vox_hip_stream_t *s, float *out);
 
 /* ------------------------------------------------------------------------
  * Device-resident streaming pipeline (the fast path).  Inputs are log-mel frames
@@ -428,7 +449,10 @@ int vox_hip_batch_set_prefill_kv(vox_hip_batch_t *b, int on);
  * streams always streams the bf16 fragment-major copies (on a wmx4-rounded model they hold the
  * planes' values, so the tokens are the model's).  VOX_HIP_BATCH_GEMV=<0|1|2|4|8> sets the
  * initial value at vox_hip_batch_create (ignored for a Q8 model).  Returns 0; -1 (vox_hip_last_error) for
- * another value, for a Q8 model, or between vox_hip_batch_begin_rows and vox_hip_batch_finish. */
+ * another value, for a Q8 model, or between vox_hip_batch_begin_rows and vox_hip_batch_finish.
+ * A mixed call (a stream with a delay of its own, vox_hip_stream_set_delay) takes the MFMA step
+ * whatever this switch, _q8 and _wmx4 say, as calls of more than 8 slots do: k_gemvr has no
+ * per-slot prologue.  vox_hip_batch_gemv_stats does not count its steps; vox_hip_batch_stats does. */
 int vox_hip_batch_set_gemv_rows(vox_hip_batch_t *b, int max_rows);
 /* The same opt-in for a model with Q8 step tensors (int8 rows and one f32 scale per row; buckets
  * <= 8 as above): the

@@ -192,6 +192,10 @@ struct vox_hip_model {
     float* ada_scale;              // device [dec_layers][dec_dim]
     std::vector<float> ada_host;   // host copy
     std::vector<std::vector<float>> ada_down, ada_up;
+    // ada tables of streams with a delay of their own (vox_hip_stream_set_delay), [delay]: built on
+    // first use, then neither moved nor freed before the model (slot tables and graphs hold them)
+    float* ada_tab[VOX_HIP_MAX_DELAY_TOKENS + 1];
+    std::vector<float> ada_tab_host[VOX_HIP_MAX_DELAY_TOKENS + 1];
     float *rope_enc, *rope_dec;    // device tables [rope_positions][hd]
     int rope_positions;
     int rope_gen;                  // bumped when the tables are reallocated (graphs hold the pointer)
@@ -461,21 +465,21 @@ static int lm_head_grid(const vox_hip_model* m) {
     return m->mlm.plane ? gemv_grid_mx4(m->c.vocab) : gemv_grid(m->c.vocab);
 }
 
-static int model_update_ada(vox_hip_model_t* m) {
-    // vox_update_time_conditioning (voxtral.c:31-80)
+// the ada table [dec_layers][dec_dim] of a delay: vox_update_time_conditioning (voxtral.c:31-80)
+static void model_ada_host(const vox_hip_model_t* m, int delay_tokens, std::vector<float>& out) {
     const vox_hip_config_t& c = m->c;
     int D = c.dec_dim, A = c.ada_dim;
     std::vector<float> t_cond(D), hidden(A);
     int half = D / 2;
     float log_theta = logf(10000.0f);
-    float t = (float)m->delay_tokens;
+    float t = (float)delay_tokens;
     for (int i = 0; i < half; i++) {
         float inv_freq = expf(-log_theta * (float)i / (float)half);
         float emb = t * inv_freq;
         t_cond[i] = cosf(emb);
         t_cond[i + half] = sinf(emb);
     }
-    m->ada_host.assign((size_t)c.dec_layers * D, 0.f);
+    out.assign((size_t)c.dec_layers * D, 0.f);
     for (int l = 0; l < c.dec_layers; l++) {
         const float* down = m->ada_down[l].data();
         const float* up = m->ada_up[l].data();
@@ -484,14 +488,33 @@ static int model_update_ada(vox_hip_model_t* m) {
             for (int j = 0; j < D; j++) sum += down[(size_t)i * D + j] * t_cond[j];
             hidden[i] = host_gelu(sum, c.gelu_erf);
         }
-        float* sc = m->ada_host.data() + (size_t)l * D;
+        float* sc = out.data() + (size_t)l * D;
         for (int i = 0; i < D; i++) {
             float sum = 0.f;
             for (int j = 0; j < A; j++) sum += up[(size_t)i * A + j] * hidden[j];
             sc[i] = sum;
         }
     }
+}
+
+static int model_update_ada(vox_hip_model_t* m) {
+    model_ada_host(m, m->delay_tokens, m->ada_host);
     CK(h2d(m->ada_scale, m->ada_host.data(), m->ada_host.size() * 4));
+    return 0;
+}
+
+// the model's table of delay d (0 .. VOX_HIP_MAX_DELAY_TOKENS), made on first use
+static int model_ada_table(vox_hip_model_t* m, int d) {
+    if (d < 0 || d > VOX_HIP_MAX_DELAY_TOKENS) return set_err("delay of %d tokens is not 0..%d", d, VOX_HIP_MAX_DELAY_TOKENS);
+    if (m->ada_tab[d]) return 0;
+    model_ada_host(m, d, m->ada_tab_host[d]);
+    float* t = nullptr;
+    CK(dalloc(&t, m->ada_tab_host[d].size()));
+    if (hipError_t e = h2d(t, m->ada_tab_host[d].data(), m->ada_tab_host[d].size() * 4); e != hipSuccess) {
+        dfree(t);
+        return set_err("ada table upload: %s", hipGetErrorString(e));
+    }
+    m->ada_tab[d] = t;
     return 0;
 }
 
@@ -552,6 +575,7 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     m->ad0 = m->ad1 = m->tok_emb = nullptr;
     m->ad0_s = m->ad1_s = m->tok_emb_s = nullptr;
     m->conv0_b = m->conv1_b = m->enc_norm = m->dec_norm = m->ada_scale = nullptr;
+    for (float*& t : m->ada_tab) t = nullptr;
     m->rope_enc = m->rope_dec = nullptr;
     memset(&m->plm, 0, sizeof m->plm);
     memset(&m->wstats, 0, sizeof m->wstats);
@@ -723,6 +747,7 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
     dfree(m->enc_norm); dfree(m->ad0); dfree(m->ad1); dfree(m->tok_emb); dfree(m->dec_norm);
     dfree(m->ad0_s); dfree(m->ad1_s); dfree(m->tok_emb_s);
     dfree(m->ada_scale); dfree(m->rope_enc); dfree(m->rope_dec);
+    for (float* t : m->ada_tab) dfree(t);
     delete m;
 }
 
@@ -871,6 +896,7 @@ struct vox_hip_stream {
     int graph_ready;              // bit mask of built graphs
     int started, eos_seen, n_generated;
     int h_state[4];
+    int delay;                    // vox_hip_stream_set_delay: the stream's own delay in tokens, -1: the model's
     // profiling
     int profiling;
     int graph_prof;               // the last (eager, profiled) steps recorded W1|W3 events
@@ -939,6 +965,7 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     vox_hip_stream_t* s = new vox_hip_stream_t();
     s->m = m;
     s->uid = next_uid++;
+    s->delay = -1;
     const vox_hip_config_t& c = m->c;
     auto fail = [&]() -> vox_hip_stream_t* { vox_hip_stream_free(s); return nullptr; };
 #define TRYH(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_err("%s: %s", #x, hipGetErrorString(e__)); return fail(); } } while (0)
@@ -1003,6 +1030,37 @@ static hipError_t queue_high_priority(hipStream_t* q) {
     const char* e = getenv("VOX_HIP_BATCH_PRIORITY");
     if (e && atoi(e) == 0) return hipStreamCreateWithFlags(q, hipStreamNonBlocking);
     return hipStreamCreateWithPriority(q, hipStreamNonBlocking, hi);
+}
+
+// the stream's delay and ada table: its own (vox_hip_stream_set_delay), or the model's read at use
+static int stream_delay(const vox_hip_stream_t* s) { return s->delay < 0 ? s->m->delay_tokens : s->delay; }
+static const float* stream_ada(const vox_hip_stream_t* s) { return s->delay < 0 ? s->m->ada_scale : s->m->ada_tab[s->delay]; }
+
+extern "C" int vox_hip_stream_set_delay(vox_hip_stream_t* s, int delay_tokens) {
+    if (!s) return set_err("stream_set_delay: null stream");
+    if (delay_tokens < -1 || delay_tokens > VOX_HIP_MAX_DELAY_TOKENS)
+        return set_err("stream_set_delay: %d tokens is not -1 (the model's delay) or 0..%d", delay_tokens, VOX_HIP_MAX_DELAY_TOKENS);
+    if (s->started)
+        return set_err("stream_set_delay: the stream's decoder has started (vox_hip_stream_reset or _reset_decoder first)");
+    if (delay_tokens >= 0 && model_ada_table(s->m, delay_tokens)) return -1;
+    s->delay = delay_tokens;
+    // the step graphs hold the ada pointer
+    for (int g = 0; g < STEP_GRAPHS; g++)
+        if (s->step_exec[g]) {
+            hipGraphExecDestroy(s->step_exec[g]);
+            s->step_exec[g] = nullptr;
+        }
+    s->graph_ready = 0;
+    return 0;
+}
+
+extern "C" int vox_hip_stream_delay(const vox_hip_stream_t* s) { return s ? stream_delay(s) : -1; }
+
+extern "C" int vox_hip_stream_ada_scale(vox_hip_stream_t* s, float* out) {
+    if (!s || !out) return set_err("stream_ada_scale: null argument");
+    const std::vector<float>& t = s->delay < 0 ? s->m->ada_host : s->m->ada_tab_host[s->delay];
+    memcpy(out, t.data(), t.size() * 4);
+    return 0;
 }
 
 extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s) { return s->kvt == KV_F16; }
@@ -1572,6 +1630,14 @@ struct RowsScratch {
     float *x, *qkv, *xn, *att, *hid;
     uint16_t *pa, *pc;
 };
+// Where a decoder pass takes its ada rows when not from the model's table (the layer
+// descriptor's): table: another table [layers][D] for all rows (a stream's own delay); slots: row
+// r from slots[r].ada (the wide batched step of a call with delays of its own: the per-slot norm
+// instances)
+struct RowsAda {
+    const float* table = nullptr;
+    const BatchSlot* slots = nullptr;
+};
 
 static RowsLayer enc_rows_layer(const vox_hip_model_t* m, int l) {
     const EncLayerD& L = m->enc[l];
@@ -1602,11 +1668,12 @@ static RowsStack dec_rows_stack(const vox_hip_config_t& c) {
 // or, planes != null, as the wo input planes.
 template <class Attn>
 static int rows_layers(const vox_hip_model_t* m, const RowsStack& S, const RowsScratch& B, const GemmfQ& q, bool gf, int n,
-                       Attn attn) {
+                       Attn attn, const RowsAda& ada = RowsAda{}) {
     const int D = S.D, NQKV = S.Q + 2 * S.KV, HID = S.hidden;
     hipStream_t st = q.st;
     for (int l = 0; l < S.layers; l++) {
-        const RowsLayer L = S.layer(m, l);
+        RowsLayer L = S.layer(m, l);
+        if (ada.table) L.ada = ada.table + (size_t)l * D;
         // RMSNorm, QKV (+ bias)
         if (gf) {
             CK(launch_rmsnorm_fplanes(B.x, n, D, L.attn_norm, nullptr, S.eps, B.pa, nullptr, 0, st));
@@ -1619,12 +1686,14 @@ static int rows_layers(const vox_hip_model_t* m, const RowsStack& S, const RowsS
         // wo (+ bias) residual; RMSNorm (x (1 + ada)), W1|W3 with SwiGLU, w2 (+ bias) residual
         if (gf) {
             if (gemmf_on(q, EPI_RESID, B.pa, S.Q, n, L.fo, L.so, D, L.bo, B.x, D, nullptr)) return -1;
-            CK(launch_rmsnorm_fplanes(B.x, n, D, L.ffn_norm, L.ada, S.eps, B.pa, nullptr, 0, st));
+            if (ada.slots) CK(launch_rmsnorm_fplanes_slots(B.x, n, D, L.ffn_norm, ada.slots, (size_t)l * D, S.eps, B.pa, st));
+            else CK(launch_rmsnorm_fplanes(B.x, n, D, L.ffn_norm, L.ada, S.eps, B.pa, nullptr, 0, st));
             if (gemmf_on(q, EPI_SWIGLU, B.pa, D, n, L.f13, L.s13, 2 * HID, nullptr, nullptr, HID, B.pc)) return -1;
             if (gemmf_on(q, EPI_RESID, B.pc, HID, n, L.f2, L.s2, D, L.b2, B.x, D, nullptr)) return -1;
         } else {
             CK(launch_gemm(EPI_RESID, 3, B.att, S.Q, L.wo, L.so, S.Q, n, D, L.bo, B.x, D, st, q.ws, q.ws_n));
-            CK(launch_rmsnorm_rows(B.x, D, B.xn, D, L.ffn_norm, L.ada, n, D, S.eps, st));
+            if (ada.slots) CK(launch_rmsnorm_rows_slots(B.x, D, B.xn, D, L.ffn_norm, ada.slots, (size_t)l * D, n, D, S.eps, st));
+            else CK(launch_rmsnorm_rows(B.x, D, B.xn, D, L.ffn_norm, L.ada, n, D, S.eps, st));
             CK(launch_gemm(EPI_SWIGLU, 3, B.xn, D, L.w13, L.s13, D, n, 2 * HID, nullptr, B.hid, HID, st, q.ws, q.ws_n));
             CK(launch_gemm(EPI_RESID, 3, B.hid, HID, L.w2, L.s2, HID, n, D, L.b2, B.x, D, st, q.ws, q.ws_n));
         }
@@ -2166,7 +2235,7 @@ extern "C" int vox_hip_stream_read_adapter(vox_hip_stream_t* s, int first, int n
 // device state after the prompt's prefill rows 0..np-1: the next step reads row np with the
 // streaming pad token (voxtral.c:1036-1061)
 static int stream_prefilled(vox_hip_stream_t* s, hipStream_t q) {
-    const int np = 32 + s->m->delay_tokens;
+    const int np = 32 + stream_delay(s);
     const int st4[4] = {np, np, TOKEN_STREAMING_PAD, s->n_generated};
     CK(hipMemcpyAsync(s->state, st4, sizeof st4, hipMemcpyHostToDevice, q));
     s->h_state[0] = np;
@@ -2246,7 +2315,7 @@ static int run_decoder_rows(vox_hip_stream_t* s, float* x, int n, int pos0, cons
         CK(launch_attn_rows_mf(hd, s->qd_, DQ, Kc, Vc, s->dcap, s->attd, DQ, n, H, KVH, pos0, 0, c.dec_window, scale, st,
                                s->gws, s->gws_n, planes, s->kvt));
         return 0;
-    });
+    }, RowsAda{s->delay < 0 ? nullptr : stream_ada(s), nullptr});
 }
 
 // The tensors a decode step streams (single-stream k_gemv and the R-row k_gemvr step): QKV, wo,
@@ -2329,6 +2398,7 @@ static int enqueue_step_layers(vox_hip_stream_t* s, const int* state, int pos, c
         CK(launch_gemv(t.pro, t.epi, a, st));
         // norm * (1 + ada) -> W1|W3 -> silu * up (decoder.c:742-758)
         t = dec_step_tensor(m, l, T_W13);
+        if (s->delay >= 0) t.ada = stream_ada(s) + (size_t)l * c.dec_dim;
         step_tensor_args(a, t, s->xd, s->gated, c.dec_eps, 1);
         // profiling: HIP events recorded by the W1|W3 launch's own dispatch (eager steps)
         const bool gprof = s->profiling && state && !s->capturing && (int)s->pev.size() == 2 * c.dec_layers;
@@ -2473,7 +2543,7 @@ static int ring_read(const T* ring, int cap, int rec, long long first, int n, T*
 // the first generated token then comes from row prompt_len-1 through a regular step
 static int stream_prefill(vox_hip_stream_t* s) {
     vox_hip_model_t* m = s->m;
-    const int np = 32 + m->delay_tokens;
+    const int np = 32 + stream_delay(s);
     if (stream_alloc_dec_rows(s, np)) return -1;
     if (ensure_rope(s, np + 2)) return -1;
     CK(launch_embed_rows(s->adapter, m->tok_emb, m->tok_emb_s, 0, np, TOKEN_BOS, TOKEN_STREAMING_PAD, m->c.dec_dim,
@@ -2487,7 +2557,7 @@ extern "C" int vox_hip_stream_decode(vox_hip_stream_t* s, int max_steps, int sto
     vox_hip_model_t* m = s->m;
     const vox_hip_config_t& c = m->c;
     const int D = c.dec_dim, V = c.vocab, hd = c.dec_head_dim;
-    const int prompt_len = 1 + 32 + m->delay_tokens;
+    const int prompt_len = 1 + 32 + stream_delay(s);
     int produced = 0;
     if (max_steps <= 0 || s->eos_seen) return 0;
     if (!s->started) {
@@ -3302,7 +3372,9 @@ struct vox_hip_batch {
     // arguments point at the slot table and the batch's buffers only, so they stay valid as
     // streams come and go; captured again only when the model's rope table moves
     // (wmx4: [3 wmx4 + element type], the two weight sources keep graphs of their own)
-    hipGraphExec_t gexec[6][6][STEP_GRAPHS];
+    // [mixed]: the steps of a call in which a stream carries a delay of its own launch the per-slot
+    // norm instances, so they keep graphs of their own beside the plain calls'
+    hipGraphExec_t gexec[2][6][6][STEP_GRAPHS];
     int grope_gen;
     // the MFMA step streams the wmx4 fragment planes of the tensors that have one
     // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
@@ -3335,7 +3407,7 @@ struct vox_hip_batch {
     uint16_t *wpa, *wpc;
     int* wflags;
     int* wepoch;
-    hipGraphExec_t gwexec[3][2][STEP_GRAPHS];
+    hipGraphExec_t gwexec[2][3][2][STEP_GRAPHS];  // [mixed], as gexec
     int wide_q8;  // k_gemmf launches on int8 fragments in one wide step (set by batch_step_wide)
     long long n_calls, n_replays, n_rows, n_captures, n_prefill_passes, n_prefilled;
     // split-K workspace of the stacked prefills (not the lead stream's: with an encoder pass
@@ -3349,6 +3421,7 @@ struct vox_hip_batch {
     struct {
         int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kvt, done, k;
         int gemv;  // the call's steps take the GEMV path
+        int mixed; // a stream of the call carries a delay of its own: the per-slot norm instances
         vox_hip_stream_t* streams[VOX_MAX_SLOTS];
         int* tokens_out;
         int* counts_out;
@@ -3398,13 +3471,14 @@ static int model_frag(vox_hip_model_t* m) {
 }
 
 static void batch_drop_graphs(vox_hip_batch_t* b) {
-    for (auto& k : b->gexec)
-        for (auto& g : k)
-            for (auto& e : g)
-                if (e) {
-                    hipGraphExecDestroy(e);
-                    e = nullptr;
-                }
+    for (auto& x : b->gexec)
+        for (auto& k : x)
+            for (auto& g : k)
+                for (auto& e : g)
+                    if (e) {
+                        hipGraphExecDestroy(e);
+                        e = nullptr;
+                    }
     for (auto& k : b->gvexec)
         for (auto& g : k)
             for (auto& e : g)
@@ -3412,13 +3486,14 @@ static void batch_drop_graphs(vox_hip_batch_t* b) {
                     hipGraphExecDestroy(e);
                     e = nullptr;
                 }
-    for (auto& k : b->gwexec)
-        for (auto& g : k)
-            for (auto& e : g)
-                if (e) {
-                    hipGraphExecDestroy(e);
-                    e = nullptr;
-                }
+    for (auto& x : b->gwexec)
+        for (auto& k : x)
+            for (auto& g : k)
+                for (auto& e : g)
+                    if (e) {
+                        hipGraphExecDestroy(e);
+                        e = nullptr;
+                    }
 }
 
 extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
@@ -3541,7 +3616,8 @@ static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const ui
 }
 
 // one batched step over slots 0..nb-1 of the slot table (their input rows already in b->x)
-static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4) {
+// mixed: the FFN norm's ada row per slot (k_resid_xw_fplanes_slot), from the slot table
+static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4, int mixed) {
     vox_hip_model_t* m = b->m;
     auto mx = [&](const WMx4D& M) -> const uint8_t* { return wmx4 ? M.frag : nullptr; };
     const vox_hip_config_t& c = m->c;
@@ -3578,8 +3654,12 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4)
         af.qkv = b->part; af.S = skl_splits(DD, DQ + 2 * DKV); af.N = DQ + 2 * DKV; af.rope = m->rope_dec; af.xs = b->xp_q;
         CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         CK(batch_gemm(b->xp_q, DQ, F.wo, mx(L.mo), L.so, DD, nb, b->part, st));
-        CK(launch_resid_xw_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, b->xp_d, b->part,
-                                   skl_splits(DQ, DD), nullptr, b->ssq, st));
+        if (mixed)
+            CK(launch_resid_xw_fplanes_slots(b->x, nb, DD, L.ffn_norm, b->slots, (size_t)l * DD, b->xp_d, b->part,
+                                             skl_splits(DQ, DD), nullptr, b->ssq, st));
+        else
+            CK(launch_resid_xw_fplanes(b->x, nb, DD, L.ffn_norm, m->ada_scale + (size_t)l * DD, b->xp_d, b->part,
+                                       skl_splits(DQ, DD), nullptr, b->ssq, st));
         if (!L.s13) {
             // W1|W3 with the SwiGLU folded in (k_sklx: the last block of each column slice
             // sums its slabs and writes the w2 planes)
@@ -3816,7 +3896,8 @@ extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out
 // k_gemmf's hand-off epochs are i + *b->wepoch for the step's i-th launch (GemmfQ's device-word
 // discipline); the step's last kernel advances the word past them, so the launches may be
 // captured and replayed.
-static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
+// mixed: the FFN norm's ada row per slot (rows_layers' RowsAda::slots)
+static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt, int mixed) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
@@ -3844,7 +3925,7 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt) {
                         ap.ring_off = (size_t)l * ring_layer;
                         CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
                         return 0;
-                    }))
+                    }, RowsAda{nullptr, mixed ? b->slots : nullptr}))
         return -1;
     // final norm + LM head (tied embeddings) into b->logits, then the per-slot argmax, state,
     // token log and next inputs (decoder.c:762-779)
@@ -3874,13 +3955,13 @@ static int slot_bucket(int n, int* g) {
 
 // `steps` batched steps over slots 0..nb-1: replays of the bucket's step graph (captured the
 // first time, and again only when the rope table moved), or eager launches
-static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv) {
+static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv, int mixed) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
     const int gwmx4 = b->gemv_wmx4;  // likewise (vox_hip_batch_set_gemv_wmx4: on only with a plane to stream)
     const bool wide = nb > VOX_MAX_BATCH;  // buckets 64 and 128 (gemv == 0 there)
     auto step = [&]() {
-        return wide ? batch_step_wide(b, nb, splits, kvt)
-               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4);
+        return wide ? batch_step_wide(b, nb, splits, kvt, mixed)
+               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4, mixed);
     };
     if (gemv) b->n_gemv_replays += steps;
     if (gemv && gwmx4) b->n_gemv_wmx4_replays += steps;
@@ -3894,8 +3975,8 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = wide ? b->gwexec[kvt][gb - 6][gi]
-                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[3 * wmx4 + kvt][gb][gi];
+    hipGraphExec_t& ge = wide ? b->gwexec[mixed][kvt][gb - 6][gi]
+                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[mixed][3 * wmx4 + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
@@ -3942,10 +4023,12 @@ static void stream_steps_done(vox_hip_stream_t* s, int produced, int last_token)
 // member's own queue and wait there for any encoder pass queued on it.
 // prefill_kv == 0 (vox_hip_batch_set_prefill_kv, A/B): streams with 16-bit or one-byte rings
 // take that per-stream prefill as well (correct; the shared weight pass and the overlap are lost)
+// The streams of one pass share a delay (batch_begin groups them): ss[0]'s prompt length and ada
+// table speak for the group.
 static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B, bool bounded) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
-    const int np = 32 + m->delay_tokens;
+    const int np = 32 + stream_delay(ss[0]);
     // more prompts than one pass holds (ENC_SUB rows: 26 prompts of 39 rows): stacked passes of
     // as many as fit
     const int per = std::max(1, ENC_SUB / np);
@@ -4005,7 +4088,7 @@ static int batch_prefill(vox_hip_batch_t* b, vox_hip_stream_t* const* ss, int B,
                         CK(launch_attn_rows(hd, lead->qd_, er, N, cap, lead->attd, H, KVH, c.dec_window, scale, gws, gws_n, st,
                                             planes, kvt));
                         return 0;
-                    }))
+                    }, RowsAda{lead->delay < 0 ? nullptr : stream_ada(lead), nullptr}))
         return -1;
     for (int i = 0; i < B; i++)
         if (stream_prefilled(ss[i], st)) return -1;
@@ -4027,9 +4110,11 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     if (b->call.active) return set_err("batch: a begun call was not finished");
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
-    const int prompt_len = 1 + 32 + m->delay_tokens;
+    // a call in which no stream carries a delay of its own is plain: the shared-row kernels and their graphs
+    int mixed = 0;
     for (int i = 0; i < n; i++) {
         if (!streams[i] || streams[i]->m != m) return set_err("batch streams must share the batch's model");
+        mixed |= streams[i]->delay >= 0;
         if (streams[i]->kvt != streams[0]->kvt)
             return set_err("batch streams must share the decoder KV element type (vox_hip_model_set_kv_dtype)");
         for (int j = 0; j < i; j++)
@@ -4056,13 +4141,30 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     // 1. streams whose prompt is complete and whose decoder has not started: their prefills
     //    in one stacked pass; they take their first token in the batched steps below
     {
+        //    (one pass per distinct delay, each with that delay's prompt length and ada table)
         vox_hip_stream_t* pre[VOX_MAX_SLOTS];
-        int np = 0;
+        int np = 0, longest_delay = 0;
         for (int i = 0; i < n; i++) {
             vox_hip_stream_t* s = streams[i];
-            if (!s->started && !s->eos_seen && avail[i] >= prompt_len) pre[np++] = s;
+            if (!s->started && !s->eos_seen && avail[i] >= 1 + 32 + stream_delay(s)) {
+                pre[np++] = s;
+                longest_delay = std::max(longest_delay, stream_delay(s));
+            }
         }
-        if (np && batch_prefill(b, pre, np, rows != nullptr)) return -1;
+        if (np && mixed) {
+            // the rope table covers the longest prompt before the first pass is queued
+            if (ensure_rope(pre[0], 32 + longest_delay + 2)) return -1;
+            // stable grouping by delay: the streams of a delay keep the call's order
+            std::stable_sort(pre, pre + np, [](const vox_hip_stream_t* a, const vox_hip_stream_t* c2) {
+                return stream_delay(a) < stream_delay(c2);
+            });
+        }
+        for (int i0 = 0; i0 < np;) {
+            int i1 = i0 + 1;
+            while (i1 < np && stream_delay(pre[i1]) == stream_delay(pre[i0])) i1++;
+            if (batch_prefill(b, pre + i0, i1 - i0, rows != nullptr)) return -1;
+            i0 = i1;
+        }
     }
     // 2. the slot table: slot i = streams[i], a step budget per slot, empty slots up to the
     //    bucket stopped
@@ -4073,6 +4175,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     for (int i = 0; i < nb; i++) {
         memset(&hs[i], 0, sizeof hs[i]);
         hs[i].stop_tok = -1;
+        hs[i].ada = m->ada_scale;  // (a row past the call's streams rides through the norms on the model's table)
         if (i >= n) continue;
         vox_hip_stream_t* s = streams[i];
         int lim = 0;
@@ -4089,6 +4192,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
         hs[i].live = lim > 0;
         hs[i].pos = s->h_state[0];
         hs[i].produced = 0;
+        hs[i].ada = stream_ada(s);
         if (lim > 0) {
             K = std::max(K, lim);
             longest = std::max(longest, s->h_state[0] + lim);
@@ -4108,12 +4212,14 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     //    goes out here, the rest in batch_finish.
     const int k = std::min(STEP_BATCH, K);
     // buckets of up to gemv_rows slots take the R-row GEMV step (vox_hip_batch_set_gemv_rows)
-    const int gemv = b->gemv_rows && nb <= b->gemv_rows;
-    if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv)) return -1;
+    // (a mixed call takes the MFMA step: k_gemvr has no per-slot prologue)
+    const int gemv = b->gemv_rows && nb <= b->gemv_rows && !mixed;
+    if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv, mixed)) return -1;
     CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     auto& cl = b->call;
     cl.active = 1;
     cl.gemv = gemv;
+    cl.mixed = mixed;
     cl.n = n;
     for (int i = 0; i < n; i++) cl.streams[i] = streams[i];
     cl.max_steps = max_steps;
@@ -4162,7 +4268,7 @@ static int batch_finish(vox_hip_batch_t* b) {
         }
         if (!any || done >= K) break;
         k = std::min(STEP_BATCH, K - done);
-        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv)) return -1;
+        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv, cl.mixed)) return -1;
         CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     }
     // 4. host mirrors

@@ -80,8 +80,10 @@ struct BatchSlot {
     int live;               // the current step runs for this slot
     int pos;                // state[0] mirror: the attention starts without the state hop
     int produced;           // steps taken in this call (index into the batch's token log)
+    const float* ada;       // the slot's ada table [dec_layers][dec_dim] (the model's, or its stream's delay's;
+                            // read by the per-slot norm instances of a call with delays of its own)
 };
-static_assert(sizeof(BatchSlot) == 72, "BatchSlot layout");
+static_assert(sizeof(BatchSlot) == 80, "BatchSlot layout");
 // k_gemvr: k_gemv over R <= 8 input rows (a small batched decode step).  g describes row 0
 // (x, y) and everything the rows share; biases are not taken.
 constexpr int GEMVR_MAX_ROWS = 8;
@@ -145,6 +147,9 @@ int attn_maxch(int window);      // decode-attention partials per head (64-key b
 int attn_maxsplits(int window);  // 256-key spans of a window (graph buckets)
 hipError_t launch_rmsnorm_rows(const float* x, int ldx, float* y, int ldy, const float* w,
                                const float* ada, int M, int D, float eps, hipStream_t st);
+// row r's ada row = slots[r].ada + ada_off (M <= VOX_MAX_SLOTS; a slot without a table: no ada)
+hipError_t launch_rmsnorm_rows_slots(const float* x, int ldx, float* y, int ldy, const float* w, const BatchSlot* slots,
+                                     size_t ada_off, int M, int D, float eps, hipStream_t st);
 // ws: f32 workspace for split-K partials (ws_elems floats; nullptr = no split)
 hipError_t launch_gemm(int epi, int nsplit, const float* A, int lda, const void* W,
                        const float* wscale, int K, int M, int N, const float* bias, float* C,
@@ -259,6 +264,9 @@ hipError_t launch_frag_pack(const void* src, int N, int K, int q8, void* dst, hi
 // RMSNorm (+ ada) of nb rows into planes; S > 0: x += the S split slabs of part first
 hipError_t launch_rmsnorm_fplanes(float* x, int nb, int D, const float* w, const float* ada, float eps,
                                   uint16_t* xs, const float* part, int S, hipStream_t st, const float* bias = nullptr);
+// the same without slabs, row j's ada row = slots[j].ada + ada_off (nb <= VOX_MAX_SLOTS, D <= 4096)
+hipError_t launch_rmsnorm_fplanes_slots(float* x, int nb, int D, const float* w, const BatchSlot* slots, size_t ada_off,
+                                        float eps, uint16_t* xs, hipStream_t st);
 // x[j] += the S slabs of row j (+ bias); out[j] = the S slabs of row j (+ bias)
 hipError_t launch_resid_slabs(float* x, int nb, int D, const float* part, int S, const float* bias, hipStream_t st);
 hipError_t launch_slabs_rows(const float* part, int S, int nb, int N, const float* bias, float* out, int ldo,
@@ -293,6 +301,10 @@ hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const
 // launch_gemm_skl)
 hipError_t launch_resid_xw_fplanes(float* x, int nb, int D, const float* w, const float* ada, uint16_t* xs,
                                    const float* part, int S, const float* bias, float* ssq, hipStream_t st);
+// the same with row j's ada row = slots[j].ada + ada_off (same products, same order)
+hipError_t launch_resid_xw_fplanes_slots(float* x, int nb, int D, const float* w, const BatchSlot* slots, size_t ada_off,
+                                         uint16_t* xs, const float* part, int S, const float* bias, float* ssq,
+                                         hipStream_t st);
 // k_sklx: k_skl with the neighbouring row kernels folded in (bf16 weights, or their wmx4
 // fragment plane).  Inputs are
 // always planes; SKX_PRO_SCALE planes hold x * w (* (1 + ada)) of an RMSNorm whose inverse RMS

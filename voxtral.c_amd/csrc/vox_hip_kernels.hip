@@ -129,6 +129,33 @@ __global__ __launch_bounds__(256) void k_rmsnorm_rows(const float* __restrict__ 
     }
 }
 
+// k_rmsnorm_rows with row r's ada row taken from slots[r].ada + ada_off (a batch's slot table: the
+// wide step's row-major form in a call whose streams carry delays of their own; a slot without a
+// table: no ada)
+__global__ __launch_bounds__(256) void k_rmsnorm_rows_slot(const float* __restrict__ x, int ldx,
+                                                           float* __restrict__ y, int ldy,
+                                                           const float* __restrict__ w,
+                                                           const BatchSlot* __restrict__ slots, size_t ada_off,
+                                                           int D, float eps) {
+    __shared__ float red[4];
+    const float* xr = x + (size_t)blockIdx.x * ldx;
+    float* yr = y + (size_t)blockIdx.x * ldy;
+    float ss = 0.f;
+    for (int i = threadIdx.x; i < D; i += 256) ss = fmaf(xr[i], xr[i], ss);
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    float tot = red[0] + red[1] + red[2] + red[3];
+    float inv = 1.0f / sqrtf(tot / (float)D + eps);
+    const float* ab = slots[blockIdx.x].ada;
+    const float* ada = ab ? ab + ada_off : nullptr;
+    for (int i = threadIdx.x; i < D; i += 256) {
+        float v = xr[i] * inv * w[i];
+        if (ada) v *= (1.0f + ada[i]);
+        yr[i] = v;
+    }
+}
+
 // ============================================================================
 // Pipelined MFMA GEMM (the M>1 path of prefill, adapter, conv stem and the twins):
 // C[M,N] (op)= A[M,K] (f32) * W[N,K]^T (bf16, or int8 with per-row scales: the Q8 "fused
@@ -2679,6 +2706,75 @@ __global__ __launch_bounds__(512) void k_resid_rmsnorm_fplanes(float* __restrict
         *reinterpret_cast<uint2*>(xs + frag_at(j, D, 2, k)) = make_uint2(lq[0], lq[1]);
     }
 }
+// k_resid_rmsnorm_fplanes without slabs and bias, row j's ada row taken from slots[j].ada + ada_off
+// (a batch's slot table: the wide step of a call whose streams carry delays of their own; a slot
+// without a table: no ada).  Only the ada fetch waits for the slot read: the row and the norm
+// weight are requested before.  Same sums and products in the same order.
+template <int EPT>
+__global__ __launch_bounds__(512) void k_rmsnorm_fplanes_slot(const float* __restrict__ x, int D,
+                                                              const float* __restrict__ w,
+                                                              const BatchSlot* __restrict__ slots, size_t ada_off,
+                                                              float eps, uint16_t* __restrict__ xs) {
+    constexpr int NV = EPT / 4;               // float4 per thread
+    __shared__ float sred[8];
+    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k = tid * EPT;
+    const bool own = k < D;
+    const float* ab = nullptr;
+    float v[EPT], wv[EPT], av[EPT];
+    float ss = 0.f;
+    if (own) {
+        const float* xr = x + (size_t)j * D + k;
+#pragma unroll
+        for (int u = 0; u < NV; u++) {
+            const float4 a = *reinterpret_cast<const float4*>(xr + 4 * u);
+            const float4 ww = *reinterpret_cast<const float4*>(w + k + 4 * u);
+            v[4 * u] = a.x; v[4 * u + 1] = a.y; v[4 * u + 2] = a.z; v[4 * u + 3] = a.w;
+            wv[4 * u] = ww.x; wv[4 * u + 1] = ww.y; wv[4 * u + 2] = ww.z; wv[4 * u + 3] = ww.w;
+        }
+        ab = slots[j].ada;
+#pragma unroll
+        for (int u = 0; u < NV; u++) {
+            const float4 aa = ab ? *reinterpret_cast<const float4*>(ab + ada_off + k + 4 * u) : make_float4(0.f, 0.f, 0.f, 0.f);
+            av[4 * u] = aa.x; av[4 * u + 1] = aa.y; av[4 * u + 2] = aa.z; av[4 * u + 3] = aa.w;
+        }
+#pragma unroll
+        for (int e = 0; e < EPT; e++) ss = fmaf(v[e], v[e], ss);
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) sred[wave] = ss;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) tot += sred[i];
+    if (!own) return;
+    const float inv = 1.0f / sqrtf(tot / (float)D + eps);
+    uint32_t hp[EPT / 2], mp[EPT / 2], lq[EPT / 2];
+#pragma unroll
+    for (int e = 0; e < EPT; e += 2) {
+        float v0 = v[e] * inv * wv[e], v1 = v[e + 1] * inv * wv[e + 1];
+        if (ab) {
+            v0 *= (1.0f + av[e]);
+            v1 *= (1.0f + av[e + 1]);
+        }
+        uint16_t h0, m0, l0, h1, m1, l1;
+        split3(v0, h0, m0, l0);
+        split3(v1, h1, m1, l1);
+        hp[e / 2] = h0 | ((uint32_t)h1 << 16);
+        mp[e / 2] = m0 | ((uint32_t)m1 << 16);
+        lq[e / 2] = l0 | ((uint32_t)l1 << 16);
+    }
+    if (EPT == 8) {
+        *reinterpret_cast<uint4*>(xs + frag_at(j, D, 0, k)) = make_uint4(hp[0], hp[1], hp[2 % (EPT / 2)], hp[3 % (EPT / 2)]);
+        *reinterpret_cast<uint4*>(xs + frag_at(j, D, 1, k)) = make_uint4(mp[0], mp[1], mp[2 % (EPT / 2)], mp[3 % (EPT / 2)]);
+        *reinterpret_cast<uint4*>(xs + frag_at(j, D, 2, k)) = make_uint4(lq[0], lq[1], lq[2 % (EPT / 2)], lq[3 % (EPT / 2)]);
+    } else {
+        // 4 consecutive elements share one 8-B run of the fragment layout (frag_off)
+        *reinterpret_cast<uint2*>(xs + frag_at(j, D, 0, k)) = make_uint2(hp[0], hp[1]);
+        *reinterpret_cast<uint2*>(xs + frag_at(j, D, 1, k)) = make_uint2(mp[0], mp[1]);
+        *reinterpret_cast<uint2*>(xs + frag_at(j, D, 2, k)) = make_uint2(lq[0], lq[1]);
+    }
+}
 
 // rows of x (f32) into fragment-major planes
 __global__ __launch_bounds__(256) void k_split_fplanes(const float* __restrict__ x, int K, uint16_t* __restrict__ xs) {
@@ -3141,6 +3237,91 @@ __global__ __launch_bounds__(64) void k_resid_xw_fplanes(float* __restrict__ x, 
     *reinterpret_cast<uint2*>(xs + frag_at(j, D, 2, k)) = make_uint2(lq[0], lq[1]);
 }
 
+// k_resid_xw_fplanes with row j's ada row taken from slots[j].ada + ada_off (the batched step of a
+// call whose streams carry delays of their own; a slot without a table: no ada).  The slot read
+// goes out behind the first round of slab loads and only the ada fetch waits for it: the row,
+// slabs, bias and norm weight are requested before, as in the shared-row kernel, whose text this
+// repeats (a kernel of its own, so that the shared-row kernel's code stays as it was).  Same
+// products in the same order.
+__global__ __launch_bounds__(64) void k_resid_xw_fplanes_slot(float* __restrict__ x, int D,
+                                                              const float* __restrict__ part, int S,
+                                                              const float* __restrict__ bias,
+                                                              const float* __restrict__ w,
+                                                              const BatchSlot* __restrict__ slots, size_t ada_off,
+                                                              uint16_t* __restrict__ xs, float* __restrict__ ssq) {
+    // slabs per load round: 24 covers the batched step's wo (8 splits) and W2 (18) in one
+    // round of loads instead of 1 and 3 dependent ones
+    constexpr int CH = 24;
+    const int sl = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
+    const int k = sl * 256 + lane * 4;
+    float* xr = x + (size_t)j * D + k;
+    float4 v = *reinterpret_cast<const float4*>(xr);
+    const float4 ww = *reinterpret_cast<const float4*>(w + k);
+    const float* ada = nullptr;
+    float4 aa = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 bb = bias ? *reinterpret_cast<const float4*>(bias + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (S <= 0) {
+        const float* ab = slots[j].ada;
+        ada = ab ? ab + ada_off : nullptr;
+        if (ada) aa = *reinterpret_cast<const float4*>(ada + k);
+    }
+    if (S > 0) {
+        const float* pb = part + (size_t)(j >> 4) * S * SK_ROWS * D + (size_t)(j & 15) * D + k;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int s0 = 0; s0 < S; s0 += CH) {
+            float4 t[CH];
+#pragma unroll
+            for (int c = 0; c < CH; c++)
+                t[c] = s0 + c < S ? *reinterpret_cast<const float4*>(pb + (size_t)(s0 + c) * SK_ROWS * D)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (s0 == 0) {
+                // (read here, behind the round's loads: a scalar read issued earlier would be
+                // waited for together with the kernel arguments the slab addresses need)
+                const float* ab = slots[j].ada;
+                ada = ab ? ab + ada_off : nullptr;
+                if (ada) aa = *reinterpret_cast<const float4*>(ada + k);
+            }
+#pragma unroll
+            for (int c = 0; c < CH; c++)
+                if (s0 + c < S) {
+                    if (s0 + c) {
+                        r.x += t[c].x; r.y += t[c].y; r.z += t[c].z; r.w += t[c].w;
+                    } else {
+                        r = t[c];
+                    }
+                }
+        }
+        if (bias) {
+            r.x += bb.x; r.y += bb.y; r.z += bb.z; r.w += bb.w;
+        }
+        v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+        *reinterpret_cast<float4*>(xr) = v;
+    }
+    float ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w)));
+    ss = wave_sum(ss);
+    if (lane == 0) ssq[((size_t)(j >> 4) * gridDim.x + sl) * SK_ROWS + (j & 15)] = ss;
+    const float e[4] = {v.x * ww.x, v.y * ww.y, v.z * ww.z, v.w * ww.w};
+    const float ad[4] = {aa.x, aa.y, aa.z, aa.w};
+    uint32_t hp[2], mp[2], lq[2];
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+        float v0 = e[i], v1 = e[i + 1];
+        if (ada) {
+            v0 *= (1.0f + ad[i]);
+            v1 *= (1.0f + ad[i + 1]);
+        }
+        uint16_t h0, m0, l0, h1, m1, l1;
+        split3(v0, h0, m0, l0);
+        split3(v1, h1, m1, l1);
+        hp[i / 2] = h0 | ((uint32_t)h1 << 16);
+        mp[i / 2] = m0 | ((uint32_t)m1 << 16);
+        lq[i / 2] = l0 | ((uint32_t)l1 << 16);
+    }
+    *reinterpret_cast<uint2*>(xs + frag_at(j, D, 0, k)) = make_uint2(hp[0], hp[1]);
+    *reinterpret_cast<uint2*>(xs + frag_at(j, D, 1, k)) = make_uint2(mp[0], mp[1]);
+    *reinterpret_cast<uint2*>(xs + frag_at(j, D, 2, k)) = make_uint2(lq[0], lq[1]);
+}
+
 // silu(W1 x) * (W3 x) of the split W1|W3 result (16-row interleave, upload_w13) into the
 // fragment-major planes of the w2 input; a thread owns 2 consecutive hidden units
 __global__ __launch_bounds__(256) void k_swiglu_fplanes(const float* __restrict__ part, int S, int H,
@@ -3513,6 +3694,15 @@ hipError_t launch_rmsnorm_rows(const float* x, int ldx, float* y, int ldy, const
                                const float* ada, int M, int D, float eps, hipStream_t st) {
     if (M <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_rmsnorm_rows, dim3(M), dim3(256), 0, st, x, ldx, y, ldy, w, ada, D, eps);
+    LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_rmsnorm_rows_slots(const float* x, int ldx, float* y, int ldy, const float* w, const BatchSlot* slots,
+                                     size_t ada_off, int M, int D, float eps, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    if (M > VOX_MAX_SLOTS || !slots) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rmsnorm_rows_slot, dim3(M), dim3(256), 0, st, x, ldx, y, ldy, w, slots, ada_off, D, eps);
     LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -4355,6 +4545,18 @@ hipError_t launch_rmsnorm_fplanes(float* x, int nb, int D, const float* w, const
     return hipSuccess;
 }
 
+hipError_t launch_rmsnorm_fplanes_slots(float* x, int nb, int D, const float* w, const BatchSlot* slots, size_t ada_off,
+                                        float eps, uint16_t* xs, hipStream_t st) {
+    // the one-block-per-row kernels only (D <= 4096): wider rows have no per-slot instance
+    if (nb < 1 || nb > VOX_MAX_SLOTS || D % 64 || D > 8 * 512 || !slots) return hipErrorInvalidValue;
+    if (D <= 4 * 512 && D % 4 == 0)
+        hipLaunchKernelGGL(k_rmsnorm_fplanes_slot<4>, dim3(nb), dim3(512), 0, st, x, D, w, slots, ada_off, eps, xs);
+    else
+        hipLaunchKernelGGL(k_rmsnorm_fplanes_slot<8>, dim3(nb), dim3(512), 0, st, x, D, w, slots, ada_off, eps, xs);
+    LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 hipError_t launch_resid_slabs(float* x, int nb, int D, const float* part, int S, const float* bias, hipStream_t st) {
     if (nb < 1 || nb > SK_MAX_ROWS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_resid_slabs, dim3((D + 255) / 256, nb), dim3(256), 0, st, x, D, part, S, bias);
@@ -4468,6 +4670,16 @@ hipError_t launch_resid_xw_fplanes(float* x, int nb, int D, const float* w, cons
                                    const float* part, int S, const float* bias, float* ssq, hipStream_t st) {
     if (nb < 1 || nb > SK_MAX_ROWS || D % 256 || D / 256 > SKL_MAX_SLICES || !ssq) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_resid_xw_fplanes, dim3(D / 256, nb), dim3(64), 0, st, x, D, part, S, bias, w, ada, xs, ssq);
+    LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_resid_xw_fplanes_slots(float* x, int nb, int D, const float* w, const BatchSlot* slots, size_t ada_off,
+                                         uint16_t* xs, const float* part, int S, const float* bias, float* ssq,
+                                         hipStream_t st) {
+    if (nb < 1 || nb > SK_MAX_ROWS || D % 256 || D / 256 > SKL_MAX_SLICES || !ssq || !slots) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_resid_xw_fplanes_slot, dim3(D / 256, nb), dim3(64), 0, st, x, D, part, S, bias, w, slots, ada_off,
+                       xs, ssq);
     LAUNCH_CHECK();
     return hipSuccess;
 }

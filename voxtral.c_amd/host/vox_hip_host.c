@@ -667,6 +667,21 @@ int vh_stream_reset(vh_stream_t *s) {
 
 void vh_stream_set_continuous(vh_stream_t *s, int on) { s->continuous = on ? 1 : 0; }
 
+/* the stream's own delay (vox_hip_stream_set_delay): vh_set_delay's clamp and 80 ms per token;
+ * vh_stream_reset keeps it */
+int vh_stream_set_delay(vh_stream_t *s, int delay_ms) {
+    if (!s) return -1;
+    if (delay_ms < 80) delay_ms = 80;
+    if (delay_ms > 2400) delay_ms = 2400;
+    if (vox_hip_stream_set_delay(s->st, delay_ms / 80)) return fail("vh_stream_set_delay: %s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_stream_delay_ms(const vh_stream_t *s) { return s ? 80 * vox_hip_stream_delay(s->st) : -1; }
+
+/* the delay in effect for s, in tokens: its own, or the model's */
+static int stream_delay_tokens(const vh_stream_t *s) { return vox_hip_stream_delay(s->st); }
+
 int vh_stream_set_alt(vh_stream_t *s, int n_alt, float cutoff) {
     if (n_alt < 1) n_alt = 1;
     if (n_alt > VH_MAX_ALT) n_alt = VH_MAX_ALT;
@@ -861,7 +876,7 @@ static int after_drain(vh_stream_t *s, int eos) {
 static int decoder_ready(vh_stream_t *s) {
     int st6[6];
     vox_hip_stream_state(s->st, st6);
-    return st6[3] || vox_hip_stream_adapter_tokens(s->st) >= 1 + 32 + s->ctx->delay_tokens;
+    return st6[3] || vox_hip_stream_adapter_tokens(s->st) >= 1 + 32 + stream_delay_tokens(s);
 }
 
 /* stream_run_decoder (voxtral.c:1013-1240): prefill once the prompt's adapter rows exist,
@@ -910,7 +925,7 @@ int vh_stream_flush(vh_stream_t *s) {
     /* the right padding vox_stream_flush feeds (voxtral.c:1645-1656) */
     const int align = (int)((RAW_AUDIO_LENGTH_PER_TOK - (s->real_samples % RAW_AUDIO_LENGTH_PER_TOK)) %
                             RAW_AUDIO_LENGTH_PER_TOK);
-    const int pad = align + ((s->ctx->delay_tokens + 1) + OFFLINE_STREAMING_BUFFER_TOKENS) * RAW_AUDIO_LENGTH_PER_TOK;
+    const int pad = align + ((stream_delay_tokens(s) + 1) + OFFLINE_STREAMING_BUFFER_TOKENS) * RAW_AUDIO_LENGTH_PER_TOK;
     float *zeros = calloc((size_t)pad, sizeof(float));
     const int rc = vox_hip_mel_feed(s->mel, zeros, pad);
     free(zeros);
@@ -1079,7 +1094,7 @@ int vh_stream_pending(vh_stream_t *s) {
     if (st6[4]) return 0;  /* EOS: nothing more is decoded (non-continuous) */
     const int rows = vox_hip_stream_adapter_tokens(s->st);
     int left;
-    if (!st6[3]) left = rows >= 1 + 32 + s->ctx->delay_tokens ? rows - (32 + s->ctx->delay_tokens) : 0;
+    if (!st6[3]) left = rows >= 1 + 32 + stream_delay_tokens(s) ? rows - (32 + stream_delay_tokens(s)) : 0;
     else left = rows - st6[1] > 0 ? rows - st6[1] : 0;
     /* a chunk deferred for the scheduler's encoder pass has rows to come */
     return left + (s->pend_n > 0);
@@ -1214,7 +1229,7 @@ int vh_sched_run(vh_sched_t *q) {
             rows[i] = vox_hip_stream_adapter_tokens(s->st);
             int st6[6];
             vox_hip_stream_state(s->st, st6);
-            ran[i] = st6[3] || rows[i] >= 1 + 32 + s->ctx->delay_tokens;
+            ran[i] = st6[3] || rows[i] >= 1 + 32 + stream_delay_tokens(s);
         }
     /* 0. every attached stream's deferred chunk through one batched encoder pass (the layers'
      *    weights read once for all of them); with the overlap it is enqueued after the first

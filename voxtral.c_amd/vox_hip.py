@@ -130,6 +130,7 @@ EXPORTS = [
     "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
+    "vox_hip_stream_set_delay", "vox_hip_stream_delay", "vox_hip_stream_ada_scale",
     "vox_hip_stream_adapter_tokens", "vox_hip_stream_read_adapter", "vox_hip_stream_decode",
     "vox_hip_batch_create", "vox_hip_batch_free", "vox_hip_batch_decode", "vox_hip_batch_decode_rows",
     "vox_hip_batch_begin_rows", "vox_hip_batch_finish",
@@ -185,6 +186,8 @@ def lib():
         "vox_hip_gemmf_q8_rows": (I, [I, I, I, fp, P, fp, fp, I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
         "vox_hip_stream_reset": (I, [P]), "vox_hip_stream_reset_decoder": (I, [P]),
+        "vox_hip_stream_set_delay": (I, [P, I]), "vox_hip_stream_delay": (I, [P]),
+        "vox_hip_stream_ada_scale": (I, [P, fp]),
         "vox_hip_stream_encode_mel": (I, [P, P, I, I]),
         "vox_hip_stream_adapter_tokens": (I, [P]),
         "vox_hip_stream_read_adapter": (I, [P, I, I, fp]),
@@ -248,6 +251,7 @@ def _err(what):
 
 
 KV_F32, KV_F16, KV_FP8 = 0, 1, 2                       # decoder KV ring element types
+MAX_DELAY_TOKENS = 30                                  # VOX_HIP_MAX_DELAY_TOKENS (2400 ms)
 KV_NP_DTYPE = {KV_F32: np.float32, KV_F16: np.float16, KV_FP8: np.uint8}
 
 
@@ -470,6 +474,25 @@ class Stream:
     def reset(self):
         if lib().vox_hip_stream_reset(self.h) != 0:
             _err("reset")
+
+    def set_delay(self, delay_tokens: int | None):
+        """vox_hip_stream_set_delay: the stream's own delay in tokens (0..MAX_DELAY_TOKENS, 80 ms
+        each); None or -1: follow the model (the default).  Refused once the decoder has started."""
+        if lib().vox_hip_stream_set_delay(self.h, -1 if delay_tokens is None else int(delay_tokens)) != 0:
+            _err("stream_set_delay")
+
+    @property
+    def delay_tokens(self) -> int:
+        """the delay in effect: the stream's own, or the model's"""
+        return lib().vox_hip_stream_delay(self.h)
+
+    def ada_scale(self):
+        """the stream's ada table (Model.ada_scale's twin)"""
+        c = self.cfg
+        out = np.empty(c.dec_layers * c.dec_dim, np.float32)
+        if lib().vox_hip_stream_ada_scale(self.h, fptr(out)) != 0:
+            _err("stream_ada_scale")
+        return out.reshape(c.dec_layers, c.dec_dim)
 
     @property
     def kv_fp16(self) -> bool:
@@ -748,7 +771,7 @@ class AudioSession(Session):
         self.feed(self.mel, stop_at_eos)
 
     def flush_samples(self, stop_at_eos=True):
-        pad = right_pad_samples(self.real_samples, self.s.model.delay_tokens)
+        pad = right_pad_samples(self.real_samples, self.s.delay_tokens)
         self.mel.feed(np.zeros(pad, np.float32))
         self.flush(self.mel, stop_at_eos)
 
@@ -993,6 +1016,7 @@ def host_lib():
         "vh_sched_detach": (I, [P, P]), "vh_sched_run": (I, [P]),
         "vh_sched_stats": (None, [P, ctypes.POINTER(SchedStats)]),
         "vh_sched_set_step_cap": (None, [P, I]), "vh_stream_pending": (I, [P]),
+        "vh_stream_set_delay": (I, [P, I]), "vh_stream_delay_ms": (I, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(H, name)
@@ -1050,6 +1074,14 @@ class HostStream:
         """vh_stream_reset: new audio on this (detached) stream, its buffers and settings kept"""
         if host_lib().vh_stream_reset(self.h) != 0:
             _herr("vh_stream_reset")
+
+    def set_delay(self, delay_ms: int):
+        """vh_stream_set_delay: this stream's own delay (clamped to 80..2400 ms, 80 ms per token)"""
+        if host_lib().vh_stream_set_delay(self.h, int(delay_ms)) != 0:
+            _herr("vh_stream_set_delay")
+
+    def delay_ms(self) -> int:
+        return host_lib().vh_stream_delay_ms(self.h)
 
     def get(self) -> list[int]:
         out, buf = [], np.empty(4096, np.int32)
