@@ -107,6 +107,12 @@ int vh_stream_pending(vh_stream_t *s);
  * quality not evaluated).  0, or -1 (vh_last_error).  vh_stream_reset keeps a stream's type. */
 int vh_set_kv_dtype(vh_ctx_t *ctx, int dtype);
 int vh_stream_kv_dtype(const vh_stream_t *s);
+/* The encoder KV rings of the streams vh_stream_init makes from now on: on = 1 IEEE half
+ * (vox_hip_model_set_enc_kv_fp16, voxtral_hip.h: half the rings' bytes, quality not evaluated),
+ * 0 f32 (default).  0, or -1 (vh_last_error).  vh_stream_reset keeps a stream's type; one
+ * vh_sched_t serves streams of both types. */
+int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on);
+int vh_stream_enc_kv_fp16(const vh_stream_t *s);
 
 /* The model behind a context (for the model-level calls of voxtral_hip.h, such as
  * vox_hip_model_wmx4_stats); the context keeps owning it. */

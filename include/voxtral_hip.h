@@ -114,10 +114,23 @@ int vox_hip_model_set_kv_fp16(vox_hip_model_t *m, int on);
  * stays f32 in the f32 ring's order.  A quarter of the f32 ring's bytes per step and per
  * stream.  Its effect on transcripts is NOT evaluated.  Opt-in: off unless VOX_HIP_KV_FP8 is
  * set nonzero at model creation (it wins over VOX_DECODER_KV_FP16) or dtype = 2 is passed.
- * The encoder KV stays f32.  Every decoder path honours the element type, the batch's stacked
+ * The encoder KV is not touched by this call (vox_hip_model_set_enc_kv_fp16).  Every decoder
+ * path honours the element type, the batch's stacked
  * prefill of joining streams included (vox_hip_batch_set_prefill_kv).  head_dim 128 only for 1
  * and 2; returns 0, or -1 (vox_hip_last_error) for another head_dim or dtype. */
 int vox_hip_model_set_kv_dtype(vox_hip_model_t *m, int dtype);
+/* The encoder's K/V rings (no reference counterpart: the reference's VOX_DECODER_KV_FP16 is
+ * decoder-only): streams created after this call with on = 1 keep their encoder rings in IEEE
+ * half -- stores round with the decoder ring's rule (nearest even, overflow to infinity), loads
+ * widen to f32, the windowed attention keeps its f32 MFMA, f32 queries and the f32 ring's
+ * accumulation order.  Half the ring's bytes: (enc_window + 1088) slots x 32 layers x 2048
+ * columns x K and V = 0.96 GB per stream as f32, 0.48 GB as half; 123 / 62 GB at 128 streams.
+ * Its effect on transcripts is NOT evaluated.  Opt-in: off unless VOX_HIP_ENC_KV_FP16 is set
+ * nonzero at model creation or on = 1 is passed.  Every encoder path honours the stream's type
+ * (one-row GEMV, the skinny chains, the long passes, the batched pass, vox_hip_encoder_full_step).
+ * There is NO FP8 encoder ring.  head_dim 64 only (Voxtral's encoder); returns 0, or -1
+ * (vox_hip_last_error) for another head_dim. */
+int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t *m, int on);
 /* wpack13 (no reference counterpart): at creation every bf16 matrix of the single-stream
  * decode step (Q|K|V, wo, W1|W3, W2 per decoder layer, and the LM head) whose nonzero
  * exponents span at most 30 binades also gets a 13-bit-per-weight copy that the M = 1 GEMV
@@ -264,12 +277,27 @@ void vox_hip_stream_free(vox_hip_stream_t *s);
 int vox_hip_stream_kv_fp16(const vox_hip_stream_t *s);
 /* the stream's decoder KV ring element: 0 f32, 1 IEEE half, 2 FP8 E4M3 (vox_hip_model_set_kv_dtype) */
 int vox_hip_stream_kv_dtype(const vox_hip_stream_t *s);
+/* 1 if the stream's encoder KV rings hold IEEE half (vox_hip_model_set_enc_kv_fp16), else 0 */
+int vox_hip_stream_enc_kv_fp16(const vox_hip_stream_t *s);
+/* Tests / diagnostics: the stream's own encoder passes since creation, by the path they took:
+ * out5[0] one-row GEMV passes, [1] fused skinny chains (k_sklx), [2] slab skinny chains,
+ * [3] M > 1 rows passes (GEMM), [4] fused-chain passes whose attention took a split key grid and
+ * the combine kernel.  Passes of a batched call that stacks several streams are not counted. */
+int vox_hip_stream_enc_paths(const vox_hip_stream_t *s, long long out5[5]);
+/* bytes of the stream's encoder K and V rings together (all layers) */
+long long vox_hip_stream_enc_kv_bytes(const vox_hip_stream_t *s);
 /* Tests / diagnostics: the raw ring elements of decoder layer `layer` at logical positions
  * [first_logical_pos, first_logical_pos + n), [n][dec_kv_heads * dec_head_dim] in the stream's
  * element type (4, 2 or 1 bytes each) to k_out / v_out (either may be null).  Waits for the
  * stream's queue.  -1 (vox_hip_last_error) for positions not appended yet or already
  * overwritten by the ring's wrap. */
 int vox_hip_stream_read_kv(vox_hip_stream_t *s, int layer, int first_logical_pos, int n, void *k_out, void *v_out);
+/* Tests / diagnostics: the encoder twin of vox_hip_stream_read_kv -- the raw ring elements of
+ * encoder layer `layer` at logical encoder positions [first_logical_pos, first_logical_pos + n),
+ * [n][enc_kv_heads * enc_head_dim] in the stream's element type (4 or 2 bytes each) to k_out /
+ * v_out (either may be null).  Waits for the stream's queue.  -1 (vox_hip_last_error) for
+ * positions beyond the rows encoded so far or already overwritten by the ring's wrap. */
+int vox_hip_stream_read_enc_kv(vox_hip_stream_t *s, int layer, int first_logical_pos, int n, void *k_out, void *v_out);
 /* Tests: the kernels' own FP8 ring store and load helpers run on the device over x[0..n):
  * codes[i] = the byte a ring slot would hold, back[i] = the f32 the attention kernels read from
  * it (either may be null).  Must equal csrc/vox_kv8.h for every input. */

@@ -203,6 +203,7 @@ struct vox_hip_model {
     std::vector<DecFragD> efrag;   // fragment-major encoder matrices (empty until a short chunk)
     uint8_t* lm_frag;              // fragment-major LM head (tied embeddings)
     int kvt;                       // decoder KV ring element of streams created from now on (KV_F32 / KV_F16 / KV_FP8)
+    int ekvt;                      // encoder KV ring element of streams created from now on (KV_F32 / KV_F16)
     WPackD plm;                    // wpack13 copy of the LM head
     int wpack;                     // VOX_HIP_WPACK (default 1), read once at creation
     vox_hip_wpack_stats_t wstats;
@@ -570,6 +571,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         // are set, head_dim 128 only like it; vox_hip_model_set_kv_dtype overrides
         const char* e8 = getenv("VOX_HIP_KV_FP8");
         if (e8 && atoi(e8) != 0 && cfg->dec_head_dim == 128) m->kvt = KV_FP8;
+        // the encoder's rings (no reference counterpart: VOX_DECODER_KV_FP16 is decoder-only):
+        // IEEE half when VOX_HIP_ENC_KV_FP16 is set nonzero, head_dim 64 only;
+        // vox_hip_model_set_enc_kv_fp16 overrides
+        const char* ee = getenv("VOX_HIP_ENC_KV_FP16");
+        m->ekvt = (ee && atoi(ee) != 0 && cfg->enc_head_dim == 64) ? KV_F16 : KV_F32;
     }
     m->conv0_w = m->conv1_w = nullptr;
     m->ad0 = m->ad1 = m->tok_emb = nullptr;
@@ -827,6 +833,13 @@ extern "C" int vox_hip_model_set_kv_dtype(vox_hip_model_t* m, int dtype) {
     return 0;
 }
 
+extern "C" int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t* m, int on) {
+    if (!m) return set_err("model_set_enc_kv_fp16: null model");
+    if (on && m->c.enc_head_dim != 64) return set_err("16-bit encoder KV: head_dim 64 only (got %d)", m->c.enc_head_dim);
+    m->ekvt = on ? KV_F16 : KV_F32;
+    return 0;
+}
+
 extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s);
 
 extern "C" int vox_hip_model_ada_scale(vox_hip_model_t* m, float* out) {
@@ -850,8 +863,12 @@ struct vox_hip_stream {
     hipStream_t st;
     // rolling KV caches [layers][cap][kv_dim]
     float *ek, *ev, *dk, *dv;   // dk / dv: elements of type kvt (f32, IEEE half or FP8 E4M3 bytes)
-    int ecap, dcap;
-    int kvt;
+    int ecap, dcap;             // ek / ev: elements of type ekvt (f32 or IEEE half)
+    int kvt, ekvt;
+    // encoder passes of this stream by path (vox_hip_stream_enc_paths): one-row GEMV, fused
+    // skinny chain (k_sklx), slab skinny chain, M > 1 rows pass, and layer-0 attention launches
+    // that took a split key grid
+    long long enc_paths[5];
     long long enc_pos;  // next encoder logical position
     // conv stem
     float *mel_p, *mel_tail, *c0_p, *c0_tail, *c0_res, *im2col;
@@ -976,8 +993,10 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     s->ecap = c.enc_window + ENC_SUB + 64;
     s->dcap = c.dec_window + DEC_SLACK;
     s->kvt = m->kvt;
-    TRYH(dalloc(&s->ek, (size_t)c.enc_layers * s->ecap * EKV));
-    TRYH(dalloc(&s->ev, (size_t)c.enc_layers * s->ecap * EKV));
+    s->ekvt = m->ekvt;
+    // (a half encoder ring has head_dim 64, so EKV is a multiple of 2)
+    TRYH(dalloc(&s->ek, (size_t)c.enc_layers * s->ecap * EKV / (4 / kv_esize(s->ekvt))));
+    TRYH(dalloc(&s->ev, (size_t)c.enc_layers * s->ecap * EKV / (4 / kv_esize(s->ekvt))));
     // (dalloc counts floats: a half ring takes half of them, a one-byte ring a quarter; the
     // narrow modes have head_dim 128, so DKV is a multiple of 4)
     TRYH(dalloc(&s->dk, (size_t)c.dec_layers * s->dcap * DKV / (4 / kv_esize(s->kvt))));
@@ -1065,6 +1084,26 @@ extern "C" int vox_hip_stream_ada_scale(vox_hip_stream_t* s, float* out) {
 
 extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s) { return s->kvt == KV_F16; }
 extern "C" int vox_hip_stream_kv_dtype(const vox_hip_stream_t* s) { return s->kvt; }
+
+extern "C" int vox_hip_stream_enc_kv_fp16(const vox_hip_stream_t* s) { return s && s->ekvt == KV_F16; }
+extern "C" int vox_hip_stream_enc_paths(const vox_hip_stream_t* s, long long out5[5]) {
+    if (!s || !out5) return set_err("stream_enc_paths: null argument");
+    for (int i = 0; i < 5; i++) out5[i] = s->enc_paths[i];
+    return 0;
+}
+// bytes of the stream's encoder K and V rings together
+extern "C" long long vox_hip_stream_enc_kv_bytes(const vox_hip_stream_t* s) {
+    if (!s) return -1;
+    const vox_hip_config_t& c = s->m->c;
+    return 2LL * c.enc_layers * s->ecap * c.enc_kv_heads * c.enc_head_dim * (long long)kv_esize(s->ekvt);
+}
+
+// layer l's encoder K or V ring (base = s->ek or s->ev) in the stream's element type
+static float* enc_ring(const vox_hip_stream_t* s, float* base, int l) {
+    const vox_hip_config_t& c = s->m->c;
+    const size_t elems = (size_t)l * s->ecap * c.enc_kv_heads * c.enc_head_dim;
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * kv_esize(s->ekvt));
+}
 
 // layer l's decoder K or V ring (base = s->dk or s->dv) in the stream's element type
 static float* dec_ring(const vox_hip_stream_t* s, float* base, int l) {
@@ -1445,11 +1484,12 @@ static int run_encoder_rows_skinny(vox_hip_stream_t* s, float* x, int n, long lo
         f.eps = c.enc_eps;
         const int nsl_wo = sklx_slices(ED, EQ), nsl_w2 = sklx_slices(ED, EH);
         CK(launch_rmsnorm_fplanes(x, n, ED, m->enc[0].attn_norm, nullptr, c.enc_eps, xa, nullptr, 0, st));
+        s->enc_paths[1]++;
         for (int l = 0; l < c.enc_layers; l++) {
             const EncLayerD& L = m->enc[l];
             const DecFragD& F = m->efrag[l];
-            float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-            float* Vc = s->ev + (size_t)l * s->ecap * EKV;
+            float* Kc = enc_ring(s, s->ek, l);
+            float* Vc = enc_ring(s, s->ev, l);
             // QKV (attention RMSNorm: layer 0 normalised planes, then x * w planes scaled by
             // the inverse RMS), bias + RoPE + K/V append epilogue (encoder.c:562-607)
             SklFused q = f;
@@ -1465,9 +1505,12 @@ static int run_encoder_rows_skinny(vox_hip_stream_t* s, float* x, int n, long lo
             q.q = s->q;
             q.Kc = Kc;
             q.Vc = Vc;
+            q.kvt = s->ekvt;
+            int ns = 0;
             CK(launch_gemm_sklx(l ? SKX_PRO_SCALE : SKX_PRO_PLANES, SKX_EPI_QKV, xa, ED, F.wqkv, NQKV, n, q, st));
             CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale,
-                                 st, s->gws, s->gws_n, xq));
+                                 st, s->gws, s->gws_n, xq, s->ekvt, &ns));
+            if (l == 0) s->enc_paths[4] += ns > 1;
             // wo + bias residual (encoder.c:640-644); the FFN norm's planes and row sums of squares
             SklFused o = f;
             o.x = x;
@@ -1496,20 +1539,22 @@ static int run_encoder_rows_skinny(vox_hip_stream_t* s, float* x, int n, long lo
         CK(launch_rmsnorm_rows(x, ED, x, ED, m->enc_norm, nullptr, n, ED, c.enc_eps, st));
         return 0;
     }
+    s->enc_paths[2]++;
     for (int l = 0; l < c.enc_layers; l++) {
         const EncLayerD& L = m->enc[l];
         const DecFragD& F = m->efrag[l];
-        float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-        float* Vc = s->ev + (size_t)l * s->ecap * EKV;
+        float* Kc = enc_ring(s, s->ek, l);
+        float* Vc = enc_ring(s, s->ev, l);
         // previous layer's w2 residual (+ bias) then RMSNorm -> planes (encoder.c:562-566, 680-684)
         CK(launch_rmsnorm_fplanes(x, n, ED, L.attn_norm, nullptr, c.enc_eps, xp, l ? sl : nullptr,
                                   l ? skl_splits(EH, ED) : 0, st, l ? m->enc[l - 1].b2 : nullptr));
         CK(launch_gemm_skl(xp, ED, F.wqkv, L.sqkv, NQKV, n, sl, st));
         // QKV slabs + biases -> RoPE -> K/V append (one pass), attention with its output
         // merged straight into the wo planes
-        CK(launch_slabs_rope_kv(sl, skl_splits(ED, NQKV), n, L.bqkv, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
+        CK(launch_slabs_rope_kv(sl, skl_splits(ED, NQKV), n, L.bqkv, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st,
+                                s->ekvt));
         CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale, st,
-                             s->gws, s->gws_n, xp));
+                             s->gws, s->gws_n, xp, s->ekvt));
         CK(launch_gemm_skl(xp, EQ, F.wo, L.so, ED, n, sl, st));
         // wo residual (+ bias) then the FFN RMSNorm -> planes (encoder.c:640-650)
         CK(launch_rmsnorm_fplanes(x, n, ED, L.ffn_norm, nullptr, c.enc_eps, xp, sl, skl_splits(EQ, ED), st, L.bo));
@@ -1740,19 +1785,19 @@ static int run_encoder_row_gemv(vox_hip_stream_t* s, float* x, long long pos0, c
     hipStream_t st = s->st;
     for (int l = 0; l < c.enc_layers; l++) {
         const EncLayerD& L = m->enc[l];
-        float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-        float* Vc = s->ev + (size_t)l * s->ecap * EKV;
+        float* Kc = enc_ring(s, s->ek, l);
+        float* Vc = enc_ring(s, s->ev, l);
         GemvArgs a;
         // RMSNorm -> QKV + bias -> RoPE -> K/V append (encoder.c:562-607)
         memset(&a, 0, sizeof a);
         a.x = x; a.K = ED; a.W = L.wqkv; a.wscale = L.sqkv; a.rows = EQ + 2 * EKV; a.bias = L.bqkv;
         a.norm_w = L.attn_norm; a.eps = c.enc_eps; a.y = s->q;
         a.qd = EQ; a.kvd = EKV; a.hd = hd; a.pos = (int)pos0; a.rope = rope - (size_t)pos0 * hd;
-        a.Kc = Kc; a.Vc = Vc; a.cap = s->ecap;
+        a.Kc = Kc; a.Vc = Vc; a.cap = s->ecap; a.kvt = s->ekvt;
         CK(launch_gemv(PRO_NORM, EPI_QKV_BIAS, a, st));
         // windowed attention of the one query (encoder.c:609-638)
         CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, 1, H, KVH, (int)pos0, 0, c.enc_window, scale,
-                               st, s->gws, s->gws_n));
+                               st, s->gws, s->gws_n, nullptr, s->ekvt));
         // wo + bias residual (encoder.c:640-644)
         memset(&a, 0, sizeof a);
         a.x = s->att; a.K = EQ; a.W = L.wo; a.wscale = L.so; a.rows = ED; a.bias = L.bo; a.y = x;
@@ -1784,17 +1829,21 @@ static int run_encoder_rows(vox_hip_stream_t* s, float* x, int n, long long pos0
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = s->st;
     if (n > ENC_SUB) return set_err("encoder pass of %d rows > %d", n, ENC_SUB);
-    if (n == 1 && enc_gemv_ok(m)) return run_encoder_row_gemv(s, x, pos0, rope);
+    if (n == 1 && enc_gemv_ok(m)) {
+        s->enc_paths[0]++;
+        return run_encoder_row_gemv(s, x, pos0, rope);
+    }
     if (n <= enc_skinny_rows() && enc_skinny_env() && enc_skinny_ok(c)) return run_encoder_rows_skinny(s, x, n, pos0, rope);
+    s->enc_paths[3]++;
     const bool gf = enc_gemmf_ok(m, n);
     if (gf && stream_enc_planes(s)) return -1;
     // RoPE + K/V append (encoder.c:562-607), windowed attention (:609-638)
     if (rows_layers(m, enc_rows_stack(c), enc_rows_scratch(s, x), stream_gemmfq(s), gf, n, [&](int l, uint16_t* planes) -> int {
-            float* Kc = s->ek + (size_t)l * s->ecap * EKV;
-            float* Vc = s->ev + (size_t)l * s->ecap * EKV;
-            CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st));
+            float* Kc = enc_ring(s, s->ek, l);
+            float* Vc = enc_ring(s, s->ev, l);
+            CK(launch_rope_kv(s->qkv, n, EQ, EKV, hd, rope, (int)pos0, s->q, Kc, Vc, s->ecap, st, s->ekvt));
             CK(launch_attn_rows_mf(hd, s->q, EQ, Kc, Vc, s->ecap, s->att, EQ, n, H, KVH, (int)pos0, 0, c.enc_window, scale,
-                                   st, s->gws, s->gws_n, planes));
+                                   st, s->gws, s->gws_n, planes, s->ekvt));
             return 0;
         }))
         return -1;
@@ -2080,12 +2129,13 @@ static int run_encoder_rows_batch(vox_hip_stream_t* lead, float* X, int N, vox_h
     // every stream's RoPE + K/V append and attention in one launch each (row offsets)
     if (rows_layers(m, enc_rows_stack(c), enc_rows_scratch(lead, X), stream_gemmfq(lead), gf, N, [&](int l, uint16_t* planes) -> int {
             for (int b = 0; b < B; b++) {
-                er.Kc[b] = ss[b]->ek + (size_t)l * ss[b]->ecap * EKV;
-                er.Vc[b] = ss[b]->ev + (size_t)l * ss[b]->ecap * EKV;
+                er.Kc[b] = enc_ring(ss[b], ss[b]->ek, l);
+                er.Vc[b] = enc_ring(ss[b], ss[b]->ev, l);
             }
-            CK(launch_rope_kv_rows(lead->qkv, N, EQ, EKV, hd, m->rope_enc, er, lead->q, lead->ecap, st));
+            // (one ring type per pass: vox_hip_stream_encode_mel_batch groups the streams by it)
+            CK(launch_rope_kv_rows(lead->qkv, N, EQ, EKV, hd, m->rope_enc, er, lead->q, lead->ecap, st, lead->ekvt));
             CK(launch_attn_rows(hd, lead->q, er, N, lead->ecap, lead->att, H, KVH, c.enc_window, scale, lead->gws,
-                                lead->gws_n, st, planes));
+                                lead->gws_n, st, planes, lead->ekvt));
             return 0;
         }))
         return -1;
@@ -2099,16 +2149,11 @@ static int run_encoder_rows_batch(vox_hip_stream_t* lead, float* X, int N, vox_h
 // downsample + adapter on its own queue; HIP events order the queues.  Falls back to one
 // stream at a time when the stacked rows exceed one pass (ENC_SUB).  added[b] = adapter rows
 // appended to stream b.  Synchronous unless every stream is in async-encode mode.
-extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, const float* const* mels, const int* n,
-                                               int B, int mel_on_device, int* added) {
-    if (B < 1 || !ss || !mels || !n || !added) return set_err("encode_mel_batch: bad arguments");
-    if (B > VOX_MAX_BATCH) return set_err("encode_mel_batch: at most %d streams", VOX_MAX_BATCH);
-    for (int b = 0; b < B; b++) {
-        if (!ss[b] || ss[b]->m != ss[0]->m || ss[b]->ecap != ss[0]->ecap)
-            return set_err("encode_mel_batch: streams of one model");
-        for (int j = 0; j < b; j++)
-            if (ss[j] == ss[b]) return set_err("encode_mel_batch: stream listed twice");
-    }
+// encode_mel_batch_pass: the streams of one encoder ring type (one stacked pass, ss[0] leads).
+// sync: wait for every stream's queue at the end unless all of them are in async-encode mode
+// (false: the caller, which holds the whole list, does)
+static int encode_mel_batch_pass(vox_hip_stream_t* const* ss, const float* const* mels, const int* n, int B,
+                                 int mel_on_device, int* added, bool sync = true) {
     vox_hip_stream_t* lead = ss[0];
     const vox_hip_config_t& c = lead->m->c;
     const int ED = c.enc_dim;
@@ -2184,6 +2229,47 @@ extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, cons
         if (enc_suffix_batch(lead, lead->xbatch, ss, T1.data(), off.data(), B, added)) return -1;
         CK(hipEventRecord(lead->sev, lead->st));
         for (int b = 1; b < B; b++) CK(hipStreamWaitEvent(ss[b]->st, lead->sev, 0));
+    }
+    if (sync && !all_async)
+        for (int b = 0; b < B; b++) CK(hipStreamSynchronize(ss[b]->st));
+    return 0;
+}
+
+// A list that mixes encoder ring types (vox_hip_model_set_enc_kv_fp16 between the streams'
+// creations): one stacked pass per type, each over its streams in list order with the type's
+// first stream leading, the f32 group or the half group first by which the list names first.
+// Every stream's own queue carries its work as in a single pass, and added[] keeps list order.
+// Synchronous unless every listed stream, of either type, is in async-encode mode.
+extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, const float* const* mels, const int* n,
+                                               int B, int mel_on_device, int* added) {
+    if (B < 1 || !ss || !mels || !n || !added) return set_err("encode_mel_batch: bad arguments");
+    if (B > VOX_MAX_BATCH) return set_err("encode_mel_batch: at most %d streams", VOX_MAX_BATCH);
+    bool mixed = false, all_async = true;
+    for (int b = 0; b < B; b++) {
+        if (!ss[b] || ss[b]->m != ss[0]->m || ss[b]->ecap != ss[0]->ecap)
+            return set_err("encode_mel_batch: streams of one model");
+        all_async = all_async && ss[b]->enc_async;
+        for (int j = 0; j < b; j++)
+            if (ss[j] == ss[b]) return set_err("encode_mel_batch: stream listed twice");
+        mixed = mixed || ss[b]->ekvt != ss[0]->ekvt;
+    }
+    if (!mixed) return encode_mel_batch_pass(ss, mels, n, B, mel_on_device, added);
+    for (int pass = 0; pass < 2; pass++) {
+        // pass 0: the streams of ss[0]'s type; pass 1: the others
+        std::vector<vox_hip_stream_t*> gs;
+        std::vector<const float*> gm;
+        std::vector<int> gn, gi;
+        for (int b = 0; b < B; b++)
+            if ((ss[b]->ekvt == ss[0]->ekvt) == (pass == 0)) {
+                gs.push_back(ss[b]);
+                gm.push_back(mels[b]);
+                gn.push_back(n[b]);
+                gi.push_back(b);
+            }
+        std::vector<int> ga(gs.size(), 0);
+        if (encode_mel_batch_pass(gs.data(), gm.data(), gn.data(), (int)gs.size(), mel_on_device, ga.data(), false))
+            return -1;
+        for (size_t i = 0; i < gi.size(); i++) added[gi[i]] = ga[i];
     }
     if (!all_async)
         for (int b = 0; b < B; b++) CK(hipStreamSynchronize(ss[b]->st));
@@ -2701,6 +2787,36 @@ extern "C" int vox_hip_stream_read_kv(vox_hip_stream_t* s, int layer, int first,
         for (int i = 0; i < n;) {
             const int slot = (first + i) % s->dcap;
             const int run = std::min(n - i, s->dcap - slot);  // up to the ring's end
+            CK(hipMemcpy(static_cast<char*>(outs[w]) + (size_t)i * row, ring + (size_t)slot * row, (size_t)run * row,
+                         hipMemcpyDeviceToHost));
+            i += run;
+        }
+    }
+    return 0;
+}
+
+// The encoder twin of vox_hip_stream_read_kv: raw ring elements of logical encoder positions
+// [first, first + n) of one encoder layer, in the stream's element type (f32 or IEEE half),
+// [n][enc_kv_heads * enc_head_dim] each.  Waits for the stream's queue.
+extern "C" int vox_hip_stream_read_enc_kv(vox_hip_stream_t* s, int layer, int first, int n, void* k_out, void* v_out) {
+    if (!s) return set_err("read_enc_kv: null stream");
+    const vox_hip_config_t& c = s->m->c;
+    const long long pos = s->enc_pos;
+    if (layer < 0 || layer >= c.enc_layers) return set_err("read_enc_kv: layer %d of %d", layer, c.enc_layers);
+    if (n < 0 || first < 0 || (long long)first + n > pos)
+        return set_err("read_enc_kv: positions [%d, %d + %d) not appended yet (stream at %lld)", first, first, n, pos);
+    if (first < pos - s->ecap)
+        return set_err("read_enc_kv: position %d already overwritten (stream at %lld, ring of %d)", first, pos, s->ecap);
+    CK(hipStreamSynchronize(s->st));
+    const size_t row = (size_t)c.enc_kv_heads * c.enc_head_dim * kv_esize(s->ekvt);
+    void* outs[2] = {k_out, v_out};
+    float* bases[2] = {s->ek, s->ev};
+    for (int w = 0; w < 2; w++) {
+        if (!outs[w]) continue;
+        const char* ring = reinterpret_cast<const char*>(enc_ring(s, bases[w], layer));
+        for (int i = 0; i < n;) {
+            const int slot = (first + i) % s->ecap;
+            const int run = std::min(n - i, s->ecap - slot);  // up to the ring's end
             CK(hipMemcpy(static_cast<char*>(outs[w]) + (size_t)i * row, ring + (size_t)slot * row, (size_t)run * row,
                          hipMemcpyDeviceToHost));
             i += run;

@@ -159,11 +159,13 @@ hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, cons
 hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc, const float* Vc,
                              int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0,
                              int k_first, int window, float scale, hipStream_t st, float* ws = nullptr,
-                             size_t ws_elems = 0, uint16_t* xs = nullptr, int kvt = 0);
+                             size_t ws_elems = 0, uint16_t* xs = nullptr, int kvt = 0, int* ns_out = nullptr);
+// ns_out: the number of key-range splits the launch took (> 1: split grid + combine)
 // xs: the output also (or only, through the combine kernel) as fragment-major planes
 // the skinny encoder's QKV slabs (+ bias) -> RoPE'd q rows and the K/V ring slots (one pass)
 hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bias, int qd, int kvd, int hd,
-                                const float* rope, int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st);
+                                const float* rope, int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st,
+                                int kvt = 0);
 hipError_t launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t st);
 const void* gemv_kernel(int pro, int epi, const GemvArgs& a);
 hipError_t launch_gemv_timed(int pro, int epi, const GemvArgs& a, hipEvent_t start, hipEvent_t stop,
@@ -213,8 +215,10 @@ struct EncRows {
     float* Vc[VOX_MAX_BATCH];
 };
 // RoPE + K/V append of every stacked row into its stream's ring (k_rope_kv per row block)
-// kvt (here and in launch_attn_rows): the rings' element type, KV_F32 for the encoder's; the
-// decoder's 16-bit and one-byte rings at head_dim 128 only, er.Kc / er.Vc then point at them
+// kvt (here and in launch_attn_rows): the rings' element type, er.Kc / er.Vc point at such
+// elements.  The decoder's 16-bit and one-byte rings at head_dim 128 only; the encoder's opt-in
+// 16-bit rings (vox_hip_model_set_enc_kv_fp16) at head_dim 64.  KV_FP8 at head_dim 64 is refused:
+// there is no one-byte encoder ring.
 hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd, const float* rope_table,
                                const EncRows& er, float* q, int cap, hipStream_t st, int kvt = 0);
 // windowed attention of every stream's rows against its own ring, one launch (+ one combine):
@@ -335,6 +339,7 @@ struct SklFused {
     float* q = nullptr;
     float* Kc = nullptr;
     float* Vc = nullptr;
+    int kvt = 0;                  // SKX_EPI_QKV: the ring element, KV_F32 or KV_F16 (the encoder's rings)
 };
 // column slices of a k_sklx launch (the ssq_out slices its consumer sums)
 int sklx_slices(int N, int K);

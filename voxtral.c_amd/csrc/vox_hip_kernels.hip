@@ -96,6 +96,15 @@ template <class T> __device__ __forceinline__ void kv_st2(T* p, float a, float b
         *reinterpret_cast<uint16_t*>(p) = (uint16_t)kv8_enc2(a, b);
     }
 }
+// A value as the f32 it rounds to, before a half store.  Without it the compiler folds a roped
+// key's last fma and the conversion into v_fma_mixlo_f16, which rounds the exact fma once: at an
+// f32 value that lies halfway between two halves the stored half is then not the nearest-even
+// rounding of the f32 ring's element.  The encoder's half instances store kv_f32(...) values, so
+// their rings hold half(f32 element) bit for bit; the decoder's instances are as they were.
+__device__ __forceinline__ float kv_f32(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 // element e of a ring (f32, half or fp8 by the element type) written as the pair (a, b) at e, e + 1
 __device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float b, int kvt) {
     if (kvt == KV_FP8) kv_st2(reinterpret_cast<kv8_t*>(base) + e, a, b);
@@ -433,7 +442,8 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
 // RoPE + KV append for M>1 rows (voxtral_encoder.c:580-607, voxtral_decoder.c:531-541).
 // qkv [M, qd + 2*kvd] -> q [M, qd] roped; K/V ring slots (pos0 + i) % cap.
 // ============================================================================
-template <class KT>
+// F32R: the roped key pair is rounded to f32 before the store (kv_f32; the encoder's half rings)
+template <class KT, int F32R = 0>
 __global__ __launch_bounds__(256) void k_rope_kv(const float* __restrict__ qkv, int M, int qd,
                                                  int kvd, int hd, const float* __restrict__ rope,
                                                  int pos0, float* __restrict__ q,
@@ -457,7 +467,8 @@ __global__ __launch_bounds__(256) void k_rope_kv(const float* __restrict__ qkv, 
         int d = (2 * p) % hd / 2;
         float c = rp[2 * d], s = rp[2 * d + 1];
         float x0 = row[qd + 2 * p], x1 = row[qd + 2 * p + 1];
-        kv_st2(kr + 2 * p, x0 * c - x1 * s, x0 * s + x1 * c);
+        if constexpr (F32R) kv_st2(kr + 2 * p, kv_f32(x0 * c - x1 * s), kv_f32(x0 * s + x1 * c));
+        else kv_st2(kr + 2 * p, x0 * c - x1 * s, x0 * s + x1 * c);
     }
     for (int p = threadIdx.x; p < kvd / 2; p += 256) kv_st2(vr + 2 * p, row[qd + kvd + 2 * p], row[qd + kvd + 2 * p + 1]);
 }
@@ -466,7 +477,7 @@ __global__ __launch_bounds__(256) void k_rope_kv(const float* __restrict__ qkv, 
 // from the row offsets (same operations per row as k_rope_kv).  KT: the ring element (float for
 // the encoder's rings; the decoder's stacked prefill takes its streams' type, er.Kc / er.Vc
 // being layer bases in bytes whatever they point at)
-template <class KT>
+template <class KT, int F32R = 0>
 __global__ __launch_bounds__(256) void k_rope_kv_rows(const float* __restrict__ qkv, int qd, int kvd, int hd,
                                                       const float* __restrict__ rope_table, const EncRows er,
                                                       float* __restrict__ q, int cap) {
@@ -491,7 +502,8 @@ __global__ __launch_bounds__(256) void k_rope_kv_rows(const float* __restrict__ 
         int d = (2 * p) % hd / 2;
         float c = rp[2 * d], sn = rp[2 * d + 1];
         float x0 = xr[qd + 2 * p], x1 = xr[qd + 2 * p + 1];
-        kv_st2(kr + 2 * p, x0 * c - x1 * sn, x0 * sn + x1 * c);
+        if constexpr (F32R) kv_st2(kr + 2 * p, kv_f32(x0 * c - x1 * sn), kv_f32(x0 * sn + x1 * c));
+        else kv_st2(kr + 2 * p, x0 * c - x1 * sn, x0 * sn + x1 * c);
     }
     for (int p = threadIdx.x; p < kvd / 2; p += 256) kv_st2(vr + 2 * p, xr[qd + kvd + 2 * p], xr[qd + kvd + 2 * p + 1]);
 }
@@ -1149,6 +1161,10 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
                         a.y[er0] = o0;
                         a.y[er1] = o1;
                     } else {
+                        // (o0 / o1 are f32 values here: shared with the q store above and passed through
+                        // the runtime kvt switch, no k_gemv instance folds them into v_fma_mixlo_f16 -- see
+                        // kv_f32; this kernel is the decoder's too, so it carries no barrier of its own,
+                        // and tests/test_gpu_enc_kv16.py holds the encoder's one-row path to the exact rule)
                         kv_st2_rt(a.Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kvt);
                     }
                 } else {
@@ -2523,7 +2539,9 @@ __global__ __launch_bounds__(256) void k_resid_slabs(float* __restrict__ x, int 
 
 // QKV slabs of row blockIdx.x summed in split order (+ bias), RoPE of q and k, K/V append at
 // ring slot (pos0 + i) % cap: k_slabs_rows + k_rope_kv in one pass with the same operations
-// in the same order (voxtral_encoder.c:570-607).  rope: the row of position pos0.
+// in the same order (voxtral_encoder.c:570-607).  rope: the row of position pos0.  KT: the ring
+// element (float, or kvh_t for the encoder's opt-in 16-bit rings: kv_st2's rounding)
+template <class KT = float>
 __global__ __launch_bounds__(256) void k_slabs_rope_kv(const float* __restrict__ part, int S,
                                                        const float* __restrict__ bias, int qd, int kvd, int hd,
                                                        const float* __restrict__ rope, int pos0,
@@ -2545,12 +2563,23 @@ __global__ __launch_bounds__(256) void k_slabs_rope_kv(const float* __restrict__
         x1 += bb.y;
     }
     if (n >= qd + kvd) {
+        if constexpr (sizeof(KT) != 4) {
+            kv_st2(reinterpret_cast<KT*>(Vc) + (size_t)slot * kvd + (n - qd - kvd), x0, x1);
+            return;
+        }
         float* vr = Vc + (size_t)slot * kvd + (n - qd - kvd);
         vr[0] = x0;
         vr[1] = x1;
         return;
     }
     const float c = cs.x, s = cs.y;  // qd is a multiple of hd: the pair's rope index n % hd / 2
+    if constexpr (sizeof(KT) != 4) {
+        if (n >= qd) {
+            kv_st2(reinterpret_cast<KT*>(Kc) + (size_t)slot * kvd + (n - qd), kv_f32(x0 * c - x1 * s),
+                   kv_f32(x0 * s + x1 * c));
+            return;
+        }
+    }
     float* dst = n < qd ? q + (size_t)i * qd + n : Kc + (size_t)slot * kvd + (n - qd);
     dst[0] = x0 * c - x1 * s;
     dst[1] = x0 * s + x1 * c;
@@ -3347,7 +3376,9 @@ __global__ __launch_bounds__(256) void k_swiglu_fplanes(const float* __restrict_
 // projections.  Same grid, planes and MFMA loop as k_skl (bf16 weights, or the wmx4 fragment
 // plane for the batched decode step's W1|W3); see SklFused.
 // ============================================================================
-template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16>
+// KT: the ring element of the SKX_EPI_QKV append (float, or kvh_t for the encoder's opt-in 16-bit
+// rings; SklFused::kvt picks the instance)
+template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16, class KT = float>
 __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ xs, int K,
                                                   const uint8_t* __restrict__ W, int N, int nb, const SklFused f) {
     __shared__ uint4 xb[KS * 6 * 64];  // [block][plane][half][lane]
@@ -3545,10 +3576,21 @@ __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ x
                 x1 += bb.y;
             }
             if (n >= f.qd + f.kvd) {
+                if constexpr (sizeof(KT) != 4) {
+                    kv_st2(reinterpret_cast<KT*>(f.Vc) + (size_t)slot * f.kvd + (n - f.qd - f.kvd), x0, x1);
+                    continue;
+                }
                 float* vr = f.Vc + (size_t)slot * f.kvd + (n - f.qd - f.kvd);
                 vr[0] = x0;
                 vr[1] = x1;
                 continue;
+            }
+            if constexpr (sizeof(KT) != 4) {
+                if (n >= f.qd) {
+                    kv_st2(reinterpret_cast<KT*>(f.Kc) + (size_t)slot * f.kvd + (n - f.qd), kv_f32(x0 * cs.x - x1 * cs.y),
+                           kv_f32(x0 * cs.y + x1 * cs.x));
+                    continue;
+                }
             }
             float* dst = n < f.qd ? f.q + (size_t)i * f.qd + n : f.Kc + (size_t)slot * f.kvd + (n - f.qd);
             dst[0] = x0 * cs.x - x1 * cs.y;
@@ -3843,6 +3885,8 @@ hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, cons
     if (kvd % 2 || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
     if (kvt == KV_FP8)
         hipLaunchKernelGGL(k_rope_kv<kv8_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
+    else if (kvt == KV_F16 && hd == 64)  // the encoder's rings
+        hipLaunchKernelGGL((k_rope_kv<kvh_t, 1>), dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
     else if (kvt == KV_F16)
         hipLaunchKernelGGL(k_rope_kv<kvh_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
     else
@@ -3857,9 +3901,12 @@ hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd,
                                const EncRows& er, float* q, int cap, hipStream_t st, int kvt) {
     if (N <= 0) return hipSuccess;
     if (er.B < 1 || er.B > VOX_MAX_BATCH || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
-    if (kvt != KV_F32 && (hd != 128 || kvd % 2)) return hipErrorInvalidValue;
+    // narrow rings: the decoder's at head_dim 128; IEEE half also at 64 (the encoder's opt-in rings)
+    if (kvt != KV_F32 && ((hd != 128 && !(kvt == KV_F16 && hd == 64)) || kvd % 2)) return hipErrorInvalidValue;
     if (kvt == KV_FP8)
         hipLaunchKernelGGL(k_rope_kv_rows<kv8_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
+    else if (kvt == KV_F16 && hd == 64)  // the encoder's rings
+        hipLaunchKernelGGL((k_rope_kv_rows<kvh_t, 1>), dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
     else if (kvt == KV_F16)
         hipLaunchKernelGGL(k_rope_kv_rows<kvh_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
     else
@@ -3883,7 +3930,8 @@ hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, in
                             int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs, int kvt) {
     if (N <= 0) return hipSuccess;
     if (er.B < 1 || er.B > VOX_MAX_BATCH || (hd != 64 && hd != 128)) return hipErrorInvalidValue;
-    if (kvt < KV_F32 || kvt > KV_FP8 || (kvt != KV_F32 && hd != 128)) return hipErrorInvalidValue;
+    if (kvt < KV_F32 || kvt > KV_FP8 || (kvt != KV_F32 && hd != 128 && !(kvt == KV_F16 && hd == 64)))
+        return hipErrorInvalidValue;
     if (xs && N > PLANE_MAX_ROWS) return hipErrorInvalidValue;
     int qbm = 0, keys = 0;
     for (int b = 0; b < er.B; b++) {
@@ -3902,9 +3950,14 @@ hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, in
     }
     dim3 grid(H, qbm, ns * er.B);
     // xs: the output rows as the wo input's planes (by the attention itself, or by the combine)
-    // (a 16-bit or one-byte ring: planes by k_split_fplanes after the kernel, as launch_attn_rows_mf)
-    uint16_t* kxs = ns == 1 && kvt == KV_F32 && att_planes() ? xs : nullptr;
-    if (kvt == KV_FP8)
+    // (a 16-bit or one-byte decoder ring: planes by k_split_fplanes after the kernel, as
+    // launch_attn_rows_mf; the encoder's 16-bit ring, head_dim 64, writes them itself like f32)
+    const bool enc16 = kvt == KV_F16 && hd == 64;
+    uint16_t* kxs = ns == 1 && (kvt == KV_F32 || enc16) && att_planes() ? xs : nullptr;
+    if (enc16)
+        hipLaunchKernelGGL((k_attn_mf<64, kvh_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O, H * hd,
+                           N, H, KVH, 0, 0, window, scale, ns, ws, er, kxs);
+    else if (kvt == KV_FP8)
         hipLaunchKernelGGL((k_attn_mf<128, kv8_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
                            H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, nullptr);
     else if (kvt == KV_F16)
@@ -3932,7 +3985,8 @@ hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, in
 hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc, const float* Vc,
                              int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0,
                              int k_first, int window, float scale, hipStream_t st, float* ws, size_t ws_elems,
-                             uint16_t* xs, int kvt) {
+                             uint16_t* xs, int kvt, int* ns_out) {
+    if (ns_out) *ns_out = 0;
     if (M <= 0) return hipSuccess;
     if ((hd != 64 && hd != 128) || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
     if (xs && (M > PLANE_MAX_ROWS || ldo != H * hd)) return hipErrorInvalidValue;
@@ -3953,7 +4007,13 @@ hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc,
         while (ns > 1 && (size_t)H * M * ns * (hd + 2) > ws_elems) ns--;
     }
     dim3 grid(H, qb, ns);
-    if (kvt == KV_FP8) {
+    if (ns_out) *ns_out = ns;
+    const bool enc16 = kvt == KV_F16 && hd == 64;
+    if (enc16) {
+        // the encoder's opt-in 16-bit ring: the f32 instance's grid, splits and plane output
+        hipLaunchKernelGGL((k_attn_mf<64, kvh_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0,
+                           k_first, window, scale, ns, ws, EncRows{}, ns == 1 && att_planes() ? xs : nullptr);
+    } else if (kvt == KV_FP8) {
         // the one-byte decoder ring (prefill)
         if (hd != 128) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_attn_mf<128, kv8_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH,
@@ -3978,17 +4038,23 @@ hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc,
         else
             hipLaunchKernelGGL(k_attn_tiled_combine<128>, dim3(H, M), dim3(128), 0, st, ws, ns, M, O, ldo, xs);
         LAUNCH_CHECK();
-    } else if (xs && (kvt != KV_F32 || !att_planes())) {
+    } else if (xs && ((kvt != KV_F32 && !enc16) || !att_planes())) {
         return launch_split_fplanes(O, M, H * hd, xs, st);
     }
     return hipSuccess;
 }
 
 hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bias, int qd, int kvd, int hd,
-                                const float* rope, int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st) {
+                                const float* rope, int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st,
+                                int kvt) {
     if (M <= 0) return hipSuccess;
     if (M > SK_MAX_ROWS || S < 1 || qd % hd || kvd % hd || hd % 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_slabs_rope_kv, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias, qd, kvd,
+    if (kvt != KV_F32 && kvt != KV_F16) return hipErrorInvalidValue;  // no one-byte instance
+    if (kvt == KV_F16)
+        hipLaunchKernelGGL(k_slabs_rope_kv<kvh_t>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias,
+                           qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
+    else
+        hipLaunchKernelGGL(k_slabs_rope_kv<float>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias, qd, kvd,
                        hd, rope, pos0, q, Kc, Vc, cap);
     LAUNCH_CHECK();
     return hipSuccess;
@@ -4793,13 +4859,13 @@ static int sklx_nw(int N, int K) {
 
 int sklx_slices(int N, int K) { return N / (16 * sklx_nw(N, K)); }
 
-template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16>
+template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16, class KT = float>
 static hipError_t sklx_launch(const uint16_t* xs, int K, const void* W, int N, int nb, const SklFused& f,
                               hipStream_t st) {
     const int units = (N / (16 * NW)) * (K / (64 * KS));
     const int Z = (nb + SK_ROWS - 1) / SK_ROWS;
     const int grid = Z > 1 ? (units + 7) / 8 * 8 * Z : units;
-    hipLaunchKernelGGL((k_sklx<NW, KS, PRO, EPI, WF>), dim3(grid), dim3(NW * 64), 0, st, xs, K,
+    hipLaunchKernelGGL((k_sklx<NW, KS, PRO, EPI, WF, KT>), dim3(grid), dim3(NW * 64), 0, st, xs, K,
                        static_cast<const uint8_t*>(W), N, nb, f);
     return hipGetLastError();
 }
@@ -4818,6 +4884,8 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
     if (epi == SKX_EPI_QKV && (!f.q || !f.Kc || !f.Vc || !f.rope || f.hd % 2 || f.qd % f.hd || f.cap < 1 ||
                                N != f.qd + 2 * f.kvd))
         return hipErrorInvalidValue;
+    // the append's ring element: f32, or IEEE half with the QKV epilogue (no one-byte instance)
+    if (f.kvt != KV_F32 && (f.kvt != KV_F16 || epi != SKX_EPI_QKV || mx4 || f.kvd % 2)) return hipErrorInvalidValue;
 #define SKX_CFG(PP, EE) SKX_X(4, 4, PP, EE) SKX_X(4, 8, PP, EE) SKX_X(8, 4, PP, EE) SKX_X(8, 8, PP, EE)
     if (mx4) {
         // the wmx4 fragment plane: the batched decode step's W1|W3 only
@@ -4829,6 +4897,17 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
     }
 #define SKX_X(NWW, KSS, PP, EE) \
     if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE>(xs, K, Wf, N, nb, f, st);
+    if (f.kvt == KV_F16) {
+#define SKX_H(NWW, KSS, PP, EE) \
+    if (nw == NWW && ks == KSS && pro == PP && epi == EE) \
+        return sklx_launch<NWW, KSS, PP, EE, WF_BF16, kvh_t>(xs, K, Wf, N, nb, f, st);
+#define SKX_HCFG(PP, EE) SKX_H(4, 4, PP, EE) SKX_H(4, 8, PP, EE) SKX_H(8, 4, PP, EE) SKX_H(8, 8, PP, EE)
+        SKX_HCFG(SKX_PRO_PLANES, SKX_EPI_QKV)
+        SKX_HCFG(SKX_PRO_SCALE, SKX_EPI_QKV)
+#undef SKX_HCFG
+#undef SKX_H
+        return hipErrorInvalidValue;
+    }
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_SCALE, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_RESID)

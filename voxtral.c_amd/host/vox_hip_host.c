@@ -1088,6 +1088,13 @@ int vh_set_kv_dtype(vh_ctx_t *ctx, int dtype) {
 
 int vh_stream_kv_dtype(const vh_stream_t *s) { return vox_hip_stream_kv_dtype(s->st); }
 
+int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on) {
+    if (vox_hip_model_set_enc_kv_fp16(ctx->model, on)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_stream_enc_kv_fp16(const vh_stream_t *s) { return vox_hip_stream_enc_kv_fp16(s->st); }
+
 int vh_stream_pending(vh_stream_t *s) {
     int st6[6];
     vox_hip_stream_state(s->st, st6);

@@ -122,6 +122,8 @@ EXPORTS = [
     "vox_hip_model_create", "vox_hip_model_free", "vox_hip_model_set_delay",
     "vox_hip_model_ada_scale", "vox_hip_model_set_kv_fp16", "vox_hip_stream_kv_fp16",
     "vox_hip_model_set_kv_dtype", "vox_hip_stream_kv_dtype", "vox_hip_stream_read_kv", "vox_hip_kv8_convert",
+    "vox_hip_model_set_enc_kv_fp16", "vox_hip_stream_enc_kv_fp16", "vox_hip_stream_read_enc_kv",
+    "vox_hip_stream_enc_kv_bytes", "vox_hip_stream_enc_paths",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
@@ -171,6 +173,10 @@ def lib():
         "vox_hip_model_set_kv_fp16": (I, [P, I]), "vox_hip_stream_kv_fp16": (I, [P]),
         "vox_hip_model_set_kv_dtype": (I, [P, I]), "vox_hip_stream_kv_dtype": (I, [P]),
         "vox_hip_stream_read_kv": (I, [P, I, I, I, P, P]),
+        "vox_hip_model_set_enc_kv_fp16": (I, [P, I]), "vox_hip_stream_enc_kv_fp16": (I, [P]),
+        "vox_hip_stream_read_enc_kv": (I, [P, I, I, I, P, P]),
+        "vox_hip_stream_enc_kv_bytes": (ctypes.c_longlong, [P]),
+        "vox_hip_stream_enc_paths": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_kv8_convert": (I, [fp, I, P, fp]),
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
@@ -397,6 +403,12 @@ class Model:
         if lib().vox_hip_model_set_kv_dtype(self.h, int(dtype)) != 0:
             _err("set_kv_dtype")
 
+    def set_enc_kv_fp16(self, on: bool):
+        """vox_hip_model_set_enc_kv_fp16: streams created afterwards keep their encoder K/V rings
+        in IEEE half (half the ring's bytes; f32 arithmetic; quality not evaluated)"""
+        if lib().vox_hip_model_set_enc_kv_fp16(self.h, int(on)) != 0:
+            _err("set_enc_kv_fp16")
+
     def wpack_stats(self) -> dict:
         """What the single-stream decode GEMV streams as wpack13 planes (13 bits per bf16
         weight, lossless) and what stayed raw: tensor counts, bytes, host packing time"""
@@ -516,6 +528,36 @@ class Stream:
             return k, v
         if dt is np.uint8:
             return kv8_decode(k), kv8_decode(v)
+        return k.astype(np.float32), v.astype(np.float32)
+
+    @property
+    def enc_kv_fp16(self) -> bool:
+        """True when the stream's encoder K/V rings hold IEEE half (Model.set_enc_kv_fp16)"""
+        return bool(lib().vox_hip_stream_enc_kv_fp16(self.h))
+
+    @property
+    def enc_kv_bytes(self) -> int:
+        """bytes of the stream's encoder K and V rings together"""
+        return int(lib().vox_hip_stream_enc_kv_bytes(self.h))
+
+    def enc_paths(self) -> dict:
+        """vox_hip_stream_enc_paths: this stream's encoder passes by the path they took"""
+        out = (ctypes.c_longlong * 5)()
+        if lib().vox_hip_stream_enc_paths(self.h, out) != 0:
+            _err("enc_paths")
+        return dict(zip(("gemv_row", "fused", "slab", "rows", "fused_split"), (int(v) for v in out)))
+
+    def read_enc_kv(self, layer: int, first: int, n: int, decoded: bool = False):
+        """vox_hip_stream_read_enc_kv: the K and V ring elements of logical encoder positions
+        [first, first + n) of one encoder layer, [n, enc_kv_heads * enc_head_dim] each: raw
+        (float32, or float16 on a half stream) or, decoded, widened to float32"""
+        dt = np.float16 if self.enc_kv_fp16 else np.float32
+        kvd = self.cfg.enc_kv_heads * self.cfg.enc_head_dim
+        k, v = np.empty((n, kvd), dt), np.empty((n, kvd), dt)
+        if lib().vox_hip_stream_read_enc_kv(self.h, int(layer), int(first), int(n), k.ctypes.data, v.ctypes.data) != 0:
+            _err("read_enc_kv")
+        if not decoded:
+            return k, v
         return k.astype(np.float32), v.astype(np.float32)
 
     def encode_mel(self, mel: np.ndarray) -> int:
@@ -1017,6 +1059,7 @@ def host_lib():
         "vh_sched_stats": (None, [P, ctypes.POINTER(SchedStats)]),
         "vh_sched_set_step_cap": (None, [P, I]), "vh_stream_pending": (I, [P]),
         "vh_stream_set_delay": (I, [P, I]), "vh_stream_delay_ms": (I, [P]),
+        "vh_set_enc_kv_fp16": (I, [P, I]), "vh_stream_enc_kv_fp16": (I, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(H, name)
