@@ -141,8 +141,11 @@ vh_ctx_t *vh_ctx_wrap(vox_hip_model_t *model, const vox_hip_config_t *cfg, int d
  *      own drain.
  * By default (VOX_HIP_SCHED_OVERLAP=0: off; off too while a live-mode stream is attached) step
  * 0's pass is only enqueued and steps 1-2 decode the rows that were complete when the run
- * started (vox_hip_batch_decode_rows), so the pass runs beside the batched steps; it completes
- * before the run returns and its rows are decoded by the next run.  Greedy ids do not depend
+ * started (vox_hip_batch_begin_rows / _finish around the pass's enqueue), so the pass runs
+ * beside the batched steps.  Without a step cap the run waits for the pass and drains its rows
+ * too; with one the run may return while the pass is still running, and the next run waits for
+ * every stream's queue before it counts rows and decodes them.  An adapter buffer the pass
+ * outgrows inside that window outlives the begun call (voxtral_hip.h).  Greedy ids do not depend
  * on when a row is decoded.  vh_stream_pending counts those rows.
  * Called after every round of feeds, it yields per stream the ids vh_stream_feed would have
  * queued (vh_stream_get / get_alt read them as before).  Streams with --alt (n_alt > 1) stay
@@ -180,6 +183,15 @@ void vh_sched_stats(const vh_sched_t *q, vh_sched_stats_t *out);
  * stream's vh_stream_pending is 0 to drain.  cap <= 0 (the default): every run drains every
  * stream, as vox_stream_feed does. */
 void vh_sched_set_step_cap(vh_sched_t *q, int cap);
+/* Test hook: the next encoder pass of a vh_sched_run on q (step 0) returns an error before it
+ * enqueues anything -- a host return only, no device call, the streams' deferred chunks stay
+ * deferred.  That run finishes the batched steps it had begun, queues their ids as usual and
+ * returns -1 ("encoder pass failed (vh_sched_debug_fail_next_encode)"); later runs work and no
+ * id is lost or repeated. */
+void vh_sched_debug_fail_next_encode(vh_sched_t *q);
+/* vox_hip_stream_adapter_stats (voxtral_hip.h) of the stream behind s: adapter buffer capacity
+ * in rows, its growths, and those of them inside a begun batched call.  0, or -1. */
+int vh_stream_adapter_stats(const vh_stream_t *s, long long out3[3]);
 /* The scheduler's batch on the R-row GEMV step (vox_hip_batch_set_gemv_rows: buckets of up to
  * max_rows = 0, 1, 2, 4 or 8 slots; vox_hip_batch_set_gemv_rows_q8: the same for a model with
  * Q8 step tensors) and that step on the wmx4 GEMV planes (vox_hip_batch_set_gemv_wmx4).  Each

@@ -339,6 +339,18 @@ int vox_hip_stream_ada_scale(vox_hip_stream_t *s, float *out);
 int vox_hip_stream_encode_mel(vox_hip_stream_t *s, const float *mel, int n_frames,
                               int mel_on_device);
 int vox_hip_stream_adapter_tokens(vox_hip_stream_t *s);
+/* The adapter buffer of a stream starts at 1024 rows (about 82 s of audio) and doubles when an
+ * encoder pass needs more: a larger buffer is allocated, the rows are copied, the stream's step
+ * graphs are captured again on the new address.  vox_hip_set_adapter_rows0 sets the first
+ * capacity of streams created from now on, process-wide: a power of two in 16..1024, or 0 for
+ * the default of 1024 (for tests, which reach a growth within seconds of audio; the rows and ids
+ * do not depend on it).  Host state only, callable without a device.  Returns 0; -1
+ * (vox_hip_last_error) for any other value, which leaves the setting as it was.
+ * vox_hip_stream_adapter_stats: out3[0] the stream's capacity in rows, [1] its growths so far,
+ * [2] those of them that happened while the stream was listed in a begun, unfinished batched
+ * call (vox_hip_batch_begin_rows below), where the outgrown buffer outlives the call. */
+int vox_hip_set_adapter_rows0(int rows);
+int vox_hip_stream_adapter_stats(const vox_hip_stream_t *s, long long out3[3]);
 /* on != 0: vox_hip_stream_encode_mel returns once the pass is enqueued on the stream's HIP
  * queue (its adapter-row count is known on the host); everything later on the same stream
  * (decode, read_adapter, reset) is ordered behind it and the batched step waits for every
@@ -444,7 +456,20 @@ int vox_hip_batch_decode_rows(vox_hip_batch_t *b, vox_hip_stream_t **streams, in
  * returning the total as decode_rows does.  In between the caller may enqueue work on other
  * queues -- the per-GPU scheduler enqueues the cross-stream encoder pass there, after the
  * steps, so the steps are on the device first -- but must not touch the listed streams'
- * decoder state or call another batch function on b. */
+ * decoder state or call another batch function on b.
+ * The library enforces that window.  The call's slot table names each listed stream's state,
+ * token ring, adapter buffer, KV rings, alternatives ring and ada table and is uploaded once, so
+ * between begin and finish none of them is freed or moved: encoding a listed stream
+ * (vox_hip_stream_encode_mel, _encode_mel_batch, the mel feed) stays allowed, and an adapter
+ * buffer it outgrows is kept for the call -- which reads only its rows[i] first rows, all of
+ * them in the old buffer -- and freed by finish after its last wait (or by
+ * vox_hip_batch_free).  Every entry point that would free or rewrite what the call reads, or
+ * move a listed stream's decoder, returns -1 with vox_hip_last_error naming the begun call
+ * and changes nothing: vox_hip_stream_free (void: the error only; free the stream after
+ * finish), vox_hip_stream_reset, _reset_decoder, vox_hip_stream_decode,
+ * vox_hip_decoder_prefill_step, vox_hip_decoder_full_step, vox_hip_stream_set_alt,
+ * vox_hip_stream_set_delay, listing the stream in a call of another batch object, and
+ * vox_hip_model_set_delay on the model of any begun call. */
 int vox_hip_batch_begin_rows(vox_hip_batch_t *b, vox_hip_stream_t **streams, int n, const int *rows,
                              int max_steps, int stop_at_eos, int *tokens_out, int *counts_out);
 int vox_hip_batch_finish(vox_hip_batch_t *b);

@@ -214,6 +214,7 @@ struct vox_hip_model {
     long long fstats[4];           // fragment planes: tensors, plane bytes, their bf16 bytes, host microseconds
     int gemmf_q8;                  // vox_hip_gemmf_q8() at creation: k_gemmf streams the int8 fragment copies of Q8 tensors
     long long n_gemmf_q8;          // k_gemmf launches on int8 fragments (vox_hip_model_gemmf_q8_stats)
+    int begun_calls;               // batched calls of this model between begin_rows and finish (their slots read ada_scale)
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -389,6 +390,18 @@ extern "C" int vox_hip_set_gemmf_q8(int on) {
     return 0;
 }
 extern "C" int vox_hip_gemmf_q8(void) { return gemmf_q8_mode(); }
+// first capacity (rows) of the adapter buffer of streams created from now on; it doubles from
+// there (include/voxtral_hip.h).  Host state only: no device call.
+static const int ADAPTER_ROWS0 = 1024;
+static int g_adapter_rows0 = ADAPTER_ROWS0;
+extern "C" int vox_hip_set_adapter_rows0(int rows) {
+    if (rows == 0) rows = ADAPTER_ROWS0;
+    if (rows < 16 || rows > ADAPTER_ROWS0 || (rows & (rows - 1)))
+        return set_err("adapter rows0: 0 (the default of %d) or a power of two in 16..%d (got %d)", ADAPTER_ROWS0,
+                       ADAPTER_ROWS0, rows);
+    g_adapter_rows0 = rows;
+    return 0;
+}
 
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -807,6 +820,8 @@ extern "C" int vox_hip_model_gemmf_q8_stats(const vox_hip_model_t* m, long long 
 }
 
 extern "C" int vox_hip_model_set_delay(vox_hip_model_t* m, int delay_tokens) {
+    // the slots of a begun call read the model's ada table on every step
+    if (m->begun_calls > 0) return set_err("model_set_delay: a begun call of this model was not finished");
     m->delay_tokens = delay_tokens;
     return model_update_ada(m);
 }
@@ -883,6 +898,10 @@ struct vox_hip_stream {
     // adapter
     float *adapter, *ad_mid;
     int adapter_cap, total_adapter;
+    // the begun, unfinished batched call that lists this stream (vox_hip_batch_begin_rows ..
+    // vox_hip_batch_finish), null otherwise: its slot table holds the stream's buffer pointers
+    struct vox_hip_batch* held;
+    long long ad_grows, ad_grows_held;  // adapter buffer growths / of them inside such a call
     // decoder
     float *xd, *xnd, *qkvd, *qd_, *attd, *gated, *part, *logits, *pval;
     float *part_alt, *alts;  // stream_fill_alts partials / per-step records [tokens_cap][ALT_REC]
@@ -940,17 +959,45 @@ static int stream_alloc_frames(vox_hip_stream_t* s, int frames) {
     return 0;
 }
 
+static int batch_park(struct vox_hip_batch* b, float* p);
+static const char* HELD_MSG = "the stream is in a begun call that was not finished (vox_hip_batch_finish first)";
+
+// The adapter buffer holds `need` rows: a larger one is allocated, the rows copied on the
+// stream's queue, the old one freed.  Inside a begun batched call that lists the stream
+// (s->held) the old buffer is not freed: the call's slot table holds its address and the steps
+// batch_finish has yet to enqueue read the call's rows[i] first rows through it.  All of those
+// exist there, and nothing writes the old buffer again, so the call reads the same rows it
+// would have read without the growth; the batch frees the buffer after its last wait.
 static int stream_alloc_adapter(vox_hip_stream_t* s, int need) {
     if (need <= s->adapter_cap) return 0;
     const int D = s->m->c.dec_dim;
-    int nc = s->adapter_cap ? s->adapter_cap : 1024;
+    int nc = s->adapter_cap ? s->adapter_cap : g_adapter_rows0;
     while (nc < need) nc *= 2;
     float* na = nullptr;
     CK(dalloc(&na, (size_t)nc * D));
     if (s->adapter && s->total_adapter > 0)
-        CK(hipMemcpyAsync(na, s->adapter, (size_t)s->total_adapter * D * 4, hipMemcpyDeviceToDevice, s->st));
-    CK(hipStreamSynchronize(s->st));
-    dfree(s->adapter);
+        if (hipError_t e = hipMemcpyAsync(na, s->adapter, (size_t)s->total_adapter * D * 4, hipMemcpyDeviceToDevice, s->st);
+            e != hipSuccess) {
+            dfree(na);
+            return set_err("adapter rows copy: %s", hipGetErrorString(e));
+        }
+    if (hipError_t e = hipStreamSynchronize(s->st); e != hipSuccess) {
+        dfree(na);
+        return set_err("adapter rows copy: %s", hipGetErrorString(e));
+    }
+    if (s->adapter_cap) {
+        s->ad_grows++;
+        s->ad_grows_held += s->held != nullptr;
+    }
+    if (s->held && s->adapter) {
+        if (batch_park(s->held, s->adapter)) {
+            dfree(na);
+            return -1;
+        }
+        s->adapter = nullptr;
+    } else {
+        dfree(s->adapter);
+    }
     s->adapter = na;
     s->adapter_cap = nc;
     s->graph_ready = 0;  // the step graph captured the old pointer
@@ -1031,7 +1078,7 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     TRYH(hipEventCreate(&s->evt[1]));
     TRYH(hipEventCreateWithFlags(&s->sev, hipEventDisableTiming));
 #undef TRYH
-    if (stream_alloc_frames(s, 2048) || stream_alloc_adapter(s, 1024) || stream_alloc_dec_rows(s, 64))
+    if (stream_alloc_frames(s, 2048) || stream_alloc_adapter(s, g_adapter_rows0) || stream_alloc_dec_rows(s, 64))
         return fail();
     if (vox_hip_stream_reset(s)) return fail();
     return s;
@@ -1057,6 +1104,7 @@ static const float* stream_ada(const vox_hip_stream_t* s) { return s->delay < 0 
 
 extern "C" int vox_hip_stream_set_delay(vox_hip_stream_t* s, int delay_tokens) {
     if (!s) return set_err("stream_set_delay: null stream");
+    if (s->held) return set_err("stream_set_delay: %s", HELD_MSG);
     if (delay_tokens < -1 || delay_tokens > VOX_HIP_MAX_DELAY_TOKENS)
         return set_err("stream_set_delay: %d tokens is not -1 (the model's delay) or 0..%d", delay_tokens, VOX_HIP_MAX_DELAY_TOKENS);
     if (s->started)
@@ -1114,6 +1162,11 @@ static float* dec_ring(const vox_hip_stream_t* s, float* base, int l) {
 
 extern "C" void vox_hip_stream_free(vox_hip_stream_t* s) {
     if (!s) return;
+    if (s->held) {
+        // (void: reported through vox_hip_last_error; the stream stays whole for the call)
+        set_err("stream_free: %s", HELD_MSG);
+        return;
+    }
     if (s->st) hipStreamSynchronize(s->st);
     for (int g = 0; g < STEP_GRAPHS; g++)
         if (s->step_exec[g]) hipGraphExecDestroy(s->step_exec[g]);
@@ -1135,6 +1188,7 @@ extern "C" void vox_hip_stream_free(vox_hip_stream_t* s) {
 
 extern "C" int vox_hip_stream_reset_decoder(vox_hip_stream_t* s) {
     // stream_reset_decoder_state (voxtral.c:766-783): KV length 0, adapter backlog dropped
+    if (s->held) return set_err("stream_reset_decoder: %s", HELD_MSG);
     s->total_adapter = 0;
     s->started = 0;
     s->eos_seen = 0;
@@ -1148,6 +1202,7 @@ extern "C" int vox_hip_stream_reset_decoder(vox_hip_stream_t* s) {
 
 extern "C" int vox_hip_stream_reset(vox_hip_stream_t* s) {
     // stream_reset_full_state (voxtral.c:786-814)
+    if (s->held) return set_err("stream_reset: %s", HELD_MSG);
     const vox_hip_config_t& c = s->m->c;
     s->enc_pos = 0;
     s->res_count = 0;
@@ -1851,6 +1906,12 @@ static int run_encoder_rows(vox_hip_stream_t* s, float* x, int n, long long pos0
     return 0;
 }
 
+// The model's rope tables cover last_pos.  Growing them waits for the whole device and moves
+// the tables.  An encoder pass enqueued inside a begun batched call (the scheduler's steps-first
+// order) can get here: the wait then covers the call's chunk in flight too, which is deliberate
+// -- the old tables are freed only once nothing reads them, and batch_run captures its graphs
+// again when rope_gen moved, so the later chunks read the new ones.  The overlap of that one
+// run is lost; the tables double, so this happens a handful of times per process.
 static int ensure_rope(vox_hip_stream_t* s, long long last_pos) {
     vox_hip_model_t* m = s->m;
     if (last_pos < m->rope_positions) return 0;
@@ -2307,6 +2368,14 @@ extern "C" int vox_hip_stream_set_async_encode(vox_hip_stream_t* s, int on) {
 
 extern "C" int vox_hip_stream_adapter_tokens(vox_hip_stream_t* s) { return s->total_adapter; }
 
+extern "C" int vox_hip_stream_adapter_stats(const vox_hip_stream_t* s, long long out3[3]) {
+    if (!s || !out3) return set_err("stream_adapter_stats: null argument");
+    out3[0] = s->adapter_cap;
+    out3[1] = s->ad_grows;
+    out3[2] = s->ad_grows_held;
+    return 0;
+}
+
 extern "C" int vox_hip_stream_read_adapter(vox_hip_stream_t* s, int first, int n, float* out) {
     const int D = s->m->c.dec_dim;
     if (first < 0 || first + n > s->total_adapter) return set_err("adapter rows out of range");
@@ -2645,6 +2714,7 @@ extern "C" int vox_hip_stream_decode(vox_hip_stream_t* s, int max_steps, int sto
     const int D = c.dec_dim, V = c.vocab, hd = c.dec_head_dim;
     const int prompt_len = 1 + 32 + stream_delay(s);
     int produced = 0;
+    if (s->held) return set_err("stream_decode: %s", HELD_MSG);
     if (max_steps <= 0 || s->eos_seen) return 0;
     if (!s->started) {
         if (s->total_adapter < prompt_len) return 0;
@@ -2703,6 +2773,8 @@ extern "C" int vox_hip_stream_decode(vox_hip_stream_t* s, int max_steps, int sto
 // vox_stream_set_alt (voxtral.c:1329-1337)
 extern "C" int vox_hip_stream_set_alt(vox_hip_stream_t* s, int n_alt, float cutoff) {
     if (!s) return -1;
+    // (the call's slot names the alternatives ring by the mode the stream had at begin)
+    if (s->held) return set_err("stream_set_alt: %s", HELD_MSG);
     if (n_alt < 1) n_alt = 1;
     if (n_alt > VOX_HIP_MAX_ALT) n_alt = VOX_HIP_MAX_ALT;
     if (cutoff < 0) cutoff = 0;
@@ -3404,6 +3476,7 @@ extern "C" int vox_hip_encoder_full_step(vox_hip_stream_t* s, float* x, int new_
 extern "C" int vox_hip_decoder_prefill_step(vox_hip_stream_t* s, float* x, int seq_len,
                                             const float* rope_freqs, int logical_start) {
     const vox_hip_config_t& c = s->m->c;
+    if (s->held) return set_err("decoder_prefill_step: %s", HELD_MSG);
     if (stream_alloc_dec_rows(s, seq_len)) return -1;
     CK(hipMemcpyAsync(s->xd, x, (size_t)seq_len * c.dec_dim * 4, hipMemcpyHostToDevice, s->st));
     if (upload_rope_rows(s, rope_freqs, (size_t)seq_len * c.dec_head_dim)) return -1;
@@ -3429,6 +3502,7 @@ extern "C" void vox_hip_decoder_end(vox_hip_stream_t* s) {
 extern "C" int vox_hip_decoder_full_step(vox_hip_stream_t* s, const float* rope_freqs, int logical_pos,
                                          float* logits) {
     const vox_hip_config_t& c = s->m->c;
+    if (s->held) return set_err("decoder_full_step: %s", HELD_MSG);
     if (upload_rope_rows(s, rope_freqs, (size_t)c.dec_head_dim)) return -1;
     const int ctx = std::min(logical_pos + 1, c.dec_window);
     if (enqueue_step_layers(s, nullptr, logical_pos, s->rope_rows, (ctx + ATT_BLOCK_KEYS - 1) / ATT_BLOCK_KEYS))
@@ -3542,11 +3616,44 @@ struct vox_hip_batch {
         int* tokens_out;
         int* counts_out;
     } call;
+    // adapter buffers the begun call's members outgrew (stream_alloc_adapter): the slot table
+    // still names them, so they live until the call's last wait (batch_release)
+    float** parked;
+    int n_parked, cap_parked;
 };
 
 static_assert(VOX_MAX_SLOTS == VOX_HIP_BATCH_MAX_SLOTS, "the public bound of vox_hip_batch_create");
 static int* slot_toklog(BatchSlot* slots, int rows) { return reinterpret_cast<int*>(slots + rows); }
 static size_t slot_bytes(int rows) { return (sizeof(BatchSlot) + sizeof(int) * BATCH_TOKLOG) * (size_t)rows; }
+
+// The window of a begun call (batch_begin .. batch_finish).  Its slot table names each member's
+// state, tokens, adapter, Kc, Vc, alts and ada buffers and is uploaded once, so until the call
+// ends none of them may be freed or moved, and nothing else may advance a member's decoder:
+// batch_hold marks the members (the stream entry points that would do either refuse a held
+// stream; encoding stays allowed and parks an outgrown adapter buffer here), batch_release
+// ends the window after the call's last wait on the batch queue.
+static int batch_park(vox_hip_batch_t* b, float* p) {
+    if (b->n_parked == b->cap_parked) {
+        const int nc = b->cap_parked ? 2 * b->cap_parked : 16;
+        float** np = static_cast<float**>(realloc(b->parked, sizeof(float*) * nc));
+        if (!np) return set_err("batch: out of host memory for a parked adapter buffer");
+        b->parked = np;
+        b->cap_parked = nc;
+    }
+    b->parked[b->n_parked++] = p;
+    return 0;
+}
+static void batch_hold(vox_hip_batch_t* b) {
+    for (int i = 0; i < b->call.n; i++) b->call.streams[i]->held = b;
+    b->m->begun_calls++;
+}
+static void batch_release(vox_hip_batch_t* b) {
+    for (int i = 0; i < b->call.n; i++)
+        if (b->call.streams[i]->held == b) b->call.streams[i]->held = nullptr;
+    b->m->begun_calls--;
+    for (int i = 0; i < b->n_parked; i++) dfree(b->parked[i]);
+    b->n_parked = 0;
+}
 
 // pack one [N, K] matrix (bf16, or int8 when q8) into fragment order (k_frag_pack)
 static int frag_copy(uint8_t** dst, const uint8_t* src, int N, int K, int q8) {
@@ -3615,6 +3722,10 @@ static void batch_drop_graphs(vox_hip_batch_t* b) {
 extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
     if (!b) return;
     if (b->st) hipStreamSynchronize(b->st);
+    // a begun call that was never finished ends here: its members are released, its parked
+    // adapter buffers freed (the steps in flight are done, the later chunks never run)
+    if (b->call.active) batch_release(b);
+    free(b->parked);
     dfree(b->x); dfree(b->part); dfree(b->ssq); dfree(b->ticket); dfree(b->q); dfree(b->att);
     dfree(b->logits); dfree(b->pval); dfree(b->pidx); dfree(b->palt); dfree(b->apart);
     dfree(b->xp_d); dfree(b->xp_q); dfree(b->xp_h); dfree(b->pgws); dfree(b->gflags); dfree(b->hid);
@@ -4230,6 +4341,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     int mixed = 0;
     for (int i = 0; i < n; i++) {
         if (!streams[i] || streams[i]->m != m) return set_err("batch streams must share the batch's model");
+        if (streams[i]->held) return set_err("batch streams[%d]: %s", i, HELD_MSG);
         mixed |= streams[i]->delay >= 0;
         if (streams[i]->kvt != streams[0]->kvt)
             return set_err("batch streams must share the decoder KV element type (vox_hip_model_set_kv_dtype)");
@@ -4350,13 +4462,25 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     cl.k = k;
     cl.tokens_out = tokens_out;
     cl.counts_out = counts_out;
+    batch_hold(b);
     return 0;
 }
 
+static int batch_finish_steps(vox_hip_batch_t* b);
+
 static int batch_finish(vox_hip_batch_t* b) {
+    if (!b->call.active) return set_err("batch_finish: no begun call");
+    b->call.active = 0;
+    const int r = batch_finish_steps(b);
+    // every step of the call has been waited for (on an error the queue is waited for here):
+    // the members may move their buffers again, the adapter buffers they outgrew are freed
+    if (r < 0) (void)hipStreamSynchronize(b->st);
+    batch_release(b);
+    return r;
+}
+
+static int batch_finish_steps(vox_hip_batch_t* b) {
     auto& cl = b->call;
-    if (!cl.active) return set_err("batch_finish: no begun call");
-    cl.active = 0;
     const int n = cl.n, max_steps = cl.max_steps, K = cl.K;
     vox_hip_stream_t** streams = cl.streams;
     int* tokens_out = cl.tokens_out;
@@ -4436,6 +4560,7 @@ extern "C" int vox_hip_batch_begin_rows(vox_hip_batch_t* b, vox_hip_stream_t** s
         b->call.counts_out = counts_out;
         b->call.K = 0;
         b->call.k = 0;
+        batch_hold(b);
     }
     return 0;
 }

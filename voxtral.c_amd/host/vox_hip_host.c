@@ -995,6 +995,7 @@ struct vh_sched {
     int cap, n;
     vh_stream_t *s[VH_SCHED_MAX];
     int *tok;                 /* [cap][VH_SCHED_STEPS] */
+    int fail_next_encode;     /* vh_sched_debug_fail_next_encode: the next pass returns an error */
     vh_sched_stats_t stats;
 };
 
@@ -1054,6 +1055,16 @@ int vh_sched_detach(vh_sched_t *q, vh_stream_t *s) {
 }
 
 void vh_sched_set_step_cap(vh_sched_t *q, int cap) { q->step_cap = cap > 0 ? cap : 0; }
+
+void vh_sched_debug_fail_next_encode(vh_sched_t *q) {
+    if (q) q->fail_next_encode = 1;
+}
+
+int vh_stream_adapter_stats(const vh_stream_t *s, long long out3[3]) {
+    if (!s || !out3) return fail("vh_stream_adapter_stats: null argument");
+    if (vox_hip_stream_adapter_stats(s->st, out3)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
 
 static int sched_batch(vh_sched_t *q) {
     if (!q->batch) q->batch = vox_hip_batch_create(q->ctx->model, q->cap);
@@ -1142,7 +1153,10 @@ static int sched_encode(vh_sched_t *q, int overlap);
  * bounded: stream i reads only its first rows[i] adapter rows (an encoder pass may still be
  * running on its queue).  enc_between: the run's encoder pass is enqueued between the first
  * round's begin and finish (vox_hip_batch_begin_rows / vox_hip_batch_finish), so the steps are
- * on the device before the pass; *enc_done tells whether that happened */
+ * on the device before the pass; *enc_done tells whether that happened.  A pass that fails
+ * there does not leave the begun call open: the call is finished and its ids are queued as on
+ * the success path -- the device state has advanced by them -- and only then is the error
+ * returned, so the next run works and no id is lost or repeated. */
 static int sched_steps(vh_sched_t *q, int bounded, const int *rows, const int *ran, int *eos, int *total,
                        int enc_between, int *enc_done) {
     for (int iter = 0;; iter++) {
@@ -1170,12 +1184,16 @@ static int sched_steps(vh_sched_t *q, int bounded, const int *rows, const int *r
         }
         double t0 = now_ms();
         const int cap = q->step_cap > 0 && q->step_cap < VH_SCHED_STEPS ? q->step_cap : VH_SCHED_STEPS;
-        int r;
+        int r, enc_failed = 0;
+        char enc_err[sizeof g_err];
         if (bounded && enc_between && iter == 0) {
             if (vox_hip_batch_begin_rows(q->batch, hs, nb, brows, cap, 1, q->tok, counts) < 0)
                 return fail("batched decoder: %s", vox_hip_last_error());
             const double tb = now_ms();
-            if (sched_encode(q, 1)) return -1;
+            if (sched_encode(q, 1)) {
+                enc_failed = 1;
+                snprintf(enc_err, sizeof enc_err, "%s", g_err);
+            }
             *enc_done = 1;
             t0 += now_ms() - tb;  /* the pass's enqueue is the encoder's time */
             r = vox_hip_batch_finish(q->batch);
@@ -1206,6 +1224,7 @@ static int sched_steps(vh_sched_t *q, int bounded, const int *rows, const int *r
             more |= n == cap;
         }
         q->stats.tokens += r;
+        if (enc_failed) return fail("%s", enc_err);
         /* with a step cap, a scheduled stream's rows beyond it wait for the next run */
         if (r == 0 || !more) break;
     }
@@ -1288,8 +1307,17 @@ int vh_sched_run(vh_sched_t *q) {
 }
 
 /* the run's encoder pass over every attached stream's deferred chunk (step 0 of vh_sched_run);
- * overlap: left running on the streams' queues (vh_sched_run syncs them before it returns) */
+ * overlap: left running on the streams' queues.  Without a step cap vh_sched_run waits for it
+ * before it returns and drains its rows; with one the run may return with the pass in flight
+ * and the next run waits for every stream's queue before it counts rows.
+ * In the steps-first order this runs between vox_hip_batch_begin_rows and _finish: an adapter
+ * buffer that grows here is kept alive for the begun call by the library. */
 static int sched_encode(vh_sched_t *q, int overlap) {
+    if (q->fail_next_encode) {
+        /* the test hook: an error before anything is enqueued; the chunks stay deferred */
+        q->fail_next_encode = 0;
+        return fail("encoder pass failed (vh_sched_debug_fail_next_encode)");
+    }
     {
         vox_hip_stream_t *hs[VH_SCHED_MAX];
         const float *mp[VH_SCHED_MAX];
@@ -1322,9 +1350,10 @@ static int sched_encode(vh_sched_t *q, int overlap) {
                 q->stats.enc_ms += dt;
                 for (int k = 0; k < nb; k++) q->s[idx[k]]->enc_ms += dt / nb;
             } else {
-                /* still running: it completes beside the steps (step 3); enc_ms counts the
-                 * enqueue.  (Leaving it running past the run's end, for the next run to wait
-                 * for, measured no faster: profiles/r4_serve_overlap_ab.txt.) */
+                /* still running beside the steps; enc_ms counts the enqueue.  Without a step
+                 * cap the run waits for it (step 3); with one it may outlive the run and the
+                 * next run waits for it before counting rows (without the
+                 * cap that measured no faster: profiles/r4_serve_overlap_ab.txt). */
                 q->stats.enc_ms += now_ms() - t0;
             }
             for (int k = 0; k < nb; k++) {

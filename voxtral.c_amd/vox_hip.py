@@ -134,6 +134,7 @@ EXPORTS = [
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
     "vox_hip_stream_set_delay", "vox_hip_stream_delay", "vox_hip_stream_ada_scale",
     "vox_hip_stream_adapter_tokens", "vox_hip_stream_read_adapter", "vox_hip_stream_decode",
+    "vox_hip_set_adapter_rows0", "vox_hip_stream_adapter_stats",
     "vox_hip_batch_create", "vox_hip_batch_free", "vox_hip_batch_decode", "vox_hip_batch_decode_rows",
     "vox_hip_batch_begin_rows", "vox_hip_batch_finish",
     "vox_hip_batch_read_logits",
@@ -196,6 +197,8 @@ def lib():
         "vox_hip_stream_ada_scale": (I, [P, fp]),
         "vox_hip_stream_encode_mel": (I, [P, P, I, I]),
         "vox_hip_stream_adapter_tokens": (I, [P]),
+        "vox_hip_set_adapter_rows0": (I, [I]),
+        "vox_hip_stream_adapter_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_stream_read_adapter": (I, [P, I, I, fp]),
         "vox_hip_stream_decode": (I, [P, I, I, ip, fp]),
         "vox_hip_stream_state": (I, [P, ip]),
@@ -360,6 +363,13 @@ def gemmf_q8_rows(x, W_i8, scales, fmt: int) -> np.ndarray:
     if lib().vox_hip_gemmf_q8_rows(M, N, K, fptr(xv), W.ctypes.data, fptr(sc), fptr(y), int(fmt)) != 0:
         _err("gemmf_q8_rows")
     return y
+
+
+def set_adapter_rows0(rows: int):
+    """vox_hip_set_adapter_rows0: the first adapter-buffer capacity (rows) of streams created from
+    now on, a power of two in 16..1024; 0 restores the default of 1024.  Needs no device."""
+    if lib().vox_hip_set_adapter_rows0(int(rows)) != 0:
+        _err("set_adapter_rows0")
 
 
 def init(device: int | None = None):
@@ -587,6 +597,14 @@ class Stream:
     @property
     def adapter_tokens(self) -> int:
         return lib().vox_hip_stream_adapter_tokens(self.h)
+
+    def adapter_stats(self) -> dict:
+        """vox_hip_stream_adapter_stats: the adapter buffer's capacity in rows, its growths, and
+        those of them that happened inside a begun, unfinished batched call"""
+        out = (ctypes.c_longlong * 3)()
+        if lib().vox_hip_stream_adapter_stats(self.h, out) != 0:
+            _err("adapter_stats")
+        return dict(zip(("cap", "grows", "grows_held"), (int(v) for v in out)))
 
     def read_adapter(self, first: int = 0, n: int | None = None) -> np.ndarray:
         if n is None:
@@ -1060,6 +1078,8 @@ def host_lib():
         "vh_sched_set_step_cap": (None, [P, I]), "vh_stream_pending": (I, [P]),
         "vh_stream_set_delay": (I, [P, I]), "vh_stream_delay_ms": (I, [P]),
         "vh_set_enc_kv_fp16": (I, [P, I]), "vh_stream_enc_kv_fp16": (I, [P]),
+        "vh_sched_debug_fail_next_encode": (None, [P]),
+        "vh_stream_adapter_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(H, name)
@@ -1143,6 +1163,13 @@ class HostStream:
         """adapter rows not decoded yet (vh_stream_pending)"""
         return host_lib().vh_stream_pending(self.h)
 
+    def adapter_stats(self) -> dict:
+        """vh_stream_adapter_stats: as Stream.adapter_stats, for the stream behind this one"""
+        out = (ctypes.c_longlong * 3)()
+        if host_lib().vh_stream_adapter_stats(self.h, out) != 0:
+            _herr("vh_stream_adapter_stats")
+        return dict(zip(("cap", "grows", "grows_held"), (int(v) for v in out)))
+
     def get_alt(self) -> np.ndarray:
         """queued records [n, 4]: the chosen id, then the accepted alternatives, -1 padded"""
         out, buf = [], np.empty((1024, 4), np.int32)
@@ -1185,6 +1212,11 @@ class Scheduler:
     def set_step_cap(self, cap: int):
         """vh_sched_set_step_cap: at most `cap` steps per stream and run (0: drain every run)"""
         host_lib().vh_sched_set_step_cap(self.h, int(cap))
+
+    def fail_next_encode(self):
+        """vh_sched_debug_fail_next_encode (test hook): the next run's encoder pass returns an
+        error before it enqueues anything, so that run() raises after finishing its steps"""
+        host_lib().vh_sched_debug_fail_next_encode(self.h)
 
     def stats(self) -> dict:
         st = SchedStats()
