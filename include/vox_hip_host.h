@@ -113,6 +113,14 @@ int vh_stream_kv_dtype(const vh_stream_t *s);
  * vh_sched_t serves streams of both types. */
 int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on);
 int vh_stream_enc_kv_fp16(const vh_stream_t *s);
+/* Decoder K/V rings of streams initialised after this call start at slots0 slots and double as
+ * the stream's position needs them, up to the full window + 64 (vox_hip_model_set_kv_grow,
+ * voxtral_hip.h: lossless; a one-minute session holds 1024 slots of the 8256).  0: full rings
+ * from the start (default).  0, or -1 (vh_last_error).  vh_stream_reset returns a stream's rings
+ * to slots0, a continuous-mode restart keeps their capacity; one vh_sched_t serves streams of any
+ * capacities.  vh_stream_kv_slots: the slots of s's rings now. */
+int vh_set_kv_grow(vh_ctx_t *ctx, int slots0);
+int vh_stream_kv_slots(const vh_stream_t *s);
 
 /* The model behind a context (for the model-level calls of voxtral_hip.h, such as
  * vox_hip_model_wmx4_stats); the context keeps owning it. */

@@ -131,6 +131,25 @@ int vox_hip_model_set_kv_dtype(vox_hip_model_t *m, int dtype);
  * There is NO FP8 encoder ring.  head_dim 64 only (Voxtral's encoder); returns 0, or -1
  * (vox_hip_last_error) for another head_dim. */
 int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t *m, int on);
+/* Decoder K/V rings that grow with the stream (no reference counterpart; lossless).  A stream
+ * created after this call with slots0 > 0 starts with decoder rings of slots0 slots (clamped to
+ * [64, dec_window + 64]; 64 holds the longest prompt) in its own element type instead of the
+ * full dec_window + 64.  Before any call appends decoder positions the rings are made to hold
+ * min(dec_window + 64, the last position the call can reach + 1): the new capacity is the
+ * smallest slots0 * 2^k that does, capped at the full size, and each layer's first rows are
+ * copied into the longer buffer (a ring below the full size has not wrapped: slot = position).
+ * Stored values, arithmetic and tokens are those of a full ring; a ring that reached the full
+ * size is the full ring.  A growth that cannot be allocated fails its call (< 0,
+ * vox_hip_last_error names the growth) before anything is enqueued, the stream intact at its
+ * old capacity.  vox_hip_stream_reset returns the rings to slots0, vox_hip_stream_reset_decoder
+ * keeps their capacity; vox_hip_memory_used follows both.  One decoder position is 80 ms of
+ * audio: 2 x dec_layers x slots x kv_heads x head_dim x element bytes per stream, e.g. 0.22 GB
+ * as f32 after one minute (1024 slots) against 1.76 GB.  Batched calls take streams of any
+ * capacities together (vox_hip_batch_kv_grow_stats).  A single stream below 256 slots runs
+ * the general decode attention where a full ring runs the short-context kernel (same values,
+ * another summation order).  slots0 = 0 (the default): full rings from the start, nothing
+ * changes.  VOX_HIP_KV_GROW=<slots> gives the initial value.  Returns 0, or -1 for slots0 < 0. */
+int vox_hip_model_set_kv_grow(vox_hip_model_t *m, int slots0);
 /* wpack13 (no reference counterpart): at creation every bf16 matrix of the single-stream
  * decode step (Q|K|V, wo, W1|W3, W2 per decoder layer, and the LM head) whose nonzero
  * exponents span at most 30 binades also gets a 13-bit-per-weight copy that the M = 1 GEMV
@@ -286,6 +305,18 @@ int vox_hip_stream_enc_kv_fp16(const vox_hip_stream_t *s);
 int vox_hip_stream_enc_paths(const vox_hip_stream_t *s, long long out5[5]);
 /* bytes of the stream's encoder K and V rings together (all layers) */
 long long vox_hip_stream_enc_kv_bytes(const vox_hip_stream_t *s);
+/* slots of the stream's decoder K/V rings now (dec_window + 64 unless vox_hip_model_set_kv_grow) */
+int vox_hip_stream_kv_slots(const vox_hip_stream_t *s);
+/* bytes of the stream's decoder K and V rings together (all layers) */
+long long vox_hip_stream_kv_bytes(const vox_hip_stream_t *s);
+/* out3: [0] growths of the stream's decoder rings since creation, [1] bytes their copies moved,
+ * [2] slots now */
+int vox_hip_stream_kv_grow_stats(const vox_hip_stream_t *s, long long out3[3]);
+/* Grow ahead: the stream's decoder rings hold `positions` positions (the full ring at most) from
+ * now on, so the calls up to that position grow nothing; a server's admission test (-1 when the
+ * rings cannot be allocated, the stream unchanged).  A stream with full rings: 0, nothing done.
+ * Refused for a stream held by a begun batched call. */
+int vox_hip_stream_reserve_kv(vox_hip_stream_t *s, int positions);
 /* Tests / diagnostics: the raw ring elements of decoder layer `layer` at logical positions
  * [first_logical_pos, first_logical_pos + n), [n][dec_kv_heads * dec_head_dim] in the stream's
  * element type (4, 2 or 1 bytes each) to k_out / v_out (either may be null).  Waits for the
@@ -480,6 +511,18 @@ int vox_hip_batch_read_logits(vox_hip_batch_t *b, vox_hip_stream_t *s, float *ou
 /* Counters since creation: [0] calls, [1] step replays, [2] live rows over those steps,
  * [3] step-graph captures, [4] batched prefill passes, [5] prefilled streams. */
 int vox_hip_batch_stats(const vox_hip_batch_t *b, long long *out6);
+/* Growing decoder rings in batched calls (vox_hip_model_set_kv_grow).  A call grows every listed
+ * stream's rings for the whole call -- its position, the prompt if it joins, min(max_steps, the
+ * rows it may read) steps -- before its prefills and slot table, copies on the batch queue; if
+ * one growth cannot be allocated the call returns -1 with nothing enqueued.  Nothing moves
+ * between begin and finish (vox_hip_stream_reserve_kv is refused there).  A call in which every
+ * listed stream has full rings is plain: today's kernels, arguments and step graphs.  A call with
+ * a shorter ring is ragged: its attention instances take each slot's ring capacity (slot modulo
+ * and layer stride) from a per-slot table, on step graphs of their own; it runs the MFMA step
+ * (<= 32 streams) or the wide step, never the R-row GEMV steps.  Same bits as the same streams
+ * on full rings.  out3: [0] ragged calls, [1] ragged step replays, [2] ragged step-graph captures
+ * (all also counted in vox_hip_batch_stats). */
+int vox_hip_batch_kv_grow_stats(const vox_hip_batch_t *b, long long out3[3]);
 /* The prefill of joining streams whose decoder KV rings are IEEE half or FP8: on = 1 (the
  * default) stacks their prompts into the shared passes on the batch queue exactly as f32
  * streams' are -- the layers' weights read once per pass of up to 26 prompts, no wait on the

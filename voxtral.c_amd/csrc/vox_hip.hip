@@ -215,6 +215,7 @@ struct vox_hip_model {
     int gemmf_q8;                  // vox_hip_gemmf_q8() at creation: k_gemmf streams the int8 fragment copies of Q8 tensors
     long long n_gemmf_q8;          // k_gemmf launches on int8 fragments (vox_hip_model_gemmf_q8_stats)
     int begun_calls;               // batched calls of this model between begin_rows and finish (their slots read ada_scale)
+    int kv_grow;                   // first decoder ring capacity (slots) of streams created from now on; 0: the full ring
 };
 
 static int upload(void* dst, const void* src, size_t bytes) {
@@ -403,6 +404,10 @@ extern "C" int vox_hip_set_adapter_rows0(int rows) {
     return 0;
 }
 
+// smallest first capacity of a growing decoder ring (vox_hip_model_set_kv_grow): the ring's
+// slack, which holds the longest prompt (32 + 30 rows); the full ring is the window plus it
+static const int KV_GROW_MIN = 64;
+
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -589,6 +594,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         // vox_hip_model_set_enc_kv_fp16 overrides
         const char* ee = getenv("VOX_HIP_ENC_KV_FP16");
         m->ekvt = (ee && atoi(ee) != 0 && cfg->enc_head_dim == 64) ? KV_F16 : KV_F32;
+        // decoder rings that start at VOX_HIP_KV_GROW slots and grow with the stream's position
+        // (unset or 0: the full ring from the start); vox_hip_model_set_kv_grow overrides
+        const char* eg = getenv("VOX_HIP_KV_GROW");
+        m->kv_grow = 0;
+        if (eg && atoi(eg) > 0) m->kv_grow = std::min(std::max(atoi(eg), KV_GROW_MIN), cfg->dec_window + KV_GROW_MIN);
     }
     m->conv0_w = m->conv1_w = nullptr;
     m->ad0 = m->ad1 = m->tok_emb = nullptr;
@@ -857,6 +867,16 @@ extern "C" int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t* m, int on) {
 
 extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s);
 
+// Streams created afterwards start with decoder rings of slots0 slots (clamped to [64, window +
+// 64]: 64 holds the longest prompt, 32 + 30 rows) that double as the stream's position needs
+// them, up to the full window + 64 (stream_grow_dec).  0: the full ring from the start (default).
+extern "C" int vox_hip_model_set_kv_grow(vox_hip_model_t* m, int slots0) {
+    if (!m) return set_err("model_set_kv_grow: null model");
+    if (slots0 < 0) return set_err("model_set_kv_grow: %d slots (0: off, or the first ring capacity)", slots0);
+    m->kv_grow = slots0 ? std::min(std::max(slots0, KV_GROW_MIN), m->c.dec_window + KV_GROW_MIN) : 0;
+    return 0;
+}
+
 extern "C" int vox_hip_model_ada_scale(vox_hip_model_t* m, float* out) {
     memcpy(out, m->ada_host.data(), m->ada_host.size() * 4);
     return 0;
@@ -867,6 +887,7 @@ extern "C" int vox_hip_model_ada_scale(vox_hip_model_t* m, float* out) {
 // ---------------------------------------------------------------------------
 static const int ENC_SUB = 1024;      // encoder rows per pass through the 32 layers
 static const int DEC_SLACK = 64;      // decoder ring capacity = window + slack
+static_assert(DEC_SLACK == KV_GROW_MIN, "a growing ring starts no smaller than the slack");
 static const int STEP_BATCH = 16;     // graph replays between EOS checks
 static const size_t GEMM_WS_ELEMS = (size_t)8 << 20;  // split-K workspace (32 MB)
 static const int TOKENS_CAP = 1 << 16;  // per-stream token / alternatives ring entries
@@ -880,6 +901,12 @@ struct vox_hip_stream {
     float *ek, *ev, *dk, *dv;   // dk / dv: elements of type kvt (f32, IEEE half or FP8 E4M3 bytes)
     int ecap, dcap;             // ek / ev: elements of type ekvt (f32 or IEEE half)
     int kvt, ekvt;
+    // growing decoder rings (vox_hip_model_set_kv_grow): the first capacity (0: the full ring from
+    // the start, dcap never moves), an upper bound of the rows the ring holds (the last position + 1
+    // of the calls that appended so far: each of them passes through stream_grow_dec first; a
+    // growth copies that many rows), growths and bytes copied by them
+    int dslots0, drows;
+    long long kv_grows, kv_copied;
     // encoder passes of this stream by path (vox_hip_stream_enc_paths): one-row GEMV, fused
     // skinny chain (k_sklx), slab skinny chain, M > 1 rows pass, and layer-0 attention launches
     // that took a split key grid
@@ -1039,6 +1066,9 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     const int EQ = c.enc_heads * c.enc_head_dim;
     s->ecap = c.enc_window + ENC_SUB + 64;
     s->dcap = c.dec_window + DEC_SLACK;
+    // (a first capacity of the full size is the plain ring)
+    s->dslots0 = m->kv_grow < s->dcap ? m->kv_grow : 0;
+    if (s->dslots0) s->dcap = s->dslots0;
     s->kvt = m->kvt;
     s->ekvt = m->ekvt;
     // (a half encoder ring has head_dim 64, so EKV is a multiple of 2)
@@ -1160,6 +1190,182 @@ static float* dec_ring(const vox_hip_stream_t* s, float* base, int l) {
     return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * kv_esize(s->kvt));
 }
 
+// ---------------------------------------------------------------------------
+// Growing decoder rings.  A ring of fewer slots than window + slack has not
+// wrapped: slot = position, so a longer ring holds the same rows at the same slots and growth
+// is a copy of each layer's first rows from pitch cap0 * DKV * esize to pitch cap1 * DKV * esize.
+// ---------------------------------------------------------------------------
+static int dec_ring_full(const vox_hip_stream_t* s) { return s->m->c.dec_window + DEC_SLACK; }
+// floats (dalloc's unit) of one of the stream's two decoder rings at `cap` slots
+static size_t dec_ring_floats(const vox_hip_stream_t* s, int cap) {
+    const vox_hip_config_t& c = s->m->c;
+    return (size_t)c.dec_layers * cap * c.dec_kv_heads * c.dec_head_dim / (4 / kv_esize(s->kvt));
+}
+// a ring buffer leaves: vox_hip_memory_used follows the rings down as well as up
+static void dec_ring_free(float*& p, size_t floats) {
+    if (!p) return;
+    dfree(p);
+    g_mem_used -= std::max(floats, (size_t)1) * sizeof(float);
+}
+// the smallest slots0 * 2^k that holds `need` positions, capped at the full ring
+static int kv_grow_cap(int slots0, int full, int need) {
+    long long c = slots0;
+    while (c < need && c < full) c *= 2;
+    return (int)std::min<long long>(c, full);
+}
+
+// One stream's pending growth: the new rings are allocated first (dec_grow_alloc; nothing is
+// enqueued and the stream is untouched, so a failure leaves it whole at its old capacity), then
+// every growth of a call is committed together (dec_grow_commit).
+struct DecGrow {
+    vox_hip_stream_t* s;
+    int need, cap;      // positions the rings are to hold; the new capacity (0: no growth)
+    bool appends;       // the caller goes on to append up to `need` positions (a reservation does not)
+    float *nk, *nv;
+};
+
+static int dec_grow_alloc(vox_hip_stream_t* s, int need, bool appends, DecGrow* g) {
+    const int full = dec_ring_full(s);
+    *g = DecGrow{s, std::min(std::max(need, 0), full), 0, appends, nullptr, nullptr};
+    if (!s->dslots0 || g->need <= s->dcap) return 0;
+    const int nc = kv_grow_cap(s->dslots0, full, g->need);
+    const size_t nf = dec_ring_floats(s, nc);
+    hipError_t e = dalloc(&g->nk, nf);
+    if (e == hipSuccess) {
+        e = dalloc(&g->nv, nf);
+        if (e != hipSuccess) dec_ring_free(g->nk, nf);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the failed hipMalloc, so no later launch check reports it
+        g->nk = g->nv = nullptr;
+        return set_err("decoder KV ring growth %d -> %d slots (%zu bytes): %s", s->dcap, nc, 2 * nf * sizeof(float),
+                       hipGetErrorString(e));
+    }
+    g->cap = nc;
+    return 0;
+}
+
+static void dec_grow_drop(DecGrow* g, int n) {
+    for (int i = 0; i < n; i++)
+        if (g[i].cap) {
+            const size_t nf = dec_ring_floats(g[i].s, g[i].cap);
+            dec_ring_free(g[i].nk, nf);
+            dec_ring_free(g[i].nv, nf);
+            g[i].cap = 0;
+        }
+}
+
+// The copies of every pending growth on queue q (the queue that reads the rings next), one 2D
+// copy per ring: the first s->drows rows of every layer (what the ring holds; the positions a
+// growth reserves enter s->drows only where the caller appends them).  Every earlier writer of a ring is done by
+// now: each entry point that appends waits for its queue before it returns, and a begun
+// batched call refuses its members to all of them.  The old rings are freed after the wait for
+// q, when their last reader, the copy, is done; the stream's step graphs hold their addresses
+// and the capacity, so they are captured again.
+static int dec_grow_commit(DecGrow* g, int n, hipStream_t q) {
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        vox_hip_stream_t* s = g[i].s;
+        if (!g[i].cap) continue;
+        any = true;
+        const vox_hip_config_t& c = s->m->c;
+        const size_t row = (size_t)c.dec_kv_heads * c.dec_head_dim * kv_esize(s->kvt);
+        const int rows = std::min(s->drows, s->dcap);
+        if (rows > 0) {
+            float* src[2] = {s->dk, s->dv};
+            float* dst[2] = {g[i].nk, g[i].nv};
+            for (int w = 0; w < 2; w++)
+                if (hipError_t e = hipMemcpy2DAsync(dst[w], (size_t)g[i].cap * row, src[w], (size_t)s->dcap * row,
+                                                    (size_t)rows * row, c.dec_layers, hipMemcpyDeviceToDevice, q);
+                    e != hipSuccess) {
+                    (void)hipStreamSynchronize(q);
+                    dec_grow_drop(g, n);
+                    return set_err("decoder KV ring growth copy: %s", hipGetErrorString(e));
+                }
+        }
+    }
+    if (any)
+        if (hipError_t e = hipStreamSynchronize(q); e != hipSuccess) {
+            dec_grow_drop(g, n);
+            return set_err("decoder KV ring growth copy: %s", hipGetErrorString(e));
+        }
+    for (int i = 0; i < n; i++) {
+        vox_hip_stream_t* s = g[i].s;
+        if (g[i].cap) {
+            const vox_hip_config_t& c = s->m->c;
+            const size_t of = dec_ring_floats(s, s->dcap);
+            s->kv_grows++;
+            s->kv_copied += 2LL * c.dec_layers * std::min(s->drows, s->dcap) * c.dec_kv_heads * c.dec_head_dim *
+                            (long long)kv_esize(s->kvt);
+            dec_ring_free(s->dk, of);
+            dec_ring_free(s->dv, of);
+            s->dk = g[i].nk;
+            s->dv = g[i].nv;
+            s->dcap = g[i].cap;
+            s->graph_ready = 0;
+            g[i].cap = 0;
+        }
+        if (g[i].appends) s->drows = std::max(s->drows, g[i].need);
+    }
+    return 0;
+}
+
+// the stream's rings hold min(full, need) positions before a call on its own queue appends them
+// (appends = false: a reservation, nothing is appended)
+static int stream_grow_dec(vox_hip_stream_t* s, int need, bool appends = true) {
+    DecGrow g;
+    if (dec_grow_alloc(s, need, appends, &g)) return -1;
+    return dec_grow_commit(&g, 1, s->st);
+}
+
+// a stream that grew goes back to its first capacity (new audio: vox_hip_stream_reset).  The
+// small rings are allocated before anything is freed, and vox_hip_stream_reset calls this before
+// it touches any other state: a failure leaves the whole stream as it was.
+static int stream_shrink_dec(vox_hip_stream_t* s) {
+    if (!s->dslots0 || s->dcap == s->dslots0) return 0;
+    const size_t nf = dec_ring_floats(s, s->dslots0), of = dec_ring_floats(s, s->dcap);
+    // the small rings first: a failure leaves the stream whole at the capacity it had
+    float *nk = nullptr, *nv = nullptr;
+    if (dalloc(&nk, nf) != hipSuccess || dalloc(&nv, nf) != hipSuccess) {
+        (void)hipGetLastError();
+        dec_ring_free(nk, nf);
+        dec_ring_free(nv, nf);
+        return set_err("stream_reset: decoder KV rings of %d slots could not be allocated", s->dslots0);
+    }
+    CK(hipStreamSynchronize(s->st));
+    dec_ring_free(s->dk, of);
+    dec_ring_free(s->dv, of);
+    s->dk = nk;
+    s->dv = nv;
+    s->dcap = s->dslots0;
+    s->drows = 0;
+    s->graph_ready = 0;
+    return 0;
+}
+
+extern "C" int vox_hip_stream_kv_slots(const vox_hip_stream_t* s) { return s ? s->dcap : -1; }
+// bytes of the stream's decoder K and V rings together
+extern "C" long long vox_hip_stream_kv_bytes(const vox_hip_stream_t* s) {
+    if (!s) return -1;
+    const vox_hip_config_t& c = s->m->c;
+    return 2LL * c.dec_layers * s->dcap * c.dec_kv_heads * c.dec_head_dim * (long long)kv_esize(s->kvt);
+}
+extern "C" int vox_hip_stream_kv_grow_stats(const vox_hip_stream_t* s, long long out3[3]) {
+    if (!s || !out3) return set_err("stream_kv_grow_stats: null argument");
+    out3[0] = s->kv_grows;
+    out3[1] = s->kv_copied;
+    out3[2] = s->dcap;
+    return 0;
+}
+// the rings hold `positions` positions (the full ring at most) from now on: a server grows
+// ahead of the calls that would, and takes a failure here as its admission test
+extern "C" int vox_hip_stream_reserve_kv(vox_hip_stream_t* s, int positions) {
+    if (!s) return set_err("stream_reserve_kv: null stream");
+    if (s->held) return set_err("stream_reserve_kv: %s", HELD_MSG);
+    if (positions < 0) return set_err("stream_reserve_kv: %d positions", positions);
+    return stream_grow_dec(s, positions, false);
+}
+
 extern "C" void vox_hip_stream_free(vox_hip_stream_t* s) {
     if (!s) return;
     if (s->held) {
@@ -1193,6 +1399,7 @@ extern "C" int vox_hip_stream_reset_decoder(vox_hip_stream_t* s) {
     s->started = 0;
     s->eos_seen = 0;
     s->n_generated = 0;
+    s->drows = 0;  // (a grown ring keeps its capacity; it holds no row worth copying)
     int st[4] = {0, 0, TOKEN_BOS, 0};
     memcpy(s->h_state, st, sizeof st);
     CK(hipMemcpyAsync(s->state, st, sizeof st, hipMemcpyHostToDevice, s->st));
@@ -1204,6 +1411,9 @@ extern "C" int vox_hip_stream_reset(vox_hip_stream_t* s) {
     // stream_reset_full_state (voxtral.c:786-814)
     if (s->held) return set_err("stream_reset: %s", HELD_MSG);
     const vox_hip_config_t& c = s->m->c;
+    // new audio: a ring that grew returns to its first capacity (first: if the small rings
+    // cannot be allocated the stream is left exactly as it was)
+    if (stream_shrink_dec(s)) return -1;
     s->enc_pos = 0;
     s->res_count = 0;
     s->enc_res_count = 0;
@@ -2716,10 +2926,15 @@ extern "C" int vox_hip_stream_decode(vox_hip_stream_t* s, int max_steps, int sto
     int produced = 0;
     if (s->held) return set_err("stream_decode: %s", HELD_MSG);
     if (max_steps <= 0 || s->eos_seen) return 0;
-    if (!s->started) {
-        if (s->total_adapter < prompt_len) return 0;
-        if (stream_prefill(s)) return -1;
+    if (!s->started && s->total_adapter < prompt_len) return 0;
+    if (s->dslots0) {
+        // a growing ring holds the call's last position before anything is enqueued: the prompt
+        // if the decoder has not started, then min(max_steps, adapter rows left) steps
+        const int pos = s->started ? s->h_state[0] : prompt_len - 1;
+        const int left = s->total_adapter - (s->started ? s->h_state[1] : prompt_len - 1);
+        if (stream_grow_dec(s, pos + std::max(0, std::min(max_steps, left)))) return -1;
     }
+    if (!s->started && stream_prefill(s)) return -1;
     const int step_base = s->n_generated;
     int avail = s->total_adapter - (s->h_state[1] > 0 ? s->h_state[1] : prompt_len - 1);
     {
@@ -3477,6 +3692,7 @@ extern "C" int vox_hip_decoder_prefill_step(vox_hip_stream_t* s, float* x, int s
                                             const float* rope_freqs, int logical_start) {
     const vox_hip_config_t& c = s->m->c;
     if (s->held) return set_err("decoder_prefill_step: %s", HELD_MSG);
+    if (s->dslots0 && stream_grow_dec(s, logical_start + seq_len)) return -1;
     if (stream_alloc_dec_rows(s, seq_len)) return -1;
     CK(hipMemcpyAsync(s->xd, x, (size_t)seq_len * c.dec_dim * 4, hipMemcpyHostToDevice, s->st));
     if (upload_rope_rows(s, rope_freqs, (size_t)seq_len * c.dec_head_dim)) return -1;
@@ -3503,6 +3719,7 @@ extern "C" int vox_hip_decoder_full_step(vox_hip_stream_t* s, const float* rope_
                                          float* logits) {
     const vox_hip_config_t& c = s->m->c;
     if (s->held) return set_err("decoder_full_step: %s", HELD_MSG);
+    if (s->dslots0 && stream_grow_dec(s, logical_pos + 1)) return -1;
     if (upload_rope_rows(s, rope_freqs, (size_t)c.dec_head_dim)) return -1;
     const int ctx = std::min(logical_pos + 1, c.dec_window);
     if (enqueue_step_layers(s, nullptr, logical_pos, s->rope_rows, (ctx + ATT_BLOCK_KEYS - 1) / ATT_BLOCK_KEYS))
@@ -3564,7 +3781,9 @@ struct vox_hip_batch {
     // (wmx4: [3 wmx4 + element type], the two weight sources keep graphs of their own)
     // [mixed]: the steps of a call in which a stream carries a delay of its own launch the per-slot
     // norm instances, so they keep graphs of their own beside the plain calls'
-    hipGraphExec_t gexec[2][6][6][STEP_GRAPHS];
+    // [mixed + 2 ragged]: likewise the steps of a call in which a stream's decoder rings are shorter
+    // than window + slack (vox_hip_model_set_kv_grow) launch the ragged attention instances
+    hipGraphExec_t gexec[4][6][6][STEP_GRAPHS];
     int grope_gen;
     // the MFMA step streams the wmx4 fragment planes of the tensors that have one
     // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
@@ -3597,7 +3816,12 @@ struct vox_hip_batch {
     uint16_t *wpa, *wpc;
     int* wflags;
     int* wepoch;
-    hipGraphExec_t gwexec[2][3][2][STEP_GRAPHS];  // [mixed], as gexec
+    hipGraphExec_t gwexec[4][3][2][STEP_GRAPHS];  // [mixed + 2 ragged], as gexec
+    // the ragged steps' ring capacity per slot, device and pinned host (made by the first ragged
+    // call; a batch that sees full rings only never allocates or reads them), their counters
+    int* dcaps;
+    int* hcaps;
+    long long n_ragged_calls, n_ragged_replays, n_ragged_captures;
     int wide_q8;  // k_gemmf launches on int8 fragments in one wide step (set by batch_step_wide)
     long long n_calls, n_replays, n_rows, n_captures, n_prefill_passes, n_prefilled;
     // split-K workspace of the stacked prefills (not the lead stream's: with an encoder pass
@@ -3612,6 +3836,7 @@ struct vox_hip_batch {
         int active, n, max_steps, stop_at_eos, K, nb, gb, gi, splits, kvt, done, k;
         int gemv;  // the call's steps take the GEMV path
         int mixed; // a stream of the call carries a delay of its own: the per-slot norm instances
+        int ragged; // a stream of the call has rings shorter than the full size: the ragged attention instances
         vox_hip_stream_t* streams[VOX_MAX_SLOTS];
         int* tokens_out;
         int* counts_out;
@@ -3732,6 +3957,8 @@ extern "C" void vox_hip_batch_free(vox_hip_batch_t* b) {
     dfree(b->wqkv); dfree(b->wxn); dfree(b->whid); dfree(b->wpa); dfree(b->wpc); dfree(b->wflags); dfree(b->wepoch);
     if (b->slots) hipFree(b->slots);
     if (b->hslots) hipHostFree(b->hslots);
+    dfree(b->dcaps);
+    if (b->hcaps) hipHostFree(b->hcaps);
     batch_drop_graphs(b);
     if (b->st) hipStreamDestroy(b->st);
     delete b;
@@ -3844,7 +4071,9 @@ static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const ui
 
 // one batched step over slots 0..nb-1 of the slot table (their input rows already in b->x)
 // mixed: the FFN norm's ada row per slot (k_resid_xw_fplanes_slot), from the slot table
-static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4, int mixed) {
+// ragged: each slot's ring capacity from b->dcaps (the ragged attention instances; the shared
+// cap and ring_off are not read)
+static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4, int mixed, int ragged) {
     vox_hip_model_t* m = b->m;
     auto mx = [&](const WMx4D& M) -> const uint8_t* { return wmx4 ? M.frag : nullptr; };
     const vox_hip_config_t& c = m->c;
@@ -3854,9 +4083,10 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
     const int cap = c.dec_window + DEC_SLACK;
     const size_t ring_layer = (size_t)cap * DKV * kv_esize(kvt);
     hipStream_t st = b->st;
-    AttnPtrs ap;
-    memset(&ap, 0, sizeof ap);
+    AttnPtrsRag ap;  // (a plain step passes its AttnPtrs part alone)
+    memset((void*)&ap, 0, sizeof ap);
     ap.slots = b->slots;
+    ap.caps = b->dcaps;
     for (int i = 0; i < nb; i++) {
         ap.q[i] = b->q + (size_t)i * DQ;
         ap.part[i] = b->apart + (size_t)i * b->apart_n;
@@ -3879,7 +4109,12 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
         // launch; past 256 keys the last key-range block of a kv head merges the partials)
         AttnFuse af;
         af.qkv = b->part; af.S = skl_splits(DD, DQ + 2 * DKV); af.N = DQ + 2 * DKV; af.rope = m->rope_dec; af.xs = b->xp_q;
-        CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
+        if (ragged) {
+            ap.layer = l;
+            CK(launch_attn_batch_fused_rag(hd, ap, af, nb, c.dec_window, scale, H, KVH, splits, st, kvt));
+        } else {
+            CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
+        }
         CK(batch_gemm(b->xp_q, DQ, F.wo, mx(L.mo), L.so, DD, nb, b->part, st));
         if (mixed)
             CK(launch_resid_xw_fplanes_slots(b->x, nb, DD, L.ffn_norm, b->slots, (size_t)l * DD, b->xp_d, b->part,
@@ -4124,7 +4359,8 @@ extern "C" int vox_hip_batch_gemv_stats(const vox_hip_batch_t* b, long long* out
 // discipline); the step's last kernel advances the word past them, so the launches may be
 // captured and replayed.
 // mixed: the FFN norm's ada row per slot (rows_layers' RowsAda::slots)
-static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt, int mixed) {
+// ragged: each slot's ring capacity from b->dcaps, as batch_step
+static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt, int mixed, int ragged) {
     vox_hip_model_t* m = b->m;
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
@@ -4138,11 +4374,13 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
     int launches = 0;
     b->wide_q8 = 0;  // this step's launches on int8 fragments (batch_run counts them again per replay)
     const GemmfQ q{st, b->pgws, GEMM_WS_ELEMS, b->wflags, &launches, &m->n_gemmf_q8, b->wepoch, &b->wide_q8};
-    AttnSlots ap;
+    AttnSlotsRag ap;  // (a plain step passes its AttnSlots part alone)
     ap.q = nullptr; ap.q_ld = 0;
     ap.part = b->apart; ap.part_ld = b->apart_n;
     ap.out = gf ? nullptr : b->att; ap.out_ld = DQ;
     ap.slots = b->slots;
+    ap.ring_off = 0;
+    ap.caps = b->dcaps; ap.layer = 0;
     AttnFuse af;
     af.qkv = b->wqkv; af.S = 1; af.N = QKV; af.rope = m->rope_dec; af.xs = b->wpa;
     // RoPE + K/V append at each live slot's own position + attention over its ring, the rows
@@ -4150,7 +4388,9 @@ static int batch_step_wide(vox_hip_batch_t* b, int nb, int splits, int kvt, int 
     if (rows_layers(m, dec_rows_stack(c), RowsScratch{b->x, b->wqkv, b->wxn, b->att, b->whid, b->wpa, b->wpc}, q, gf, nb,
                     [&](int l, uint16_t*) -> int {
                         ap.ring_off = (size_t)l * ring_layer;
-                        CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
+                        ap.layer = l;
+                        if (ragged) CK(launch_attn_batch_wide_rag(hd, ap, af, nb, c.dec_window, scale, H, KVH, splits, st, kvt));
+                        else CK(launch_attn_batch_wide(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
                         return 0;
                     }, RowsAda{nullptr, mixed ? b->slots : nullptr}))
         return -1;
@@ -4182,14 +4422,16 @@ static int slot_bucket(int n, int* g) {
 
 // `steps` batched steps over slots 0..nb-1: replays of the bucket's step graph (captured the
 // first time, and again only when the rope table moved), or eager launches
-static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv, int mixed) {
+static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv, int mixed,
+                     int ragged) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
     const int gwmx4 = b->gemv_wmx4;  // likewise (vox_hip_batch_set_gemv_wmx4: on only with a plane to stream)
     const bool wide = nb > VOX_MAX_BATCH;  // buckets 64 and 128 (gemv == 0 there)
     auto step = [&]() {
-        return wide ? batch_step_wide(b, nb, splits, kvt, mixed)
-               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4, mixed);
+        return wide ? batch_step_wide(b, nb, splits, kvt, mixed, ragged)
+               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4, mixed, ragged);
     };
+    if (ragged) b->n_ragged_replays += steps;
     if (gemv) b->n_gemv_replays += steps;
     if (gemv && gwmx4) b->n_gemv_wmx4_replays += steps;
     if (!use_graphs()) {
@@ -4202,8 +4444,9 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
     }
-    hipGraphExec_t& ge = wide ? b->gwexec[mixed][kvt][gb - 6][gi]
-                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[mixed][3 * wmx4 + kvt][gb][gi];
+    const int mr = mixed + 2 * ragged;
+    hipGraphExec_t& ge = wide ? b->gwexec[mr][kvt][gb - 6][gi]
+                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[mr][3 * wmx4 + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
@@ -4220,6 +4463,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
             return set_err("batch graph instantiate failed: %s", hipGetErrorString(e));
         }
         b->n_captures++;
+        if (ragged) b->n_ragged_captures++;
         if (gemv) b->n_gemv_captures++;
     }
     for (int k = 0; k < steps; k++) CK(hipGraphLaunch(ge, b->st));
@@ -4366,6 +4610,48 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
         }
     }
     if (max_steps == 0) return 1;
+    // 0. growing rings (vox_hip_model_set_kv_grow): every listed stream's rings hold the whole
+    //    call before the prefills are queued and the slot table names them -- its position, the
+    //    prompt if it joins, and the steps its budget allows.  All the new rings are allocated
+    //    before a copy is enqueued: a failure returns with nothing enqueued and every stream as it
+    //    was.  The copies go on the batch queue (with rows[] the members' queues are not waited
+    //    for: no encoder pass touches a decoder ring).  Nothing moves again until the call ends.
+    int ragged = 0;
+    {
+        bool grows = false;
+        for (int i = 0; i < n; i++) grows = grows || streams[i]->dslots0;
+        if (grows) {
+            std::vector<DecGrow> gr(n);
+            for (int i = 0; i < n; i++) {
+                vox_hip_stream_t* s = streams[i];
+                const int np = 32 + stream_delay(s);
+                const bool joins = !s->started && !s->eos_seen && avail[i] >= 1 + np;
+                int need = 0;
+                if (s->started && !s->eos_seen) need = s->h_state[0] + std::max(0, std::min(avail[i] - s->h_state[1], max_steps));
+                else if (joins) need = np + std::max(0, std::min(avail[i] - np, max_steps));
+                if (dec_grow_alloc(s, need, true, &gr[i])) {
+                    dec_grow_drop(gr.data(), i);
+                    return -1;
+                }
+            }
+            // the capacities the call will run on: ragged if one of them is below the full size
+            for (int i = 0; i < n; i++) ragged |= (gr[i].cap ? gr[i].cap : streams[i]->dcap) != dec_ring_full(streams[i]);
+            if (ragged && !b->hcaps) {
+                // the per-slot capacity table of the ragged instances, on the first call that needs
+                // it -- before the growths are committed, so that a failure here too leaves every
+                // stream as it was
+                hipError_t e = b->dcaps ? hipSuccess : dalloc(&b->dcaps, (size_t)b->rows);
+                if (e == hipSuccess) e = hipHostMalloc((void**)&b->hcaps, sizeof(int) * b->rows, hipHostMallocDefault);
+                if (e != hipSuccess) {
+                    b->hcaps = nullptr;
+                    dec_grow_drop(gr.data(), n);
+                    return set_err("batch: per-slot ring capacity table: %s", hipGetErrorString(e));
+                }
+            }
+            if (dec_grow_commit(gr.data(), n, b->st)) return -1;
+        }
+        b->n_ragged_calls += ragged;
+    }
     // 1. streams whose prompt is complete and whose decoder has not started: their prefills
     //    in one stacked pass; they take their first token in the batched steps below
     {
@@ -4404,6 +4690,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
         memset(&hs[i], 0, sizeof hs[i]);
         hs[i].stop_tok = -1;
         hs[i].ada = m->ada_scale;  // (a row past the call's streams rides through the norms on the model's table)
+        if (ragged) b->hcaps[i] = i < n ? streams[i]->dcap : c.dec_window + DEC_SLACK;
         if (i >= n) continue;
         vox_hip_stream_t* s = streams[i];
         int lim = 0;
@@ -4434,6 +4721,7 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     const int gi = graph_index(streams[0], std::min(longest, c.dec_window));
     const int splits = graph_splits(streams[0], gi);
     CK(hipMemcpyAsync(b->slots, hs, sizeof(BatchSlot) * nb, hipMemcpyHostToDevice, b->st));
+    if (ragged) CK(hipMemcpyAsync(b->dcaps, b->hcaps, sizeof(int) * nb, hipMemcpyHostToDevice, b->st));
     CK(launch_embed_batch(b->slots, nb, m->tok_emb, m->tok_emb_s, c.dec_dim, b->x, b->st));
     // 3. the steps, in chunks of STEP_BATCH replays: after each chunk one copy of the slot
     //    table + token log comes back; the call ends when no slot is live.  The first chunk
@@ -4441,13 +4729,15 @@ static int batch_begin(vox_hip_batch_t* b, vox_hip_stream_t** streams, int n, co
     const int k = std::min(STEP_BATCH, K);
     // buckets of up to gemv_rows slots take the R-row GEMV step (vox_hip_batch_set_gemv_rows)
     // (a mixed call takes the MFMA step: k_gemvr has no per-slot prologue)
-    const int gemv = b->gemv_rows && nb <= b->gemv_rows && !mixed;
-    if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv, mixed)) return -1;
+    // (a ragged call too: k_gemvr's QKV epilogue takes one ring geometry for all rows)
+    const int gemv = b->gemv_rows && nb <= b->gemv_rows && !mixed && !ragged;
+    if (batch_run(b, nb, gb, gi, splits, kvt, k, gemv, mixed, ragged)) return -1;
     CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     auto& cl = b->call;
     cl.active = 1;
     cl.gemv = gemv;
     cl.mixed = mixed;
+    cl.ragged = ragged;
     cl.n = n;
     for (int i = 0; i < n; i++) cl.streams[i] = streams[i];
     cl.max_steps = max_steps;
@@ -4508,7 +4798,7 @@ static int batch_finish_steps(vox_hip_batch_t* b) {
         }
         if (!any || done >= K) break;
         k = std::min(STEP_BATCH, K - done);
-        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv, cl.mixed)) return -1;
+        if (batch_run(b, cl.nb, cl.gb, cl.gi, cl.splits, cl.kvt, k, cl.gemv, cl.mixed, cl.ragged)) return -1;
         CK(hipMemcpyAsync(hs, b->slots, slot_bytes(b->rows), hipMemcpyDeviceToHost, b->st));
     }
     // 4. host mirrors
@@ -4586,6 +4876,16 @@ extern "C" int vox_hip_batch_read_logits(vox_hip_batch_t* b, vox_hip_stream_t* s
             return 0;
         }
     return set_err("batch_read_logits: the stream was not advanced by the last batched step");
+}
+
+// ragged calls (a listed stream's decoder rings shorter than the full size), their step replays
+// and their graph captures, since creation
+extern "C" int vox_hip_batch_kv_grow_stats(const vox_hip_batch_t* b, long long out3[3]) {
+    if (!b || !out3) return set_err("batch_kv_grow_stats: null argument");
+    out3[0] = b->n_ragged_calls;
+    out3[1] = b->n_ragged_replays;
+    out3[2] = b->n_ragged_captures;
+    return 0;
 }
 
 extern "C" int vox_hip_batch_stats(const vox_hip_batch_t* b, long long* out6) {

@@ -121,6 +121,20 @@ struct AttnSlots {
     const BatchSlot* slots;
     size_t ring_off;
 };
+// The ragged forms of the two: a batched call in which some stream's decoder rings
+// are shorter than window + slack (vox_hip_model_set_kv_grow).  Row z's ring holds caps[z] slots:
+// that capacity is the slot modulo, and layer `layer` of the ring starts
+// layer * caps[z] * KVH * hd * sizeof(element) bytes past the slot's Kc / Vc (ring_off and the
+// launch's shared cap are not read).  caps is a table beside the slot table, [slot] ints, that
+// only these instances read: BatchSlot, its upload and every plain instance stay as they are.
+struct AttnPtrsRag : AttnPtrs {
+    const int* caps = nullptr;
+    int layer = 0;
+};
+struct AttnSlotsRag : AttnSlots {
+    const int* caps;
+    int layer;
+};
 // Kc / Vc of the decoder rings point at f32 elements, at IEEE half ones in the 16-bit mode
 // (VOX_DECODER_KV_FP16) or at FP8 E4M3 bytes in the one-byte mode (VOX_HIP_KV_FP8, vox_kv8.h):
 // the kvt argument of the launchers
@@ -205,6 +219,13 @@ hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f,
 // block of a (slot, kv head) to arrive merging the partials
 hipError_t launch_attn_batch_wide(int hd, const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window,
                                   float scale, int H, int KVH, int splits, hipStream_t st, int kvt = 0);
+
+// the two launches above over rings of per-slot capacity (p.caps, p.layer; no shared cap): the
+// same grids, blocks and arithmetic, only the ring addresses differ
+hipError_t launch_attn_batch_fused_rag(int hd, const AttnPtrsRag& p, const AttnFuse& f, int nb, int window, float scale,
+                                       int H, int KVH, int splits, hipStream_t st, int kvt = 0);
+hipError_t launch_attn_batch_wide_rag(int hd, const AttnSlotsRag& p, const AttnFuse& f, int nb, int window, float scale,
+                                      int H, int KVH, int splits, hipStream_t st, int kvt = 0);
 
 // a batched encoder pass: rows [off[b], off[b] + nr[b]) of the stacked rows belong to stream
 // b, at logical positions pos0[b] + i, with its own K/V ring (layer base)

@@ -1574,15 +1574,23 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AP P, int cap, i
                                                           int window, float scale, int H, int KVH,
                                                           int maxs, const AttnFuse F = AttnFuse{}, int kvfast = 0) {
     constexpr int NT = NWV * 64, BK = NWV * ATT_CH;
-    constexpr bool ATTN_ROWS = std::is_same<AP, AttnSlots>::value;  // fused output also as f32 rows (out != null)
+    constexpr bool ATTN_ROWS = std::is_base_of<AttnSlots, AP>::value;  // fused output also as f32 rows (out != null)
+    // the ragged forms (AttnPtrsRag / AttnSlotsRag): the ring's capacity, hence the slot modulo
+    // below and the layer's offset, from the slot's entry of P.caps
+    constexpr bool RAGGED = std::is_base_of<AttnPtrsRag, AP>::value || std::is_base_of<AttnSlotsRag, AP>::value;
     const int zb = blockIdx.z;  // stream of a batched step (0 for a single stream)
     // batched step: ring, position and liveness from the slot table (a stopped slot's blocks
     // leave at once; uniform per block)
     const BatchSlot* __restrict__ sl = P.slots ? P.slots + zb : nullptr;
     if (sl && !sl->live) return;
+    size_t ring_off = P.ring_off;
+    if constexpr (RAGGED) {
+        cap = P.caps[zb];
+        ring_off = (size_t)P.layer * cap * KVH * HD * sizeof(KT);
+    }
     const float* __restrict__ q = attn_q(P, zb);
-    const KT* __restrict__ Kc = reinterpret_cast<const KT*>(sl ? sl->Kc + P.ring_off : attn_k(P, zb));
-    const KT* __restrict__ Vc = reinterpret_cast<const KT*>(sl ? sl->Vc + P.ring_off : attn_v(P, zb));
+    const KT* __restrict__ Kc = reinterpret_cast<const KT*>(sl ? sl->Kc + ring_off : attn_k(P, zb));
+    const KT* __restrict__ Vc = reinterpret_cast<const KT*>(sl ? sl->Vc + ring_off : attn_v(P, zb));
     const int* __restrict__ state = sl ? nullptr : attn_state(P, zb);
     float* __restrict__ part = attn_part(P, zb);
     float* __restrict__ out = attn_out(P, zb);
@@ -4440,8 +4448,9 @@ hipError_t launch_attn_decode_batch(int hd, const AttnPtrs& p, int nb, int cap, 
                            : attn_launch<float>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
 }
 
-template <class KT>
-static hipError_t attn_batch_fused(const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window, float scale,
+// AP: AttnPtrs, or AttnPtrsRag (per-slot ring capacity: cap is not read)
+template <class KT, class AP = AttnPtrs>
+static hipError_t attn_batch_fused(const AP& p, const AttnFuse& f, int nb, int cap, int window, float scale,
                                    int H, int KVH, int splits, int maxs, hipStream_t st) {
     if (g_attn_bsplit < 0) {
         const char* e = getenv("VOX_HIP_ATT_BSPLIT");
@@ -4452,15 +4461,32 @@ static hipError_t attn_batch_fused(const AttnPtrs& p, const AttnFuse& f, int nb,
     // blocks of the long path (two per (stream, kv head), last arriver merges);
     // VOX_HIP_ATT_BSPLIT=2: the 128-key blocks at any row count
     if (splits == 1 && (!g_attn_bsplit || (g_attn_bsplit == 1 && nb * KVH >= 256))) {
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT>), dim3(1, KVH, nb), dim3(1024), 0, st, p, cap, 0,
+        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p, cap, 0,
                            window, scale, H, KVH, maxs, f);
         LAUNCH_CHECK();
         return hipSuccess;
     }
-    hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT>), dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb),
+    hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AP>), dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb),
                        dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window, scale, H, KVH, maxs, f, 1);
     LAUNCH_CHECK();
     return hipSuccess;
+}
+
+static bool attn_batch_args_ok(int hd, const AttnFuse& f, int nb, int nb_max, int window, int H, int KVH, int splits,
+                               int kvt) {
+    return kvt >= KV_F32 && kvt <= KV_FP8 && hd == 128 && H % KVH == 0 && H / KVH <= 4 &&
+           attn_maxch(window) <= ATT_MAX_PARTS && splits >= 1 && splits <= attn_maxsplits(window) && nb >= 1 &&
+           nb <= nb_max && f.qkv && f.rope && f.xs && f.N == (H + 2 * KVH) * hd;
+}
+
+hipError_t launch_attn_batch_fused_rag(int hd, const AttnPtrsRag& p, const AttnFuse& f, int nb, int window, float scale,
+                                       int H, int KVH, int splits, hipStream_t st, int kvt) {
+    const int maxs = attn_maxch(window);
+    if (!attn_batch_args_ok(hd, f, nb, VOX_MAX_BATCH, window, H, KVH, splits, kvt) || f.S < 1 || !p.slots || !p.caps)
+        return hipErrorInvalidValue;
+    return kvt == KV_FP8   ? attn_batch_fused<kv8_t, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
+           : kvt == KV_F16 ? attn_batch_fused<kvh_t, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
+                           : attn_batch_fused<float, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st);
 }
 
 hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window,
@@ -4476,14 +4502,15 @@ hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f,
 // the wide step's instances: the fused kernels over the compact slot-table argument (blockIdx.z
 // up to VOX_MAX_SLOTS).  64 slots x 8 kv heads already fill the chip, so <= 256 keys always
 // take the 1024-thread block (no bsplit rule); past 256 keys the 128-key grid of the <= 32 step
-template <class KT>
-static hipError_t attn_batch_wide(const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+// AP: AttnSlots, or AttnSlotsRag (per-slot ring capacity: cap is not read)
+template <class KT, class AP = AttnSlots>
+static hipError_t attn_batch_wide(const AP& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
                                   int KVH, int splits, int maxs, hipStream_t st) {
     if (splits == 1)
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AttnSlots>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
+        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
                            cap, 0, window, scale, H, KVH, maxs, f, 0);
     else
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AttnSlots>),
+        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AP>),
                            dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb), dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window,
                            scale, H, KVH, maxs, f, 1);
     LAUNCH_CHECK();
@@ -4502,6 +4529,16 @@ hipError_t launch_attn_batch_wide(int hd, const AttnSlots& p, const AttnFuse& f,
     return kvt == KV_FP8   ? attn_batch_wide<kv8_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
            : kvt == KV_F16 ? attn_batch_wide<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
                            : attn_batch_wide<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
+}
+hipError_t launch_attn_batch_wide_rag(int hd, const AttnSlotsRag& p, const AttnFuse& f, int nb, int window, float scale,
+                                      int H, int KVH, int splits, hipStream_t st, int kvt) {
+    const int maxs = attn_maxch(window);
+    if (!attn_batch_args_ok(hd, f, nb, VOX_MAX_SLOTS, window, H, KVH, splits, kvt) || f.S != 1 || !p.slots || !p.caps ||
+        !p.part || p.part_ld < (size_t)H * maxs * (hd + 2) + KVH)
+        return hipErrorInvalidValue;
+    return kvt == KV_FP8   ? attn_batch_wide<kv8_t, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
+           : kvt == KV_F16 ? attn_batch_wide<kvh_t, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
+                           : attn_batch_wide<float, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st);
 }
 // diagnostic variants for tools/kbench (not used by the engine)
 // the batched fused attention (128-key blocks, the bsplit grid) with per-wave phase stamps

@@ -1106,6 +1106,13 @@ int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on) {
 
 int vh_stream_enc_kv_fp16(const vh_stream_t *s) { return vox_hip_stream_enc_kv_fp16(s->st); }
 
+int vh_set_kv_grow(vh_ctx_t *ctx, int slots0) {
+    if (vox_hip_model_set_kv_grow(ctx->model, slots0)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_stream_kv_slots(const vh_stream_t *s) { return vox_hip_stream_kv_slots(s->st); }
+
 int vh_stream_pending(vh_stream_t *s) {
     int st6[6];
     vox_hip_stream_state(s->st, st6);

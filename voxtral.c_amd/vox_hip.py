@@ -124,6 +124,8 @@ EXPORTS = [
     "vox_hip_model_set_kv_dtype", "vox_hip_stream_kv_dtype", "vox_hip_stream_read_kv", "vox_hip_kv8_convert",
     "vox_hip_model_set_enc_kv_fp16", "vox_hip_stream_enc_kv_fp16", "vox_hip_stream_read_enc_kv",
     "vox_hip_stream_enc_kv_bytes", "vox_hip_stream_enc_paths",
+    "vox_hip_model_set_kv_grow", "vox_hip_stream_kv_slots", "vox_hip_stream_kv_bytes",
+    "vox_hip_stream_kv_grow_stats", "vox_hip_stream_reserve_kv", "vox_hip_batch_kv_grow_stats",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
@@ -178,6 +180,11 @@ def lib():
         "vox_hip_stream_read_enc_kv": (I, [P, I, I, I, P, P]),
         "vox_hip_stream_enc_kv_bytes": (ctypes.c_longlong, [P]),
         "vox_hip_stream_enc_paths": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_model_set_kv_grow": (I, [P, I]), "vox_hip_stream_kv_slots": (I, [P]),
+        "vox_hip_stream_kv_bytes": (ctypes.c_longlong, [P]),
+        "vox_hip_stream_kv_grow_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_stream_reserve_kv": (I, [P, I]),
+        "vox_hip_batch_kv_grow_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_kv8_convert": (I, [fp, I, P, fp]),
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
@@ -419,6 +426,13 @@ class Model:
         if lib().vox_hip_model_set_enc_kv_fp16(self.h, int(on)) != 0:
             _err("set_enc_kv_fp16")
 
+    def set_kv_grow(self, slots0: int):
+        """vox_hip_model_set_kv_grow: streams created afterwards start with decoder K/V rings of
+        slots0 slots (clamped to [64, dec_window + 64]) that double as their position needs them,
+        up to the full ring; lossless.  0: full rings from the start (the default)"""
+        if lib().vox_hip_model_set_kv_grow(self.h, int(slots0)) != 0:
+            _err("set_kv_grow")
+
     def wpack_stats(self) -> dict:
         """What the single-stream decode GEMV streams as wpack13 planes (13 bits per bf16
         weight, lossless) and what stayed raw: tensor counts, bytes, host packing time"""
@@ -539,6 +553,30 @@ class Stream:
         if dt is np.uint8:
             return kv8_decode(k), kv8_decode(v)
         return k.astype(np.float32), v.astype(np.float32)
+
+    @property
+    def kv_slots(self) -> int:
+        """slots of the decoder K/V rings now (dec_window + 64 unless Model.set_kv_grow)"""
+        return lib().vox_hip_stream_kv_slots(self.h)
+
+    @property
+    def kv_bytes(self) -> int:
+        """bytes of the stream's decoder K and V rings together"""
+        return int(lib().vox_hip_stream_kv_bytes(self.h))
+
+    def kv_grow_stats(self) -> dict:
+        """vox_hip_stream_kv_grow_stats: growths of the decoder rings, bytes copied, slots now"""
+        out = (ctypes.c_longlong * 3)()
+        if lib().vox_hip_stream_kv_grow_stats(self.h, out) != 0:
+            _err("kv_grow_stats")
+        return dict(zip(("grows", "copied", "slots"), (int(v) for v in out)))
+
+    def reserve_kv(self, positions: int):
+        """vox_hip_stream_reserve_kv: grow the decoder rings ahead of time to hold `positions`
+        positions (the full ring at most); raises when they cannot be allocated or the stream is
+        held by a begun batched call"""
+        if lib().vox_hip_stream_reserve_kv(self.h, int(positions)) != 0:
+            _err("reserve_kv")
 
     @property
     def enc_kv_fp16(self) -> bool:
@@ -879,7 +917,9 @@ class Batch:
     max_streams: 1..BATCH_MAX_SLOTS (128).  Calls with up to 32 streams run the skinny MFMA step
     (or the opt-in R-row GEMV step, which the set_gemv_* / set_wmx4 switches act on); calls with
     33..128 streams run the wide k_gemmf step over the bf16 fragment-major copies.  Decoder KV
-    rings at 128 streams: ~225 GB f32, ~113 GB half, ~56 GB FP8 (Model.set_kv_dtype)."""
+    rings at 128 streams: ~225 GB f32, ~113 GB half, ~56 GB FP8 (Model.set_kv_dtype) as full rings;
+    with Model.set_kv_grow they follow each session's length instead (~28 GB f32 one minute in).
+    Streams of any ring capacities share a call (kv_grow_stats counts the ragged steps)."""
 
     def __init__(self, model: "Model", max_streams: int):
         if not 1 <= int(max_streams) <= BATCH_MAX_SLOTS:
@@ -922,6 +962,14 @@ class Batch:
             _err("vox_hip_batch_stats")
         keys = ("calls", "replays", "rows", "captures", "prefill_passes", "prefilled")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def kv_grow_stats(self) -> dict:
+        """vox_hip_batch_kv_grow_stats: calls with a decoder ring shorter than the full size
+        (Model.set_kv_grow), their step replays and step-graph captures"""
+        out = (ctypes.c_longlong * 3)()
+        if lib().vox_hip_batch_kv_grow_stats(self.h, out) != 0:
+            _err("vox_hip_batch_kv_grow_stats")
+        return dict(zip(("ragged_calls", "ragged_replays", "ragged_captures"), (int(v) for v in out)))
 
     def set_gemv_rows(self, max_rows: int) -> int:
         """vox_hip_batch_set_gemv_rows: steps of up to max_rows slots (0, 1, 2, 4, 8) take the
@@ -1078,6 +1126,7 @@ def host_lib():
         "vh_sched_set_step_cap": (None, [P, I]), "vh_stream_pending": (I, [P]),
         "vh_stream_set_delay": (I, [P, I]), "vh_stream_delay_ms": (I, [P]),
         "vh_set_enc_kv_fp16": (I, [P, I]), "vh_stream_enc_kv_fp16": (I, [P]),
+        "vh_set_kv_grow": (I, [P, I]), "vh_stream_kv_slots": (I, [P]),
         "vh_sched_debug_fail_next_encode": (None, [P]),
         "vh_stream_adapter_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
     }
@@ -1102,6 +1151,11 @@ class HostCtx:
         self.h = host_lib().vh_ctx_wrap(model.h, ctypes.byref(model._cfg_c), model.delay_tokens)
         if not self.h:
             _herr("vh_ctx_wrap")
+
+    def set_kv_grow(self, slots0: int):
+        """vh_set_kv_grow: streams initialised afterwards start with decoder rings of slots0 slots"""
+        if host_lib().vh_set_kv_grow(self.h, int(slots0)) != 0:
+            _herr("vh_set_kv_grow")
 
     def close(self):
         if self.h:
@@ -1162,6 +1216,10 @@ class HostStream:
     def pending(self) -> int:
         """adapter rows not decoded yet (vh_stream_pending)"""
         return host_lib().vh_stream_pending(self.h)
+
+    def kv_slots(self) -> int:
+        """vh_stream_kv_slots: slots of the decoder K/V rings of the stream behind this one"""
+        return host_lib().vh_stream_kv_slots(self.h)
 
     def adapter_stats(self) -> dict:
         """vh_stream_adapter_stats: as Stream.adapter_stats, for the stream behind this one"""
