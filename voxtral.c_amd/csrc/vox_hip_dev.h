@@ -263,4 +263,116 @@ __device__ __forceinline__ bf16x8 i8x8_bf16(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(bf16x8, make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)));
 }
 
+// ============================================================================
+// Decoder KV element type.  f32 by default (the CPU reference's cache); the opt-in 16-bit
+// mode (VOX_DECODER_KV_FP16, voxtral.c:189-190, voxtral_decoder.c:180-243) stores IEEE half:
+// stores round to nearest even, loads widen to f32, all arithmetic stays f32.  Kernels that
+// read the ring are templated on the element type; the two single-store epilogues (decode
+// QKV GEMV, batched RoPE + append) take it as a uniform runtime value (KV_F32 / KV_F16 / KV_FP8).
+// ============================================================================
+typedef _Float16 kvh_t;
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+// The opt-in one-byte mode (VOX_HIP_KV_FP8, KV_FP8): OCP FP8 E4M3 without a scale, by the
+// rule of vox_kv8.h.  Loads widen with v_cvt_pk_f32_fp8 (exact); the store clamps to +-448 in
+// f32 first (the conversion by itself gives NaN past the largest finite value, the rule
+// saturates) and then rounds with v_cvt_pk_fp8_f32 (nearest, ties to even, subnormals kept);
+// NaN is written as 0x7f with the sign whatever the instruction makes of it.
+__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : v < -448.f ? -448.f : v; }
+__device__ __forceinline__ unsigned kv8_fix_nan(float v, unsigned code) {
+    return v != v ? (0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) : code;
+}
+// the pair (a, b) as two codes, a in bits 0..7
+__device__ __forceinline__ unsigned kv8_enc2(float a, float b) {
+    const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
+    return kv8_fix_nan(a, w & 0xffu) | (kv8_fix_nan(b, (w >> 8) & 0xffu) << 8);
+}
+struct kv8_t {
+    uint8_t b;
+    kv8_t() = default;
+    __device__ __forceinline__ explicit kv8_t(float v) : b((uint8_t)(kv8_enc2(v, v) & 0xffu)) {}
+    __device__ __forceinline__ explicit operator float() const {
+        return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0];
+    }
+};
+static_assert(sizeof(kv8_t) == 1, "kv8_t: one byte per ring element");
+// ring element type of the launchers' kvt argument
+template <class T> __device__ __forceinline__ float4 kv_ld4(const T* p) {
+    if constexpr (sizeof(T) == 4) {
+        return *reinterpret_cast<const float4*>(p);
+    } else if constexpr (sizeof(T) == 2) {
+        const h16x4 h = *reinterpret_cast<const h16x4*>(p);
+        return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+    } else {
+        const int w = *reinterpret_cast<const int*>(p);
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+        return make_float4(lo[0], lo[1], hi[0], hi[1]);
+    }
+}
+template <class T> __device__ __forceinline__ float2 kv_ld2(const T* p) {
+    if constexpr (sizeof(T) == 4) {
+        return *reinterpret_cast<const float2*>(p);
+    } else if constexpr (sizeof(T) == 2) {
+        const h16x2 h = *reinterpret_cast<const h16x2*>(p);
+        return make_float2((float)h[0], (float)h[1]);
+    } else {
+        const auto v = __builtin_amdgcn_cvt_pk_f32_fp8((int)*reinterpret_cast<const uint16_t*>(p), false);
+        return make_float2(v[0], v[1]);
+    }
+}
+template <class T> __device__ __forceinline__ float kv_round(float v) { return (float)(T)v; }
+template <class T> __device__ __forceinline__ void kv_st2(T* p, float a, float b) {
+    if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float2*>(p) = make_float2(a, b);
+    } else if constexpr (sizeof(T) == 2) {
+        *reinterpret_cast<h16x2*>(p) = h16x2{(T)a, (T)b};
+    } else {
+        *reinterpret_cast<uint16_t*>(p) = (uint16_t)kv8_enc2(a, b);
+    }
+}
+// A value as the f32 it rounds to, before a half store.  Without it the compiler folds a roped
+// key's last fma and the conversion into v_fma_mixlo_f16, which rounds the exact fma once: at an
+// f32 value that lies halfway between two halves the stored half is then not the nearest-even
+// rounding of the f32 ring's element.  The encoder's half instances store kv_f32(...) values, so
+// their rings hold half(f32 element) bit for bit; the decoder's instances are as they were.
+__device__ __forceinline__ float kv_f32(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// element e of a ring (f32, half or fp8 by the element type) written as the pair (a, b) at e, e + 1
+__device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float b, int kvt) {
+    if (kvt == KV_FP8) kv_st2(reinterpret_cast<kv8_t*>(base) + e, a, b);
+    else if (kvt == KV_F16) kv_st2(reinterpret_cast<kvh_t*>(base) + e, a, b);
+    else kv_st2(base + e, a, b);
+}
+
+// stream_fill_alts (voxtral.c:955-1010) partials for one logit: running max / sum of
+// exp for the softmax, and an ascending-id-stable top-4 of ids >= TOKEN_TEXT_MIN (rows
+// arrive in ascending order, so a strict '>' keeps the lower id first on ties).
+__device__ __forceinline__ void alt_row(float v, int r, float& am, float& as, float (&tv)[4], int (&ti)[4]) {
+    if (v > am) {
+        as = as * expf(am - v) + 1.0f;
+        am = v;
+    } else {
+        as += expf(v - am);
+    }
+    if (r >= ALT_TEXT_MIN && v > tv[3]) {
+        // v replaces the smallest and rises past every strictly smaller entry; the entries
+        // above it are sorted, so no later pair swaps.  Static indices only: a run-time index
+        // into tv / ti put both arrays in scratch (48 B per lane).
+        tv[3] = v;
+        ti[3] = r;
+#pragma unroll
+        for (int k = 3; k > 0; k--) {
+            const bool up = tv[k] > tv[k - 1];
+            const float fv = tv[k];
+            const int fi = ti[k];
+            tv[k] = up ? tv[k - 1] : fv;
+            ti[k] = up ? ti[k - 1] : fi;
+            tv[k - 1] = up ? fv : tv[k - 1];
+            ti[k - 1] = up ? fi : ti[k - 1];
+        }
+    }
+}
+
 }  // namespace vox

@@ -57,6 +57,14 @@ struct GemvArgs {
 // decoder KV ring element types (vox_hip_model_set_kv_dtype); the element's size in bytes
 enum { KV_F32 = 0, KV_F16 = 1, KV_FP8 = 2 };
 static inline size_t kv_esize(int kvt) { return kvt == KV_FP8 ? 1 : kvt == KV_F16 ? 2 : 4; }
+// Which rings exist, for every launcher's kvt argument (the element type that Kc / Vc point at):
+// f32 rings at any head_dim; the decoder's 16-bit (VOX_DECODER_KV_FP16) and one-byte (VOX_HIP_KV_FP8,
+// vox_kv8.h) rings at head_dim 128 only; the encoder's opt-in 16-bit rings
+// (vox_hip_model_set_enc_kv_fp16) at head_dim 64.  KV_FP8 at head_dim 64 is refused: there is no
+// one-byte encoder ring.  The launchers pick their instance through kv_ring (vox_hip_kernels.hip).
+static inline bool kv_ring_ok(int kvt, int hd) {
+    return kvt == KV_F32 || (kvt == KV_F16 && (hd == 128 || hd == 64)) || (kvt == KV_FP8 && hd == 128);
+}
 
 constexpr int VOX_MAX_BATCH = 32;    // streams per skinny batched decode step (two 16-row blocks of the MFMA B
                                      // operand), per batched encoder pass (EncRows) and per vox_hip_skinny_wmx4 call
@@ -135,10 +143,6 @@ struct AttnSlotsRag : AttnSlots {
     const int* caps;
     int layer;
 };
-// Kc / Vc of the decoder rings point at f32 elements, at IEEE half ones in the 16-bit mode
-// (VOX_DECODER_KV_FP16) or at FP8 E4M3 bytes in the one-byte mode (VOX_HIP_KV_FP8, vox_kv8.h):
-// the kvt argument of the launchers
-
 // batched decode attention with the QKV epilogue folded in (k_attn_decode<.., FUSE = 1>):
 // RoPE of q / k and the KV append read the QKV projection's split-K slabs, and the output
 // goes straight into the wo input planes
@@ -237,9 +241,7 @@ struct EncRows {
 };
 // RoPE + K/V append of every stacked row into its stream's ring (k_rope_kv per row block)
 // kvt (here and in launch_attn_rows): the rings' element type, er.Kc / er.Vc point at such
-// elements.  The decoder's 16-bit and one-byte rings at head_dim 128 only; the encoder's opt-in
-// 16-bit rings (vox_hip_model_set_enc_kv_fp16) at head_dim 64.  KV_FP8 at head_dim 64 is refused:
-// there is no one-byte encoder ring.
+// elements (kv_ring_ok)
 hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd, const float* rope_table,
                                const EncRows& er, float* q, int cap, hipStream_t st, int kvt = 0);
 // windowed attention of every stream's rows against its own ring, one launch (+ one combine):

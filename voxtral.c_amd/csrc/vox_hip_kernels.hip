@@ -30,89 +30,6 @@
 namespace vox {
 
 // ============================================================================
-// Decoder KV element type.  f32 by default (the CPU reference's cache); the opt-in 16-bit
-// mode (VOX_DECODER_KV_FP16, voxtral.c:189-190, voxtral_decoder.c:180-243) stores IEEE half:
-// stores round to nearest even, loads widen to f32, all arithmetic stays f32.  Kernels that
-// read the ring are templated on the element type; the two single-store epilogues (decode
-// QKV GEMV, batched RoPE + append) take it as a uniform runtime value (KV_F32 / KV_F16 / KV_FP8).
-// ============================================================================
-typedef _Float16 kvh_t;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-// The opt-in one-byte mode (VOX_HIP_KV_FP8, KV_FP8): OCP FP8 E4M3 without a scale, by the
-// rule of vox_kv8.h.  Loads widen with v_cvt_pk_f32_fp8 (exact); the store clamps to +-448 in
-// f32 first (the conversion by itself gives NaN past the largest finite value, the rule
-// saturates) and then rounds with v_cvt_pk_fp8_f32 (nearest, ties to even, subnormals kept);
-// NaN is written as 0x7f with the sign whatever the instruction makes of it.
-__device__ __forceinline__ float kv8_clamp(float v) { return v > 448.f ? 448.f : v < -448.f ? -448.f : v; }
-__device__ __forceinline__ unsigned kv8_fix_nan(float v, unsigned code) {
-    return v != v ? (0x7fu | ((__float_as_uint(v) >> 24) & 0x80u)) : code;
-}
-// the pair (a, b) as two codes, a in bits 0..7
-__device__ __forceinline__ unsigned kv8_enc2(float a, float b) {
-    const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a), kv8_clamp(b), 0, false);
-    return kv8_fix_nan(a, w & 0xffu) | (kv8_fix_nan(b, (w >> 8) & 0xffu) << 8);
-}
-struct kv8_t {
-    uint8_t b;
-    kv8_t() = default;
-    __device__ __forceinline__ explicit kv8_t(float v) : b((uint8_t)(kv8_enc2(v, v) & 0xffu)) {}
-    __device__ __forceinline__ explicit operator float() const {
-        return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0];
-    }
-};
-static_assert(sizeof(kv8_t) == 1, "kv8_t: one byte per ring element");
-// ring element type of the launchers' kvt argument
-template <class T> __device__ __forceinline__ float4 kv_ld4(const T* p) {
-    if constexpr (sizeof(T) == 4) {
-        return *reinterpret_cast<const float4*>(p);
-    } else if constexpr (sizeof(T) == 2) {
-        const h16x4 h = *reinterpret_cast<const h16x4*>(p);
-        return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-    } else {
-        const int w = *reinterpret_cast<const int*>(p);
-        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
-        return make_float4(lo[0], lo[1], hi[0], hi[1]);
-    }
-}
-template <class T> __device__ __forceinline__ float2 kv_ld2(const T* p) {
-    if constexpr (sizeof(T) == 4) {
-        return *reinterpret_cast<const float2*>(p);
-    } else if constexpr (sizeof(T) == 2) {
-        const h16x2 h = *reinterpret_cast<const h16x2*>(p);
-        return make_float2((float)h[0], (float)h[1]);
-    } else {
-        const auto v = __builtin_amdgcn_cvt_pk_f32_fp8((int)*reinterpret_cast<const uint16_t*>(p), false);
-        return make_float2(v[0], v[1]);
-    }
-}
-template <class T> __device__ __forceinline__ float kv_round(float v) { return (float)(T)v; }
-template <class T> __device__ __forceinline__ void kv_st2(T* p, float a, float b) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float2*>(p) = make_float2(a, b);
-    } else if constexpr (sizeof(T) == 2) {
-        *reinterpret_cast<h16x2*>(p) = h16x2{(T)a, (T)b};
-    } else {
-        *reinterpret_cast<uint16_t*>(p) = (uint16_t)kv8_enc2(a, b);
-    }
-}
-// A value as the f32 it rounds to, before a half store.  Without it the compiler folds a roped
-// key's last fma and the conversion into v_fma_mixlo_f16, which rounds the exact fma once: at an
-// f32 value that lies halfway between two halves the stored half is then not the nearest-even
-// rounding of the f32 ring's element.  The encoder's half instances store kv_f32(...) values, so
-// their rings hold half(f32 element) bit for bit; the decoder's instances are as they were.
-__device__ __forceinline__ float kv_f32(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-// element e of a ring (f32, half or fp8 by the element type) written as the pair (a, b) at e, e + 1
-__device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float b, int kvt) {
-    if (kvt == KV_FP8) kv_st2(reinterpret_cast<kv8_t*>(base) + e, a, b);
-    else if (kvt == KV_F16) kv_st2(reinterpret_cast<kvh_t*>(base) + e, a, b);
-    else kv_st2(base + e, a, b);
-}
-
-// ============================================================================
 // Row-wise RMSNorm (+ optional ada scale), M>1 paths.  voxtral_kernels.c:475-492,
 // voxtral_decoder.c:564-570.  One block per row.
 // ============================================================================
@@ -777,755 +694,6 @@ __global__ __launch_bounds__(HD) void k_attn_tiled_combine(const float* __restri
         *reinterpret_cast<uint4*>(xs + frag_at(q, K, 0, k)) = make_uint4(hp[0], hp[1], hp[2], hp[3]);
         *reinterpret_cast<uint4*>(xs + frag_at(q, K, 1, k)) = make_uint4(mp[0], mp[1], mp[2], mp[3]);
         *reinterpret_cast<uint4*>(xs + frag_at(q, K, 2, k)) = make_uint4(lp[0], lp[1], lp[2], lp[3]);
-    }
-}
-
-// ============================================================================
-// M=1 weight-streaming GEMV with fused prologue / epilogue (decoder step).
-//
-// A block (4 waves) owns groups of RB rows and streams them with K split across its
-// waves: wave w reads the 1-KiB chunk blocks j*4+w of every row, so each wave keeps only
-// its quarter of x in registers (loaded once per block, normalised there when PRO_NORM),
-// never stages x through LDS, and a launch needs no more blocks than CUs x 4 to stay
-// balanced (grid-stride over groups).  Weights: 16-B non-temporal loads straight to
-// VGPRs (cdna_hip_programming.md "GEMV / M <= 16" row).  Partial sums meet in LDS; wave
-// 0 applies the epilogue.  Summation order is fixed (deterministic).
-// ============================================================================
-// stream_fill_alts (voxtral.c:955-1010) partials for one logit: running max / sum of
-// exp for the softmax, and an ascending-id-stable top-4 of ids >= TOKEN_TEXT_MIN (rows
-// arrive in ascending order, so a strict '>' keeps the lower id first on ties).
-__device__ __forceinline__ void alt_row(float v, int r, float& am, float& as, float (&tv)[4], int (&ti)[4]) {
-    if (v > am) {
-        as = as * expf(am - v) + 1.0f;
-        am = v;
-    } else {
-        as += expf(v - am);
-    }
-    if (r >= ALT_TEXT_MIN && v > tv[3]) {
-        // v replaces the smallest and rises past every strictly smaller entry; the entries
-        // above it are sorted, so no later pair swaps.  Static indices only: a run-time index
-        // into tv / ti put both arrays in scratch (48 B per lane).
-        tv[3] = v;
-        ti[3] = r;
-#pragma unroll
-        for (int k = 3; k > 0; k--) {
-            const bool up = tv[k] > tv[k - 1];
-            const float fv = tv[k];
-            const int fi = ti[k];
-            tv[k] = up ? tv[k - 1] : fv;
-            ti[k] = up ? ti[k - 1] : fi;
-            tv[k - 1] = up ? fv : tv[k - 1];
-            ti[k - 1] = up ? fi : ti[k - 1];
-        }
-    }
-}
-
-template <int EPI, int RB>
-__device__ __forceinline__ void gemv_rows(int g, int (&rows)[RB]) {
-#pragma unroll
-    for (int i = 0; i < RB; i++) {
-        if (EPI == EPI_SWIGLU) {
-            // pair i = (w1 row, w3 row) of hidden unit u = g*RB/2 + i/2 (16-row interleave)
-            const int u = g * (RB / 2) + (i >> 1);
-            rows[i] = ((u >> 4) << 5) + (u & 15) + ((i & 1) << 4);
-        } else {
-            rows[i] = g * RB + i;
-        }
-    }
-}
-
-// Weight rows come in through a buffer descriptor: the row offset is wave-uniform (an SGPR
-// soffset) and each lane keeps one 32-bit chunk offset per K round (voff), instead of a
-// 64-bit address per (row, round) -- the register count sets how many blocks stay resident.
-// Non-temporal (aux = 2: nt): every weight byte is read once per step.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-template <int RB, int KQ, bool WP = false>
-__device__ __forceinline__ void gemv_load(__amdgpu_buffer_rsrc_t W, int rowbytes, const int (&rows)[RB],
-                                          const int (&voff)[KQ], uint4 (&wv)[KQ][RB]) {
-#pragma unroll
-    for (int j = 0; j < KQ; j++)
-#pragma unroll
-        for (int i = 0; i < RB; i++) {
-            if constexpr (WP) {  // wpack13: 12-B chunks
-                const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(W, voff[j], rows[i] * rowbytes, 2);
-                wv[j][i] = make_uint4(v.x, v.y, v.z, 0u);
-                continue;
-            }
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(W, voff[j], rows[i] * rowbytes, 2);
-            wv[j][i] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-}
-
-// Q8 rows (WQ8): 16-B chunks of 16 int8, so a lane holds 16 x values per chunk, and the
-// group's RB row scales are fetched with its weights (applied before the epilogue:
-// y = scale * sum + bias, voxtral_kernels.c:316).
-#ifdef VOX_GEMV_STAMPS
-// diagnostic build only (tools/kbench_stamps): per block s_memrealtime at entry, when the
-// first group's weights have been consumed, and at exit
-__device__ unsigned long long* g_gemv_stamps;
-#define GEMV_STAMP(k) \
-    do { if (g_gemv_stamps && tid == 0) g_gemv_stamps[(size_t)blockIdx.x * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define GEMV_STAMP(k) do {} while (0)
-#endif
-
-// wpack13 rows (WF_P13, vox_wpack.h): 12-B chunks of 8 weights as IEEE halves plus one side
-// dword record per (group, thread), fetched with the group's weights by one load; x is
-// scaled by 2^D once per block after the prologue.  ldexpf is exact for 0 and for |x| in
-// [2^(-126-D), 2^(127-D)); |D| <= 40 (VOX_WPACK_MAX_D) puts those bounds at 2^-86 and 2^87
-// or beyond, past anything an RMSNorm output, an attention output or a SwiGLU product of
-// this model reaches.  Every output is then bit-identical to the bf16 instance's.
-template <int SW>
-__device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int voff, int soff, uint32_t (&sd)[SW]) {
-    if constexpr (SW == 1) {
-        sd[0] = __builtin_amdgcn_raw_buffer_load_b32(S, voff, soff, 2);
-    } else if constexpr (SW == 2) {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(S, voff, soff, 2);
-        sd[0] = v.x; sd[1] = v.y;
-    } else if constexpr (SW == 3) {
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(S, voff, soff, 2);
-        sd[0] = v.x; sd[1] = v.y; sd[2] = v.z;
-    } else {
-        static_assert(SW % 4 != 3, "side record size");
-#pragma unroll
-        for (int o = 0; o + 4 <= SW; o += 4) {
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(S, voff + o * 4, soff, 2);
-            sd[o] = v.x; sd[o + 1] = v.y; sd[o + 2] = v.z; sd[o + 3] = v.w;
-        }
-        if constexpr (SW % 4 == 1) sd[SW - 1] = __builtin_amdgcn_raw_buffer_load_b32(S, voff + (SW - 1) * 4, soff, 2);
-        if constexpr (SW % 4 == 2) {
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(S, voff + (SW - 2) * 4, soff, 2);
-            sd[SW - 2] = v.x; sd[SW - 1] = v.y;
-        }
-    }
-}
-
-// wmx4 plane (WF_MX4, vox_wmx4.h): one record of RW = RB + ceil(RB / 4) dwords per (group,
-// chunk): the RB rows' nibble dwords of that chunk and their blocks' e8m0 scale bytes, so the
-// thread that owns a chunk fetches a group's weights with one record load per K round (the
-// wave's 64 records are contiguous).  dot8m4 rebuilds each weight as the exact f32 of the bf16
-// weight and runs dot8's FMAs: every output is bit-identical to the bf16 instance's.
-template <int RW, int KQ>
-__device__ __forceinline__ void gemv_load_mx4(__amdgpu_buffer_rsrc_t W, int soff, const int (&voff)[KQ],
-                                              uint32_t (&mr)[KQ][RW]) {
-#pragma unroll
-    for (int j = 0; j < KQ; j++) gemv_load_side<RW>(W, voff[j], soff, mr[j]);
-}
-
-template <int PRO, int EPI, int RB, int KQ, int WF>
-__global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
-    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13, WM = WF == WF_MX4;
-    constexpr int XPC = WQ8 ? 4 : 2;  // float4 of x per 16-B chunk
-    constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
-    constexpr int RW = RB + (RB + 3) / 4;           // wmx4 record dwords per (group, chunk)
-    __shared__ float red[2][4][RB];
-    __shared__ float sred[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, KC = WQ8 ? K >> 4 : K >> 3;
-    const int ngroups = a.rows / RB;
-    // Groups: block b takes b, b + G, b + 2G, ... (static; run-time claims measured 3-4x
-    // slower)
-    const int G = gridDim.x;
-    int g = blockIdx.x;
-    int rows[RB];
-    uint4 wv[WM ? 1 : KQ][RB];
-    uint32_t mr[WM ? KQ : 1][RW];
-    float wsc[RB];
-    GEMV_STAMP(0);
-    bool first_group = true;
-    // wmx4: "rowbytes" is a group's bytes (KC records), the plane ngroups of them
-    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * (WQ8 ? 1 : 2);
-    void* const wbase = const_cast<void*>(WM ? a.wm_plane : WP ? a.wp_main : a.W);
-    const __amdgpu_buffer_rsrc_t wrs =
-        __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
-    void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
-    uint32_t sd[SW];
-    // chunk offsets per K round; chunks past K (K not a multiple of 16 B * 256) re-load
-    // chunk 0 and meet x = 0: every load is unconditional, so hipcc issues them all before
-    // the first wait (a guarded load makes it wait vmcnt(0) at each branch join)
-    int voff[KQ];
-#pragma unroll
-    for (int j = 0; j < KQ; j++) {
-        const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
-    }
-    // first group's weights are independent of x: issue them before the prologue
-    gemv_rows<EPI, RB>(g, rows);
-    if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);  // first: every chunk needs it
-    if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
-    else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
-    if ((EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT) && WQ8 && wave == 0) {
-#pragma unroll
-        for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
-    }
-
-    float4 xr[KQ][XPC];
-    // bf16: the RMSNorm weights (and ada) go out with x -- independent of the row sum, so the
-    // prologue waits for one L2 round trip instead of two (C2 +0.7 %, W1|W3 21.0 -> 20.8 us);
-    // Q8 (16 x values per chunk) keeps them after the sum: the early registers cost it 0.5 %
-    // (profiles/r5_gemv_prologue_ab.txt)
-    constexpr bool EARLY = PRO != PRO_NONE && !WQ8;
-    constexpr int NXP = EARLY ? XPC : 1;
-    float4 nwr[KQ][NXP], adr[KQ][NXP];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < KQ; j++) {
-        const int c = (j * 4 + wave) * 64 + lane;
-        const float4* xp = reinterpret_cast<const float4*>(a.x) + XPC * (c < KC ? c : 0);
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int h = 0; h < XPC; h++) {
-            const float4 xv = xp[h];
-            xr[j][h] = c < KC ? xv : z;
-        }
-        if (EARLY) {
-            const int cc = c < KC ? c : 0;
-            const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * cc;
-            const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * cc;
-#pragma unroll
-            for (int h = 0; h < NXP; h++) {
-                nwr[j][h] = wp[h];
-                if (PRO == PRO_NORM_ADA) adr[j][h] = ap[h];
-            }
-        }
-        if (PRO != PRO_NONE) {
-#pragma unroll
-            for (int h = 0; h < XPC; h++) {
-                const float4 v = xr[j][h];
-                ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
-            }
-        }
-    }
-    if (PRO != PRO_NONE) {
-        // RMSNorm prologue (voxtral_kernels.c:475-492; ada: voxtral_decoder.c:742-745)
-        ss = wave_sum(ss);
-        if (lane == 0) sred[wave] = ss;
-        __syncthreads();
-        const float tot = sred[0] + sred[1] + sred[2] + sred[3];
-        const float inv = 1.0f / sqrtf(tot / (float)K + a.eps);
-#pragma unroll
-        for (int j = 0; j < KQ; j++) {
-            const int c0 = (j * 4 + wave) * 64 + lane;
-            const int c = c0 < KC ? c0 : 0;
-            const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * c;
-            const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * c;
-#pragma unroll
-            for (int h = 0; h < XPC; h++) {
-                float4 v = xr[j][h];
-                const float4 nw = EARLY ? nwr[j][h % NXP] : wp[h];
-                v.x = v.x * inv * nw.x; v.y = v.y * inv * nw.y;
-                v.z = v.z * inv * nw.z; v.w = v.w * inv * nw.w;
-                if (PRO == PRO_NORM_ADA) {
-                    const float4 ad = EARLY ? adr[j][h % NXP] : ap[h];
-                    v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
-                    v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
-                }
-                xr[j][h] = v;
-            }
-        }
-    }
-
-    if (WP) {
-#pragma unroll
-        for (int j = 0; j < KQ; j++)
-#pragma unroll
-            for (int h = 0; h < XPC; h++) {
-                float4 v = xr[j][h];
-                v.x = ldexpf(v.x, a.wp_d); v.y = ldexpf(v.y, a.wp_d);
-                v.z = ldexpf(v.z, a.wp_d); v.w = ldexpf(v.w, a.wp_d);
-                xr[j][h] = v;
-            }
-    }
-
-    constexpr bool QKVE = (EPI == EPI_QKV || EPI == EPI_QKV_BIAS);
-    int lp = 0;
-    if (QKVE) lp = a.state ? a.state[0] : a.pos;
-    float best = -INFINITY;
-    int besti = 0x7fffffff;
-    // EPI_LOGITS_ALT: online softmax partial (max, sum exp) and the 4 largest text logits
-    float am = -INFINITY, as = 0.f, tv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int ti[4] = {-1, -1, -1, -1};
-    // Epilogue ownership: lane l of wave 0 finishes row l (STORE / RESID) or row pair
-    // (2l, 2l+1) (QKV rope pairs, SWIGLU w1/w3 pairs), so the epilogue's reads (residual,
-    // bias, rope, Q8 scales) go out in parallel at the top of the iteration instead of one
-    // dependent round trip per row after the reduction.  The LM head keeps one lane (its
-    // running argmax is sequential over ascending rows).
-    constexpr bool LOGIT = (EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT);
-    constexpr bool PAIRED = (QKVE || EPI == EPI_SWIGLU);
-    constexpr int NL = LOGIT ? 1 : (PAIRED ? RB / 2 : RB);
-    const bool owner = wave == 0 && lane < NL;
-    const int i0 = PAIRED ? 2 * lane : lane;
-    int buf = 0;
-    for (;;) {
-        const int gcur = g;
-        // epilogue inputs of this group (independent of the dot products)
-        int er0 = 0, er1 = 0;
-        float ein0 = 0.f, ein1 = 0.f, esc0 = 1.f, esc1 = 1.f, eb0 = 0.f, eb1 = 0.f;
-        if (!LOGIT && owner) {
-            int rr[RB];
-            gemv_rows<EPI, RB>(gcur, rr);
-#pragma unroll
-            for (int i = 0; i < RB; i++) {
-                if (i == i0) er0 = rr[i];
-                if (i == i0 + 1) er1 = rr[i];
-            }
-            if (WQ8) {
-                esc0 = a.wscale[er0];
-                if (PAIRED) esc1 = a.wscale[er1];
-            }
-            if (EPI == EPI_RESID) ein0 = a.y[er0] + (a.bias ? a.bias[er0] : 0.f);
-            if (EPI == EPI_STORE) ein0 = a.bias ? a.bias[er0] : 0.f;
-            if (EPI == EPI_QKV_BIAS) {
-                eb0 = a.bias[er0];
-                eb1 = a.bias[er1];
-            }
-            if (QKVE && er0 < a.qd + a.kvd) {
-                const int col = er0 < a.qd ? er0 : er0 - a.qd;
-                const float* rp = a.rope + (size_t)lp * a.hd + ((col % a.hd) & ~1);
-                ein0 = rp[0];
-                ein1 = rp[1];
-            }
-        }
-        float acc[RB];
-#pragma unroll
-        for (int i = 0; i < RB; i++) acc[i] = 0.f;
-#pragma unroll
-        for (int j = 0; j < KQ; j++)
-#pragma unroll
-            for (int i = 0; i < RB; i++) {
-                if constexpr (WM) acc[i] = dot8m4(mr[j][i], (mr[j][RB + (i >> 2)] >> (8 * (i & 3))) & 0xffu, xr[j][0], xr[j][1], acc[i]);
-                else if (WQ8) acc[i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[j]), acc[i]);
-                else if (WP) acc[i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[j][0], xr[j][1], acc[i]);
-                else acc[i] = dot8(wv[j][i], xr[j][0], xr[j][XPC - 1], acc[i]);
-            }
-        if (first_group) {
-            GEMV_STAMP(1);
-            first_group = false;
-        }
-        int rcur[RB];
-        float scur[RB];
-        if (LOGIT) {
-#pragma unroll
-            for (int i = 0; i < RB; i++) {
-                rcur[i] = rows[i];
-                scur[i] = WQ8 ? wsc[i] : 1.0f;
-            }
-        }
-        g += G;
-        // The next group's loads go out before this group's reduction, unconditionally: a
-        // load under `if (more)` keeps the old weight registers alive across the branch and
-        // doubles the weight register set (fewer resident blocks).  Past the last group they
-        // go through a zero-length descriptor: the range check returns zeros, no traffic.
-        {
-            const bool more = g < ngroups;
-            gemv_rows<EPI, RB>(more ? g : 0, rows);
-            if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
-            if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
-            else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
-            if (LOGIT && WQ8 && wave == 0) {
-#pragma unroll
-                for (int i = 0; i < RB; i++) wsc[i] = a.wscale[rows[i]];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < RB; i++) acc[i] = wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < RB; i++) red[buf][wave][i] = acc[i];
-        }
-        __syncthreads();
-        if (!LOGIT && owner) {
-            float v0 = ((red[buf][0][i0] + red[buf][1][i0]) + red[buf][2][i0]) + red[buf][3][i0];
-            float v1 = 0.f;
-            if (PAIRED) v1 = ((red[buf][0][i0 + 1] + red[buf][1][i0 + 1]) + red[buf][2][i0 + 1]) + red[buf][3][i0 + 1];
-            if (WQ8) {
-                v0 *= esc0;
-                v1 *= esc1;
-            }
-            if (EPI == EPI_QKV_BIAS) {
-                v0 += eb0;
-                v1 += eb1;
-            }
-            if (EPI == EPI_STORE || EPI == EPI_RESID) {
-                a.y[er0] = ein0 + v0;  // RESID: residual + bias were read at the top
-            } else if (EPI == EPI_SWIGLU) {
-                a.y[gcur * (RB / 2) + lane] = silu(v0) * v1;
-            } else if (QKVE) {
-                if (er0 < a.qd + a.kvd) {
-                    const float o0 = v0 * ein0 - v1 * ein1, o1 = v0 * ein1 + v1 * ein0;
-                    if (er0 < a.qd) {
-                        a.y[er0] = o0;
-                        a.y[er1] = o1;
-                    } else {
-                        // (o0 / o1 are f32 values here: shared with the q store above and passed through
-                        // the runtime kvt switch, no k_gemv instance folds them into v_fma_mixlo_f16 -- see
-                        // kv_f32; this kernel is the decoder's too, so it carries no barrier of its own,
-                        // and tests/test_gpu_enc_kv16.py holds the encoder's one-row path to the exact rule)
-                        kv_st2_rt(a.Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kvt);
-                    }
-                } else {
-                    kv_st2_rt(a.Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kvt);
-                }
-            }
-        }
-        if (LOGIT && wave == 0 && lane == 0) {
-            float v[RB];
-#pragma unroll
-            for (int i = 0; i < RB; i++) {
-                v[i] = ((red[buf][0][i] + red[buf][1][i]) + red[buf][2][i]) + red[buf][3][i];
-                if (WQ8) v[i] *= scur[i];
-            }
-#pragma unroll
-            for (int i = 0; i < RB; i++) {
-                a.y[rcur[i]] = v[i];
-                // first max wins (voxtral_decoder.c:771-779): rows ascend within a block
-                if (v[i] > best) { best = v[i]; besti = rcur[i]; }
-                if (EPI == EPI_LOGITS_ALT) alt_row(v[i], rcur[i], am, as, tv, ti);
-            }
-        }
-        buf ^= 1;
-        if (g >= ngroups) break;
-    }
-    GEMV_STAMP(2);
-    if ((EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT) && wave == 0 && lane == 0) {
-        a.part_val[blockIdx.x] = best;
-        a.part_idx[blockIdx.x] = besti;
-        if (EPI == EPI_LOGITS_ALT) {
-            float* pa = a.part_alt + (size_t)blockIdx.x * ALT_PART;
-            pa[0] = am;
-            pa[1] = as;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                pa[2 + k] = tv[k];
-                pa[6 + k] = __int_as_float(ti[k]);
-            }
-        }
-    }
-}
-
-// ============================================================================
-// R-row weight-streaming GEMV (R = 1, 2, 4, 8: the slot buckets of a small batched decode
-// step): y[r] = W x[r].  k_gemv's block, row groups, grid, chunk mapping, non-temporal buffer
-// loads, early next-group loads and zero-length descriptor, so the P13 instance streams the
-// model's own wpack13 planes and the MX4 instance its wmx4 GEMV plane (one record load per K
-// round, k_gemv<WF_MX4>'s fetch; each (round, row) nibble dword is decoded to eight f32 once
-// and feeds the R chains); every weight register feeds R FMA chains.  The x rows of a pass
-// live in registers (R * KQ * 8 floats per thread).  More than 160 floats (R * KQ > 20: W2 of
-// the full model at 8 rows would take 320) do not fit beside the weights: such an instance
-// runs two passes of R / 2 rows over the block's groups and reads its weights twice
-// (DESIGN.md 18.3).  The Q8 instance (WF_Q8) streams int8 rows as k_gemv<WF_Q8>
-// does: 16 weights per chunk, so R * KQ * 16 floats of x, the same 160-float bound per pass
-// (up to four passes), dot16q per (chunk, row) and the row's f32 scale times the reduced sum
-// in the epilogue owner, before the epilogue.
-//
-// Each row's arithmetic is k_gemv's, in k_gemv's order, in registers of its own: chunks in j
-// order, the wave sum, the four waves added ((0 + 1) + 2) + 3, and the RMSNorm prologue per
-// row.  So the bits of y[r] depend on W and x[r] alone -- not on R, on r or on the other
-// rows -- and equal k_gemv's for every shape.
-//
-// Epilogues per row r: STORE / RESID on row r of y (stride ldy), SWIGLU into row r of the
-// hidden buffer, QKV with RoPE at slots[r].pos, q into row r of y and K/V into the slot's own
-// rings (a slot that is not live appends nothing; its q row is never read).
-// ============================================================================
-// Q8 instance: rows per pass.  A pass holds RP * KQ * 16 floats of x per lane, at most the 160
-// the bf16 instances hold; wider instances run R / RP passes
-constexpr int gemvr_rp_q8(int R, int KQ) {
-    int rp = R;
-    while (rp > 1 && rp * KQ * 16 > 160) rp /= 2;
-    return rp;
-}
-
-template <int PRO, int EPI, int RB, int KQ, int WF, int R>
-__global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
-    constexpr bool WQ8 = WF == WF_Q8, WP = WF == WF_P13, WM = WF == WF_MX4;
-    constexpr int XPC = WQ8 ? 4 : 2;  // float4 of x per 16-B chunk
-    constexpr int SW = WP ? (KQ * RB + 3) / 4 : 1;  // side dwords per (group, thread)
-    constexpr int RW = RB + (RB + 3) / 4;           // wmx4 record dwords per (group, chunk)
-    constexpr int RP = WQ8 ? gemvr_rp_q8(R, KQ) : R * KQ > 20 ? R / 2 : R;  // rows per pass
-    constexpr bool QKVE = EPI == EPI_QKV;
-    constexpr bool PAIRED = QKVE || EPI == EPI_SWIGLU;
-    constexpr int NL = PAIRED ? RB / 2 : RB;        // epilogue lanes per row
-    static_assert(RP * NL <= 64, "the epilogue owners are lanes of wave 0");
-    __shared__ float red[2][4][RP][RB];
-    __shared__ float sred[4][RP];
-    const GemvArgs& a = ra.g;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, KC = WQ8 ? K >> 4 : K >> 3;
-    const int ngroups = a.rows / RB;
-    const int G = gridDim.x;
-    // wmx4: "rowbytes" is a group's bytes (KC records), the plane ngroups of them (k_gemv)
-    const int rowbytes = WM ? KC * (RW * 4) : WP ? KC * 12 : K * (WQ8 ? 1 : 2);
-    void* const wbase = const_cast<void*>(WM ? a.wm_plane : WP ? a.wp_main : a.W);
-    const __amdgpu_buffer_rsrc_t wrs =
-        __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
-    void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
-    // chunk offsets per K round, as k_gemv: chunks past K re-load chunk 0 and meet x = 0
-    int voff[KQ];
-#pragma unroll
-    for (int j = 0; j < KQ; j++) {
-        const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
-    }
-    // epilogue ownership: thread orow * NL + ol of wave 0 finishes row (or row pair) ol of the
-    // group for input row orow of the pass
-    const bool owner = tid < RP * NL;
-    const int orow = owner ? tid / NL : 0, ol = tid % NL;
-    const int i0 = PAIRED ? 2 * ol : ol;
-    int buf = 0;
-#pragma unroll 1
-    for (int r0 = 0; r0 < R; r0 += RP) {
-        int g = blockIdx.x;
-        int rows[RB];
-        uint4 wv[WM ? 1 : KQ][RB];
-        uint32_t mr[WM ? KQ : 1][RW];
-        uint32_t sd[SW];
-        // first group's weights are independent of x: issue them before the prologue
-        gemv_rows<EPI, RB>(g, rows);
-        if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);
-        if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
-        else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
-
-        float4 xr[RP][KQ][XPC];
-        // Q8 (16 x values per chunk) fetches the norm and ada rows after the row sums, as
-        // k_gemv<WF_Q8> does: they are not held across the sum's barrier
-        constexpr bool EARLY = !WQ8;
-        float4 nwr[KQ][EARLY ? XPC : 1], adr[KQ][EARLY ? XPC : 1];
-        float ss[RP];
-#pragma unroll
-        for (int r = 0; r < RP; r++) ss[r] = 0.f;
-#pragma unroll
-        for (int j = 0; j < KQ; j++) {
-            const int c = (j * 4 + wave) * 64 + lane;
-            const int cc = c < KC ? c : 0;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int r = 0; r < RP; r++) {
-                const float4* xp = reinterpret_cast<const float4*>(a.x + (size_t)(r0 + r) * ra.ldx) + XPC * cc;
-#pragma unroll
-                for (int h = 0; h < XPC; h++) {
-                    const float4 xv = xp[h];
-                    xr[r][j][h] = c < KC ? xv : z;
-                }
-            }
-            if (PRO != PRO_NONE) {
-                // the norm weights (and the ada row) are shared by the rows
-                const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * cc;
-                const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * cc;
-                if constexpr (EARLY) {
-#pragma unroll
-                    for (int h = 0; h < XPC; h++) {
-                        nwr[j][h] = wp[h];
-                        if (PRO == PRO_NORM_ADA) adr[j][h] = ap[h];
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < RP; r++)
-#pragma unroll
-                    for (int h = 0; h < XPC; h++) {
-                        const float4 v = xr[r][j][h];
-                        ss[r] = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss[r]))));
-                    }
-            }
-        }
-        if (PRO != PRO_NONE) {
-            // RMSNorm prologue, per row (k_gemv's arithmetic)
-#pragma unroll
-            for (int r = 0; r < RP; r++) {
-                ss[r] = wave_sum(ss[r]);
-                if (lane == 0) sred[wave][r] = ss[r];
-            }
-            __syncthreads();
-            if constexpr (WQ8) {
-                // one fetch of each norm / ada float4 for the RP rows; per element the
-                // arithmetic below is the other branch's
-                float inv[RP];
-#pragma unroll
-                for (int r = 0; r < RP; r++) {
-                    const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
-                    inv[r] = 1.0f / sqrtf(tot / (float)K + a.eps);
-                }
-#pragma unroll
-                for (int j = 0; j < KQ; j++) {
-                    const int c0 = (j * 4 + wave) * 64 + lane;
-                    const int cc = c0 < KC ? c0 : 0;
-                    const float4* wp = reinterpret_cast<const float4*>(a.norm_w) + XPC * cc;
-                    const float4* ap = reinterpret_cast<const float4*>(PRO == PRO_NORM_ADA ? a.ada : a.norm_w) + XPC * cc;
-#pragma unroll
-                    for (int h = 0; h < XPC; h++) {
-                        const float4 nw = wp[h];
-                        float4 ad = nw;
-                        if (PRO == PRO_NORM_ADA) ad = ap[h];
-#pragma unroll
-                        for (int r = 0; r < RP; r++) {
-                            float4 v = xr[r][j][h];
-                            v.x = v.x * inv[r] * nw.x; v.y = v.y * inv[r] * nw.y;
-                            v.z = v.z * inv[r] * nw.z; v.w = v.w * inv[r] * nw.w;
-                            if (PRO == PRO_NORM_ADA) {
-                                v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
-                                v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
-                            }
-                            xr[r][j][h] = v;
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < RP; r++) {
-                    const float tot = sred[0][r] + sred[1][r] + sred[2][r] + sred[3][r];
-                    const float inv = 1.0f / sqrtf(tot / (float)K + a.eps);
-#pragma unroll
-                    for (int j = 0; j < KQ; j++)
-#pragma unroll
-                        for (int h = 0; h < 2; h++) {
-                            float4 v = xr[r][j][h];
-                            const float4 nw = nwr[j][h];
-                            v.x = v.x * inv * nw.x; v.y = v.y * inv * nw.y;
-                            v.z = v.z * inv * nw.z; v.w = v.w * inv * nw.w;
-                            if (PRO == PRO_NORM_ADA) {
-                                const float4 ad = adr[j][h];
-                                v.x *= (1.0f + ad.x); v.y *= (1.0f + ad.y);
-                                v.z *= (1.0f + ad.z); v.w *= (1.0f + ad.w);
-                            }
-                            xr[r][j][h] = v;
-                        }
-                }
-            }
-        }
-        if (WP) {
-#pragma unroll
-            for (int r = 0; r < RP; r++)
-#pragma unroll
-                for (int j = 0; j < KQ; j++)
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        float4 v = xr[r][j][h];
-                        v.x = ldexpf(v.x, a.wp_d); v.y = ldexpf(v.y, a.wp_d);
-                        v.z = ldexpf(v.z, a.wp_d); v.w = ldexpf(v.w, a.wp_d);
-                        xr[r][j][h] = v;
-                    }
-        }
-
-        // the owner's row of this pass: output row, and for QKV the slot's position and rings
-        float* const yrow = a.y + (size_t)(r0 + orow) * ra.ldy;
-        int lp = 0, live = 0;
-        float *Kc = nullptr, *Vc = nullptr;
-        if (QKVE && owner) {
-            const BatchSlot* sl = ra.slots + (r0 + orow);
-            live = sl->live;
-            lp = live ? sl->pos : 0;
-            Kc = reinterpret_cast<float*>(sl->Kc + ra.ring_off);
-            Vc = reinterpret_cast<float*>(sl->Vc + ra.ring_off);
-        }
-        for (;;) {
-            const int gcur = g;
-            // epilogue inputs of this group (independent of the dot products)
-            int er0 = 0, er1 = 0;
-            float ein0 = 0.f, ein1 = 0.f, esc0 = 1.f, esc1 = 1.f;
-            if (owner) {
-                int rr[RB];
-                gemv_rows<EPI, RB>(gcur, rr);
-#pragma unroll
-                for (int i = 0; i < RB; i++) {
-                    if (i == i0) er0 = rr[i];
-                    if (i == i0 + 1) er1 = rr[i];
-                }
-                if (WQ8) {
-                    esc0 = a.wscale[er0];
-                    if (PAIRED) esc1 = a.wscale[er1];
-                }
-                if (EPI == EPI_RESID) ein0 = yrow[er0];
-                if (QKVE && er0 < a.qd + a.kvd) {
-                    const int col = er0 < a.qd ? er0 : er0 - a.qd;
-                    const float* rp = a.rope + (size_t)lp * a.hd + ((col % a.hd) & ~1);
-                    ein0 = rp[0];
-                    ein1 = rp[1];
-                }
-            }
-            float acc[RP][RB];
-#pragma unroll
-            for (int r = 0; r < RP; r++)
-#pragma unroll
-                for (int i = 0; i < RB; i++) acc[r][i] = 0.f;
-#pragma unroll
-            for (int j = 0; j < KQ; j++)
-#pragma unroll
-                for (int i = 0; i < RB; i++) {
-                    if constexpr (WM) {
-                        // one decode per (round, row) of the group, then dot8's FMAs per input row
-                        const f32x8 wd = dec8m4(mr[j][i], (mr[j][RB + (i >> 2)] >> (8 * (i & 3))) & 0xffu);
-#pragma unroll
-                        for (int r = 0; r < RP; r++) acc[r][i] = dot8f(wd, xr[r][j][0], xr[r][j][1], acc[r][i]);
-                    } else if constexpr (WQ8) {
-#pragma unroll
-                        for (int r = 0; r < RP; r++)
-                            acc[r][i] = dot16q(wv[j][i], reinterpret_cast<const float4(&)[4]>(xr[r][j]), acc[r][i]);
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < RP; r++) {
-                            if (WP) acc[r][i] = dot8h(wv[j][i], sd[(j * RB + i) >> 2], (j * RB + i) & 3, xr[r][j][0], xr[r][j][1], acc[r][i]);
-                            else acc[r][i] = dot8(wv[j][i], xr[r][j][0], xr[r][j][1], acc[r][i]);
-                        }
-                    }
-                }
-            g += G;
-            // the next group's loads before this group's reduction, unconditionally; past the
-            // last group through the zero-length descriptor (k_gemv)
-            {
-                const bool more = g < ngroups;
-                gemv_rows<EPI, RB>(more ? g : 0, rows);
-                if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
-                if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
-                else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
-            }
-#pragma unroll
-            for (int r = 0; r < RP; r++)
-#pragma unroll
-                for (int i = 0; i < RB; i++) acc[r][i] = wave_sum(acc[r][i]);
-            if (lane == 0) {
-#pragma unroll
-                for (int r = 0; r < RP; r++)
-#pragma unroll
-                    for (int i = 0; i < RB; i++) red[buf][wave][r][i] = acc[r][i];
-            }
-            __syncthreads();
-            if (owner) {
-                float v0 = ((red[buf][0][orow][i0] + red[buf][1][orow][i0]) + red[buf][2][orow][i0]) + red[buf][3][orow][i0];
-                float v1 = 0.f;
-                if (PAIRED)
-                    v1 = ((red[buf][0][orow][i0 + 1] + red[buf][1][orow][i0 + 1]) + red[buf][2][orow][i0 + 1]) +
-                         red[buf][3][orow][i0 + 1];
-                if (WQ8) {  // y = scale * sum before anything else (k_gemv)
-                    v0 *= esc0;
-                    v1 *= esc1;
-                }
-                if (EPI == EPI_STORE || EPI == EPI_RESID) {
-                    yrow[er0] = ein0 + v0;
-                } else if (EPI == EPI_SWIGLU) {
-                    yrow[gcur * (RB / 2) + ol] = silu(v0) * v1;
-                } else if (QKVE) {
-                    if (er0 < a.qd + a.kvd) {
-                        const float o0 = v0 * ein0 - v1 * ein1, o1 = v0 * ein1 + v1 * ein0;
-                        if (er0 < a.qd) {
-                            yrow[er0] = o0;
-                            yrow[er1] = o1;
-                        } else if (live) {
-                            kv_st2_rt(Kc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd), o0, o1, a.kvt);
-                        }
-                    } else if (live) {
-                        kv_st2_rt(Vc, (size_t)(lp % a.cap) * a.kvd + (er0 - a.qd - a.kvd), v0, v1, a.kvt);
-                    }
-                }
-            }
-            buf ^= 1;
-            if (g >= ngroups) break;
-        }
     }
 }
 
@@ -3740,6 +2908,22 @@ __global__ void k_mel_reflect(float* __restrict__ buf, long long n, long long re
 #define LAUNCH_CHECK() \
     do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
 
+// The ring element of a launch.  f is called with the KvRing tag of (kvt, head_dim): the element
+// type, and enc = 1 for the encoder's half rings (the instances that store kv_f32 values); a pair
+// without a ring (kv_ring_ok, vox_hip_internal.h) has no such instance and is refused.
+template <class T, int ENC = 0>
+struct KvRing {
+    using type = T;
+    static constexpr int enc = ENC;
+};
+template <class F>
+static hipError_t kv_ring(int kvt, int hd, F&& f) {
+    if (!kv_ring_ok(kvt, hd)) return hipErrorInvalidValue;
+    if (kvt == KV_FP8) return f(KvRing<kv8_t>{});
+    if (kvt == KV_F16) return hd == 64 ? f(KvRing<kvh_t, 1>{}) : f(KvRing<kvh_t>{});
+    return f(KvRing<float>{});
+}
+
 hipError_t launch_rmsnorm_rows(const float* x, int ldx, float* y, int ldy, const float* w,
                                const float* ada, int M, int D, float eps, hipStream_t st) {
     if (M <= 0) return hipSuccess;
@@ -3890,37 +3074,28 @@ hipError_t launch_kv8_convert(const float* x, int groups, uint8_t* codes, float*
 hipError_t launch_rope_kv(const float* qkv, int M, int qd, int kvd, int hd, const float* rope,
                           int pos0, float* q, float* Kc, float* Vc, int cap, hipStream_t st, int kvt) {
     if (M <= 0) return hipSuccess;
-    if (kvd % 2 || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
-    if (kvt == KV_FP8)
-        hipLaunchKernelGGL(k_rope_kv<kv8_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
-    else if (kvt == KV_F16 && hd == 64)  // the encoder's rings
-        hipLaunchKernelGGL((k_rope_kv<kvh_t, 1>), dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
-    else if (kvt == KV_F16)
-        hipLaunchKernelGGL(k_rope_kv<kvh_t>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
-    else
-        hipLaunchKernelGGL(k_rope_kv<float>, dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
-    LAUNCH_CHECK();
-    return hipSuccess;
+    if (kvd % 2) return hipErrorInvalidValue;
+    // kv_ring refuses a 16-bit or one-byte ring at a head_dim it does not exist for (kv_ring_ok).
+    // Until the launchers shared kv_ring this one launched for any head_dim; the attention over
+    // such a ring always refused it, and check_config admits head_dim 64 and 128 only.
+    return kv_ring(kvt, hd, [&](auto ring) {
+        using R = decltype(ring);
+        hipLaunchKernelGGL((k_rope_kv<typename R::type, R::enc>), dim3(M), dim3(256), 0, st, qkv, M, qd, kvd, hd, rope,
+                           pos0, q, Kc, Vc, cap);
+        return hipGetLastError();
+    });
 }
-
-VOX_KB_KNOB(g_attn_blocks, 0);  // tools/kbench knob: target grid size of the key-range split (0 = 512)
 
 hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd, const float* rope_table,
                                const EncRows& er, float* q, int cap, hipStream_t st, int kvt) {
     if (N <= 0) return hipSuccess;
-    if (er.B < 1 || er.B > VOX_MAX_BATCH || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
-    // narrow rings: the decoder's at head_dim 128; IEEE half also at 64 (the encoder's opt-in rings)
-    if (kvt != KV_F32 && ((hd != 128 && !(kvt == KV_F16 && hd == 64)) || kvd % 2)) return hipErrorInvalidValue;
-    if (kvt == KV_FP8)
-        hipLaunchKernelGGL(k_rope_kv_rows<kv8_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
-    else if (kvt == KV_F16 && hd == 64)  // the encoder's rings
-        hipLaunchKernelGGL((k_rope_kv_rows<kvh_t, 1>), dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
-    else if (kvt == KV_F16)
-        hipLaunchKernelGGL(k_rope_kv_rows<kvh_t>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
-    else
-        hipLaunchKernelGGL(k_rope_kv_rows<float>, dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd, rope_table, er, q, cap);
-    LAUNCH_CHECK();
-    return hipSuccess;
+    if (er.B < 1 || er.B > VOX_MAX_BATCH || (kvt != KV_F32 && kvd % 2)) return hipErrorInvalidValue;
+    return kv_ring(kvt, hd, [&](auto ring) {
+        using R = decltype(ring);
+        hipLaunchKernelGGL((k_rope_kv_rows<typename R::type, R::enc>), dim3(N), dim3(256), 0, st, qkv, qd, kvd, hd,
+                           rope_table, er, q, cap);
+        return hipGetLastError();
+    });
 }
 
 // VOX_HIP_ATT_PLANES=0: the attention writes f32 rows and k_split_fplanes makes the wo planes
@@ -3934,60 +3109,81 @@ static bool att_planes() {
     return g_att_planes == 1;
 }
 
+// tools/kbench knob: target grid size of launch_attn_rows_mf's key-range split (0 = 256; the comment
+// here used to say 512, the code 256)
+VOX_KB_KNOB(g_attn_blocks, 0);
+
+// Key-range splits of a k_attn_mf launch whose nblk (head, query block)s cannot fill the chip: at
+// least 64 keys per split, about `target` = 256 blocks in all (a 25-row streaming chunk over ~775
+// keys: 4), as many as the workspace holds partials of `rows` query rows for
+// (k_attn_mf, 25 rows x 775 keys: 256 blocks 10.4 us, 512 11.8, 128 13.9, 1024 12.0)
+static int attn_mf_splits(int nblk, int keys, int rows, int H, int hd, const float* ws, size_t ws_elems,
+                          int target = 256) {
+    if (!ws || nblk >= 256) return 1;
+    int ns = std::min((keys + 63) / 64, std::max(1, target / nblk));
+    while (ns > 1 && (size_t)H * rows * ns * (hd + 2) > ws_elems) ns--;
+    return ns;
+}
+
+// The k_attn_mf instance of (hd, kvt) over `grid`, then the combine of ns > 1 key ranges.  xs: the
+// output rows also as the wo input's planes: by the attention itself where its instance writes
+// them (f32 rings and the encoder's 16-bit ring), by the combine, or by k_split_fplanes after the
+// kernel (the decoder's 16-bit and one-byte rings; VOX_HIP_ATT_PLANES=0)
+template <int BAT>
+static hipError_t attn_mf_launch(int hd, int kvt, dim3 grid, const float* Q, int ldq, const float* Kc, const float* Vc,
+                                 int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0, int k_first, int window,
+                                 float scale, int ns, float* ws, const EncRows& er, uint16_t* xs, hipStream_t st) {
+    if (hd != 64 && hd != 128) return hipErrorInvalidValue;
+    const bool writes_planes = kvt == KV_F32 || (kvt == KV_F16 && hd == 64);
+    uint16_t* kxs = ns == 1 && writes_planes && att_planes() ? xs : nullptr;
+    const hipError_t e = kv_ring(kvt, hd, [&](auto ring) {
+        using R = decltype(ring);
+        using KT = typename R::type;
+#define ATTN_MF(HD)                                                                                                   \
+    hipLaunchKernelGGL((k_attn_mf<HD, KT, BAT>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0, \
+                       k_first, window, scale, ns, ws, er, kxs)
+        // head_dim 64: f32 rings and the encoder's; 128: every ring but the encoder's
+        if constexpr (std::is_same_v<KT, float> || R::enc) {
+            if (hd == 64) {
+                ATTN_MF(64);
+                return hipGetLastError();
+            }
+        }
+        if constexpr (!R::enc) ATTN_MF(128);
+#undef ATTN_MF
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    if (ns > 1) {
+        // with xs the combine writes the wo planes itself
+        if (hd == 64)
+            hipLaunchKernelGGL(k_attn_tiled_combine<64>, dim3(H, M), dim3(64), 0, st, ws, ns, M, O, ldo, xs);
+        else
+            hipLaunchKernelGGL(k_attn_tiled_combine<128>, dim3(H, M), dim3(128), 0, st, ws, ns, M, O, ldo, xs);
+        LAUNCH_CHECK();
+    } else if (xs && !kxs) {
+        return launch_split_fplanes(O, M, H * hd, xs, st);
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, int cap, float* O, int H, int KVH,
                             int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs, int kvt) {
     if (N <= 0) return hipSuccess;
-    if (er.B < 1 || er.B > VOX_MAX_BATCH || (hd != 64 && hd != 128)) return hipErrorInvalidValue;
-    if (kvt < KV_F32 || kvt > KV_FP8 || (kvt != KV_F32 && hd != 128 && !(kvt == KV_F16 && hd == 64)))
-        return hipErrorInvalidValue;
+    if (er.B < 1 || er.B > VOX_MAX_BATCH || (hd != 64 && hd != 128) || !kv_ring_ok(kvt, hd)) return hipErrorInvalidValue;
     if (xs && N > PLANE_MAX_ROWS) return hipErrorInvalidValue;
-    int qbm = 0, keys = 0;
+    int qbm = 0, keys = 0, nblk = 0;
     for (int b = 0; b < er.B; b++) {
         qbm = std::max(qbm, (er.nr[b] + 15) / 16);
         const int ks = std::max(er.pos0[b] - window + 1, 0);
         keys = std::max(keys, er.pos0[b] + er.nr[b] - ks);
+        nblk += H * ((er.nr[b] + 15) / 16);
     }
     if (qbm == 0) return hipSuccess;
-    // key splits as launch_attn_rows_mf picks them, over every stream's (head, query block)s
-    int ns = 1;
-    int nblk = 0;
-    for (int b = 0; b < er.B; b++) nblk += H * ((er.nr[b] + 15) / 16);
-    if (ws && nblk < 256) {
-        ns = std::min((keys + 63) / 64, std::max(1, 256 / nblk));
-        while (ns > 1 && (size_t)H * N * ns * (hd + 2) > ws_elems) ns--;
-    }
-    dim3 grid(H, qbm, ns * er.B);
-    // xs: the output rows as the wo input's planes (by the attention itself, or by the combine)
-    // (a 16-bit or one-byte decoder ring: planes by k_split_fplanes after the kernel, as
-    // launch_attn_rows_mf; the encoder's 16-bit ring, head_dim 64, writes them itself like f32)
-    const bool enc16 = kvt == KV_F16 && hd == 64;
-    uint16_t* kxs = ns == 1 && (kvt == KV_F32 || enc16) && att_planes() ? xs : nullptr;
-    if (enc16)
-        hipLaunchKernelGGL((k_attn_mf<64, kvh_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O, H * hd,
-                           N, H, KVH, 0, 0, window, scale, ns, ws, er, kxs);
-    else if (kvt == KV_FP8)
-        hipLaunchKernelGGL((k_attn_mf<128, kv8_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
-                           H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, nullptr);
-    else if (kvt == KV_F16)
-        hipLaunchKernelGGL((k_attn_mf<128, kvh_t, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
-                           H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, nullptr);
-    else if (hd == 64)
-        hipLaunchKernelGGL((k_attn_mf<64, float, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O, H * hd,
-                           N, H, KVH, 0, 0, window, scale, ns, ws, er, kxs);
-    else
-        hipLaunchKernelGGL((k_attn_mf<128, float, 1>), grid, dim3(256), 0, st, Q, H * hd, nullptr, nullptr, cap, O,
-                           H * hd, N, H, KVH, 0, 0, window, scale, ns, ws, er, kxs);
-    LAUNCH_CHECK();
-    if (ns > 1) {
-        if (hd == 64)
-            hipLaunchKernelGGL(k_attn_tiled_combine<64>, dim3(H, N), dim3(64), 0, st, ws, ns, N, O, H * hd, xs);
-        else
-            hipLaunchKernelGGL(k_attn_tiled_combine<128>, dim3(H, N), dim3(128), 0, st, ws, ns, N, O, H * hd, xs);
-        LAUNCH_CHECK();
-    } else if (xs && !kxs) {
-        return launch_split_fplanes(O, N, H * hd, xs, st);
-    }
-    return hipSuccess;
+    // key splits over every stream's (head, query block)s
+    const int ns = attn_mf_splits(nblk, keys, N, H, hd, ws, ws_elems);
+    return attn_mf_launch<1>(hd, kvt, dim3(H, qbm, ns * er.B), Q, H * hd, nullptr, nullptr, cap, O, H * hd, N, H, KVH, 0,
+                             0, window, scale, ns, ws, er, xs, st);
 }
 
 hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc, const float* Vc,
@@ -3996,60 +3192,18 @@ hipError_t launch_attn_rows_mf(int hd, const float* Q, int ldq, const float* Kc,
                              uint16_t* xs, int kvt, int* ns_out) {
     if (ns_out) *ns_out = 0;
     if (M <= 0) return hipSuccess;
-    if ((hd != 64 && hd != 128) || kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
+    if ((hd != 64 && hd != 128) || !kv_ring_ok(kvt, hd)) return hipErrorInvalidValue;
     if (xs && (M > PLANE_MAX_ROWS || ldo != H * hd)) return hipErrorInvalidValue;
     // 16 queries per block: 32 (each K/V tile of a 25-row streaming chunk read once per head
     // instead of twice) measured slower, 15.7 vs 14.6 us (tools/kbench, round 1)
     const int QT = 16;
     const int qb = (M + QT - 1) / QT;
-    // key-range splits when the (head, query block) grid cannot fill the chip: at least 64
-    // keys per split, about 256 blocks in all (a 25-row streaming chunk over ~775 keys: 4)
     int ks = q_pos0 - window + 1;
     if (ks < k_first) ks = k_first;
-    const int keys = q_pos0 + M - ks;
-    int ns = 1;
-    if (ws && H * qb < 256) {
-        // (k_attn_mf, 25 rows x 775 keys: 256 blocks 10.4 us, 512 11.8, 128 13.9, 1024 12.0)
-        const int target = g_attn_blocks ? g_attn_blocks : 256;
-        ns = std::min((keys + 63) / 64, std::max(1, target / (H * qb)));
-        while (ns > 1 && (size_t)H * M * ns * (hd + 2) > ws_elems) ns--;
-    }
-    dim3 grid(H, qb, ns);
+    const int ns = attn_mf_splits(H * qb, q_pos0 + M - ks, M, H, hd, ws, ws_elems, g_attn_blocks ? g_attn_blocks : 256);
     if (ns_out) *ns_out = ns;
-    const bool enc16 = kvt == KV_F16 && hd == 64;
-    if (enc16) {
-        // the encoder's opt-in 16-bit ring: the f32 instance's grid, splits and plane output
-        hipLaunchKernelGGL((k_attn_mf<64, kvh_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0,
-                           k_first, window, scale, ns, ws, EncRows{}, ns == 1 && att_planes() ? xs : nullptr);
-    } else if (kvt == KV_FP8) {
-        // the one-byte decoder ring (prefill)
-        if (hd != 128) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_attn_mf<128, kv8_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH,
-                           q_pos0, k_first, window, scale, ns, ws);
-    } else if (kvt == KV_F16) {
-        // the 16-bit decoder ring (prefill)
-        if (hd != 128) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_attn_mf<128, kvh_t>), grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH,
-                           q_pos0, k_first, window, scale, ns, ws);
-    } else if (hd == 64) {
-        hipLaunchKernelGGL(k_attn_mf<64>, grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0,
-                           k_first, window, scale, ns, ws, EncRows{}, ns == 1 && att_planes() ? xs : nullptr);
-    } else {
-        hipLaunchKernelGGL(k_attn_mf<128>, grid, dim3(256), 0, st, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0,
-                           k_first, window, scale, ns, ws, EncRows{}, ns == 1 && att_planes() ? xs : nullptr);
-    }
-    LAUNCH_CHECK();
-    if (ns > 1) {
-        // with xs the combine writes the wo planes itself
-        if (hd == 64)
-            hipLaunchKernelGGL(k_attn_tiled_combine<64>, dim3(H, M), dim3(64), 0, st, ws, ns, M, O, ldo, xs);
-        else
-            hipLaunchKernelGGL(k_attn_tiled_combine<128>, dim3(H, M), dim3(128), 0, st, ws, ns, M, O, ldo, xs);
-        LAUNCH_CHECK();
-    } else if (xs && ((kvt != KV_F32 && !enc16) || !att_planes())) {
-        return launch_split_fplanes(O, M, H * hd, xs, st);
-    }
-    return hipSuccess;
+    return attn_mf_launch<0>(hd, kvt, dim3(H, qb, ns), Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0, k_first, window,
+                             scale, ns, ws, EncRows{}, xs, st);
 }
 
 hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bias, int qd, int kvd, int hd,
@@ -4057,281 +3211,18 @@ hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bi
                                 int kvt) {
     if (M <= 0) return hipSuccess;
     if (M > SK_MAX_ROWS || S < 1 || qd % hd || kvd % hd || hd % 2) return hipErrorInvalidValue;
-    if (kvt != KV_F32 && kvt != KV_F16) return hipErrorInvalidValue;  // no one-byte instance
-    if (kvt == KV_F16)
-        hipLaunchKernelGGL(k_slabs_rope_kv<kvh_t>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias,
-                           qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
-    else
-        hipLaunchKernelGGL(k_slabs_rope_kv<float>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias, qd, kvd,
-                       hd, rope, pos0, q, Kc, Vc, cap);
-    LAUNCH_CHECK();
-    return hipSuccess;
-}
-
-#ifdef VOX_GEMV_STAMPS
-// diagnostic build only (tools/kbench_stamps): where k_gemv's per-block stamps go (null: off)
-hipError_t gemv_set_stamps(unsigned long long* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_gemv_stamps), &p, sizeof p); }
-#endif
-VOX_KB_KNOB(g_gemv_rb, 0);  // tools/kbench knob: force 4- or 8-row groups (0 = automatic)
-// Rows per group: each block should stream at least two groups, so that the next group's
-// loads overlap this group's reduction and epilogue (one group per block left every block
-// idle at its tail).  tools/kbench, bf16 / 768 blocks: QKV 10.2 -> 8.5 us with 4-row
-// groups, W1|W3 20.5 -> 20.0, W2 12.1 -> 11.4 and wo 6.7 -> 6.4 with 2-row groups; the LM
-// head (16 groups per block at 8 rows) keeps 8.
-static int gemv_rb(int rows) {
-    if (g_gemv_rb && rows % g_gemv_rb == 0) return g_gemv_rb;
-    if (rows >= 65536 && rows % 8 == 0) return 8;
-    if (rows >= 6144 && rows % 4 == 0) return 4;
-    return 2;
-}
-
-int gemv_rowgroup(int rows) { return gemv_rb(rows); }
-// wmx4 instances: a 2-row group's record would carry half a dword of padding (6 bits per
-// weight instead of 5) and a quarter of a bf16 group's bytes, so they take at least 4 rows
-// where the row count allows it; each row's bits do not depend on the group size
-static int gemv_rb_mx4(int rows) {
-    const int rb = gemv_rb(rows);
-    return rb < 4 && rows % 4 == 0 ? 4 : rb;
-}
-int gemv_rowgroup_mx4(int rows) { return gemv_rb_mx4(rows); }
-
-VOX_KB_KNOB(g_gemv_maxb, 0);  // tools/kbench knob: grid cap other than GEMV_MAX_BLOCKS (no LM head)
-static int gemv_grid_rb(int rows, int rb) {
-    // the largest divisor of the group count that fits 4 blocks per CU: every block then
-    // runs the same number of groups (no tail); tools/kbench VOX_KB_ONLY=grid: 1536-2304
-    // blocks were slower on every decode shape, bf16 and Q8 (profiles/r3_kbench_gemv_grid.txt)
-    const int ng = rows / rb, maxb = g_gemv_maxb ? g_gemv_maxb : GEMV_MAX_BLOCKS;
-    int best = 1;
-    for (int gsz = 1; gsz <= maxb && gsz <= ng; gsz++)
-        if (ng % gsz == 0) best = gsz;
-    if (best < 256 && ng > maxb) best = maxb;  // no good divisor: accept a tail
-    return best;
-}
-int gemv_grid(int rows) { return gemv_grid_rb(rows, gemv_rb(rows)); }
-int gemv_grid_mx4(int rows) { return gemv_grid_rb(rows, gemv_rb_mx4(rows)); }
-
-template <int P, int E, int RB, int Q8>
-static const void* gemv_fn(int kq) {
-    switch (kq) {
-        case 1: return reinterpret_cast<const void*>(&k_gemv<P, E, RB, 1, Q8>);
-        case 2: return reinterpret_cast<const void*>(&k_gemv<P, E, RB, 2, Q8>);
-        case 3: return reinterpret_cast<const void*>(&k_gemv<P, E, RB, 3, Q8>);
-        case 4: return reinterpret_cast<const void*>(&k_gemv<P, E, RB, 4, Q8>);
-        case 5: return reinterpret_cast<const void*>(&k_gemv<P, E, RB, 5, Q8>);
-        default: return nullptr;
-    }
-}
-
-int gemv_occupancy(const void* fn) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, 0) != hipSuccess) occ = 0;
-    return occ;
-}
-
-template <int P, int E, int RB, int Q8>
-static hipError_t gemv_k(const GemvArgs& a, int grid, hipStream_t st) {
-    const int kq = ((Q8 == WF_Q8 ? a.K >> 4 : a.K >> 3) + 255) / 256;
-    switch (kq) {
-#define KQ_CASE(Q) case Q: hipLaunchKernelGGL((k_gemv<P, E, RB, Q, Q8>), dim3(grid), dim3(256), 0, st, a); break;
-        KQ_CASE(1) KQ_CASE(2) KQ_CASE(3) KQ_CASE(4) KQ_CASE(5)
-#undef KQ_CASE
-        default: return hipErrorInvalidValue;
-    }
-    LAUNCH_CHECK();
-    return hipSuccess;
-}
-
-// the wpack13 instances: the decoder step's GEMVs (and STORE for a single packed GEMV);
-// the encoder's single-row chunks stay bf16
-template <int P, int E>
-constexpr bool gemv_p13 = (P == PRO_NONE && (E == EPI_STORE || E == EPI_RESID)) || (P == PRO_NORM && E == EPI_QKV) ||
-                          (P == PRO_NORM_ADA && E == EPI_SWIGLU) ||
-                          (P == PRO_NORM && (E == EPI_LOGITS || E == EPI_LOGITS_ALT));
-
-template <int P, int E, int RB>
-static hipError_t gemv_q(const GemvArgs& a, int grid, hipStream_t st) {
-    if (a.wscale) return gemv_k<P, E, RB, WF_Q8>(a, grid, st);
-    if constexpr (gemv_p13<P, E>) {
-        if (a.wm_plane) return gemv_k<P, E, RB, WF_MX4>(a, grid, st);
-        if (a.wp_main) return gemv_k<P, E, RB, WF_P13>(a, grid, st);
-    } else if (a.wp_main || a.wm_plane) {
-        return hipErrorInvalidValue;
-    }
-    return gemv_k<P, E, RB, WF_BF16>(a, grid, st);
-}
-template <int P, int E, int RB>
-static const void* gemv_fn_q(const GemvArgs& a, int kq) {
-    if (a.wscale) return gemv_fn<P, E, RB, WF_Q8>(kq);
-    if constexpr (gemv_p13<P, E>) {
-        if (a.wm_plane) return gemv_fn<P, E, RB, WF_MX4>(kq);
-        if (a.wp_main) return gemv_fn<P, E, RB, WF_P13>(kq);
-    } else if (a.wp_main || a.wm_plane) {
-        return nullptr;
-    }
-    return gemv_fn<P, E, RB, WF_BF16>(kq);
-}
-
-// kernel instance launch_gemv would use (tools, occupancy queries)
-// row group and grid of a launch: the wmx4 plane has its own group size
-static bool gemv_is_mx4(const GemvArgs& a) { return a.wm_plane && !a.wscale; }
-static int gemv_rb_of(const GemvArgs& a) { return gemv_is_mx4(a) ? gemv_rb_mx4(a.rows) : gemv_rb(a.rows); }
-static int gemv_grid_of(const GemvArgs& a) { return gemv_grid_rb(a.rows, gemv_rb_of(a)); }
-
-const void* gemv_kernel(int pro, int epi, const GemvArgs& a) {
-    const int rb = gemv_rb_of(a);
-    const int kq = ((a.wscale ? a.K >> 4 : a.K >> 3) + 255) / 256;
-#define GEMV_FN(P, E)         \
-    if (pro == P && epi == E) \
-        return rb == 8 ? gemv_fn_q<P, E, 8>(a, kq) : rb == 2 ? gemv_fn_q<P, E, 2>(a, kq) : gemv_fn_q<P, E, 4>(a, kq);
-    GEMV_FN(PRO_NONE, EPI_STORE) GEMV_FN(PRO_NONE, EPI_RESID) GEMV_FN(PRO_NORM, EPI_QKV)
-    GEMV_FN(PRO_NORM_ADA, EPI_SWIGLU) GEMV_FN(PRO_NORM, EPI_LOGITS) GEMV_FN(PRO_NORM, EPI_LOGITS_ALT)
-    GEMV_FN(PRO_NORM, EPI_QKV_BIAS) GEMV_FN(PRO_NORM, EPI_SWIGLU)
-#undef GEMV_FN
-    return nullptr;
-}
-
-// The same launch with HIP events recorded by the kernel's own dispatch packet
-// (hipExtLaunchKernel): they bracket the kernel itself, not the marker packets an
-// event-record node adds.  Eager launches only (not capturable into a graph).
-hipError_t launch_gemv_timed(int pro, int epi, const GemvArgs& a, hipEvent_t start, hipEvent_t stop,
-                             hipStream_t st) {
-    const void* fn = gemv_kernel(pro, epi, a);
-    if (!fn) return hipErrorInvalidValue;
-    GemvArgs args = a;
-    void* kargs[] = {&args};
-    return hipExtLaunchKernel(fn, dim3(gemv_grid_of(a)), dim3(256), kargs, 0, st, start, stop, 0);
-}
-
-// the shapes launch_gemv accepts: whole 16-B chunks per row, whole row groups, and at most
-// 5 rounds of 256 chunks per row (the instantiated KQ)
-bool gemv_ok(int rows, int K, int q8) {
-    const int kc = q8 ? K >> 4 : K >> 3;
-    return rows > 0 && K > 0 && K % (q8 ? 16 : 8) == 0 && rows % gemv_rb(rows) == 0 && (kc + 255) / 256 <= 5;
-}
-
-// the shapes the wmx4 instances accept: gemv_ok's, whole 32-weight blocks, whole wmx4 row
-// groups, and a plane that a 32-bit buffer offset reaches
-bool gemv_ok_mx4(int rows, int K) {
-    if (!gemv_ok(rows, K, 0) || K % 32 || rows % gemv_rb_mx4(rows)) return false;
-    const int rb = gemv_rb_mx4(rows);
-    return (long long)rows / rb * (K / 8) * (rb + (rb + 3) / 4) * 4 < (1LL << 31);
-}
-
-hipError_t launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t st) {
-    const int rb = gemv_rb_of(a);
-    if (!gemv_ok(a.rows, a.K, a.wscale != nullptr)) return hipErrorInvalidValue;
-    if (gemv_is_mx4(a) && !gemv_ok_mx4(a.rows, a.K)) return hipErrorInvalidValue;
-    if (epi == EPI_QKV_BIAS && !a.bias) return hipErrorInvalidValue;
-    const int grid = gemv_grid_of(a);
-#define GEMV_CASE(P, E) \
-    if (pro == P && epi == E)                                                            \
-        return rb == 8 ? gemv_q<P, E, 8>(a, grid, st) : rb == 2 ? gemv_q<P, E, 2>(a, grid, st) : gemv_q<P, E, 4>(a, grid, st);
-    GEMV_CASE(PRO_NONE, EPI_STORE) GEMV_CASE(PRO_NONE, EPI_RESID) GEMV_CASE(PRO_NORM, EPI_QKV)
-    GEMV_CASE(PRO_NORM_ADA, EPI_SWIGLU) GEMV_CASE(PRO_NORM, EPI_LOGITS) GEMV_CASE(PRO_NORM, EPI_LOGITS_ALT)
-    // the encoder's single-row chunks (run_encoder_rows_gemv)
-    GEMV_CASE(PRO_NORM, EPI_QKV_BIAS) GEMV_CASE(PRO_NORM, EPI_SWIGLU)
-#undef GEMV_CASE
-    return hipErrorInvalidValue;
-}
-
-// k_gemvr instances: 8-row groups only where the LM head has them (STORE), and more than two
-// K rounds only where the input is not a dec_dim row (wo and W2: PRO_NONE) and the group is
-// not the LM head's
-template <int P, int E, int RB, int KQ>
-constexpr bool gemvr_inst = (RB < 8 || E == EPI_STORE) && (KQ <= 2 || (P == PRO_NONE && RB < 8));
-
-template <int P, int E, int RB, int KQ, int WF>
-static const void* gemvr_fn_r(int R) {
-    if constexpr (gemvr_inst<P, E, RB, KQ>) {
-        switch (R) {
-            case 1: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 1>);
-            case 2: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 2>);
-            case 4: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 4>);
-            case 8: return reinterpret_cast<const void*>(&k_gemvr<P, E, RB, KQ, WF, 8>);
+    // kv_ring refuses a 16-bit ring at a head_dim other than 64 or 128 (kv_ring_ok), where this
+    // launcher used to launch; the attention over such a ring always refused it
+    return kv_ring(kvt, hd, [&](auto ring) {
+        using KT = typename decltype(ring)::type;
+        if constexpr (std::is_same_v<KT, kv8_t>) {
+            return hipErrorInvalidValue;  // no one-byte instance
+        } else {
+            hipLaunchKernelGGL(k_slabs_rope_kv<KT>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias,
+                               qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
+            return hipGetLastError();
         }
-    }
-    return nullptr;
-}
-template <int P, int E, int RB, int WF>
-static const void* gemvr_fn_kq(int kq, int R) {
-    switch (kq) {
-        case 1: return gemvr_fn_r<P, E, RB, 1, WF>(R);
-        case 2: return gemvr_fn_r<P, E, RB, 2, WF>(R);
-        case 3: return gemvr_fn_r<P, E, RB, 3, WF>(R);
-        case 4: return gemvr_fn_r<P, E, RB, 4, WF>(R);
-        case 5: return gemvr_fn_r<P, E, RB, 5, WF>(R);
-        default: return nullptr;
-    }
-}
-// wf: WF_BF16, WF_P13 or WF_MX4.  The MX4 instances exist for the 4- and 8-row groups of the
-// wmx4 plane (gemv_rb_mx4 of a row count that is a multiple of 4); a 2-row wmx4 plane has none
-// The Q8 instances: the same (PRO, EPI, RB) set with K rounds of 256 16-weight
-// chunks, 1..3 of them (K <= 12,288; gemvr_inst: the third only for wo / W2-like launches)
-template <int P, int E, int RB>
-static const void* gemvr_fn_kq_q8(int kq, int R) {
-    switch (kq) {
-        case 1: return gemvr_fn_r<P, E, RB, 1, WF_Q8>(R);
-        case 2: return gemvr_fn_r<P, E, RB, 2, WF_Q8>(R);
-        case 3: return gemvr_fn_r<P, E, RB, 3, WF_Q8>(R);
-        default: return nullptr;
-    }
-}
-template <int P, int E>
-static const void* gemvr_fn(int rb, int kq, int wf, int R) {
-    if (wf == WF_Q8) {
-        if (rb == 2) return gemvr_fn_kq_q8<P, E, 2>(kq, R);
-        if (rb == 4) return gemvr_fn_kq_q8<P, E, 4>(kq, R);
-        if (rb == 8) return gemvr_fn_kq_q8<P, E, 8>(kq, R);
-        return nullptr;
-    }
-    if (wf == WF_MX4) {
-        if (rb == 4) return gemvr_fn_kq<P, E, 4, WF_MX4>(kq, R);
-        if (rb == 8) return gemvr_fn_kq<P, E, 8, WF_MX4>(kq, R);
-        return nullptr;
-    }
-#define GEMVR_RB(RB) \
-    if (rb == RB) return wf == WF_P13 ? gemvr_fn_kq<P, E, RB, WF_P13>(kq, R) : gemvr_fn_kq<P, E, RB, WF_BF16>(kq, R);
-    GEMVR_RB(2) GEMVR_RB(4) GEMVR_RB(8)
-#undef GEMVR_RB
-    return nullptr;
-}
-static const void* gemvr_pick(int pro, int epi, int rows, int K, int wf, int R) {
-    if (!gemv_ok(rows, K, wf == WF_Q8)) return nullptr;
-    if (wf == WF_MX4 && !gemv_ok_mx4(rows, K)) return nullptr;
-    const int rb = wf == WF_MX4 ? gemv_rb_mx4(rows) : gemv_rb(rows);
-    const int kq = ((wf == WF_Q8 ? K >> 4 : K >> 3) + 255) / 256;
-#define GEMVR_FN(P, E) \
-    if (pro == P && epi == E) return gemvr_fn<P, E>(rb, kq, wf, R);
-    GEMVR_FN(PRO_NORM, EPI_QKV) GEMVR_FN(PRO_NONE, EPI_RESID) GEMVR_FN(PRO_NORM_ADA, EPI_SWIGLU)
-    GEMVR_FN(PRO_NORM, EPI_STORE) GEMVR_FN(PRO_NONE, EPI_STORE)
-#undef GEMVR_FN
-    return nullptr;
-}
-
-bool gemvr_ok(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_BF16, 1) != nullptr; }
-bool gemvr_ok_mx4(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_MX4, 1) != nullptr; }
-bool gemvr_ok_q8(int pro, int epi, int rows, int K) { return gemvr_pick(pro, epi, rows, K, WF_Q8, 1) != nullptr; }
-
-// weight source of a launch, in gemv_q's order: Q8 rows (wscale), the wmx4 plane, the wpack13
-// planes, the raw rows
-static int gemvr_wf(const GemvRArgs& a) {
-    return a.g.wscale ? WF_Q8 : a.g.wm_plane ? WF_MX4 : a.g.wp_main ? WF_P13 : WF_BF16;
-}
-
-// kernel instance launch_gemvr would use (tools, occupancy queries)
-const void* gemvr_kernel(int pro, int epi, int R, const GemvRArgs& a) {
-    return gemvr_pick(pro, epi, a.g.rows, a.g.K, gemvr_wf(a), R);
-}
-
-hipError_t launch_gemvr(int pro, int epi, int R, const GemvRArgs& a, hipStream_t st) {
-    if (a.g.bias || (epi == EPI_QKV && !a.slots)) return hipErrorInvalidValue;
-    const void* fn = gemvr_kernel(pro, epi, R, a);
-    if (!fn) return hipErrorInvalidValue;
-    GemvRArgs args = a;
-    void* kargs[] = {&args};
-    // the wmx4 plane has its own group size, hence its own grid (k_gemv's wmx4 launch)
-    const int grid = gemvr_wf(a) == WF_MX4 ? gemv_grid_mx4(a.g.rows) : gemv_grid(a.g.rows);
-    return hipLaunchKernel(fn, dim3(grid), dim3(256), kargs, 0, st);
+    });
 }
 
 // partial slots per head (at least 4)
@@ -4409,136 +3300,96 @@ int g_attn_short = -1;  // k_attn_short for one stream's contexts <= 256 keys (V
 hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const float* Vc, int cap,
                               const int* state, int pos_host, int window, float scale, int H,
                               int KVH, float* part, float* out, int splits, hipStream_t st, int kvt) {
-    if (kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
     if (g_attn_short < 0) {
         const char* e = getenv("VOX_HIP_ATT_SHORT");
         g_attn_short = (e && atoi(e) == 0) ? 0 : 1;
     }
-    if (g_attn_short && splits == 1 && hd == 128 && window > ATT_BK && cap >= ATT_BK && H % KVH == 0) {
-        // contexts of <= 256 keys (splits == 1) with a window of > 256: nothing has left the
-        // window (lp < 256 < window) and the ring has not wrapped, so keys = slots 0..lp (a
-        // window of exactly 256 would reach L = 256 again at lp >= 256 with wrapped slots)
-        if (kvt == KV_FP8)
-            hipLaunchKernelGGL((k_attn_short<128, kv8_t, 4>), dim3(H), dim3(1024), 0, st, q,
-                               reinterpret_cast<const kv8_t*>(Kc), reinterpret_cast<const kv8_t*>(Vc), state, pos_host,
-                               scale, H, KVH, out);
-        else if (kvt == KV_F16)
-            hipLaunchKernelGGL((k_attn_short<128, kvh_t, 4>), dim3(H), dim3(1024), 0, st, q,
-                               reinterpret_cast<const kvh_t*>(Kc), reinterpret_cast<const kvh_t*>(Vc), state, pos_host,
-                               scale, H, KVH, out);
-        else
-            hipLaunchKernelGGL((k_attn_short<128, float, 4>), dim3(H), dim3(1024), 0, st, q, Kc, Vc, state, pos_host,
-                               scale, H, KVH, out);
-        LAUNCH_CHECK();
-        return hipSuccess;
-    }
-    AttnPtrs p;
-    memset(&p, 0, sizeof p);
-    p.q[0] = q; p.Kc[0] = Kc; p.Vc[0] = Vc; p.state[0] = state; p.part[0] = part; p.out[0] = out;
-    return kvt == KV_FP8   ? attn_launch<kv8_t>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st)
-           : kvt == KV_F16 ? attn_launch<kvh_t>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st)
-                           : attn_launch<float>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st);
+    // contexts of <= 256 keys (splits == 1) with a window of > 256: nothing has left the
+    // window (lp < 256 < window) and the ring has not wrapped, so keys = slots 0..lp (a
+    // window of exactly 256 would reach L = 256 again at lp >= 256 with wrapped slots)
+    const bool shortctx = g_attn_short && splits == 1 && hd == 128 && window > ATT_BK && cap >= ATT_BK && H % KVH == 0;
+    return kv_ring(kvt, hd, [&](auto ring) {
+        using KT = typename decltype(ring)::type;
+        if (shortctx) {
+            hipLaunchKernelGGL((k_attn_short<128, KT, 4>), dim3(H), dim3(1024), 0, st, q, reinterpret_cast<const KT*>(Kc),
+                               reinterpret_cast<const KT*>(Vc), state, pos_host, scale, H, KVH, out);
+            return hipGetLastError();
+        }
+        AttnPtrs p;
+        memset(&p, 0, sizeof p);
+        p.q[0] = q; p.Kc[0] = Kc; p.Vc[0] = Vc; p.state[0] = state; p.part[0] = part; p.out[0] = out;
+        return attn_launch<KT>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st);
+    });
 }
 
 hipError_t launch_attn_decode_batch(int hd, const AttnPtrs& p, int nb, int cap, int window, float scale,
                                     int H, int KVH, int splits, hipStream_t st, int kvt) {
-    if (kvt < KV_F32 || kvt > KV_FP8) return hipErrorInvalidValue;
-    return kvt == KV_FP8   ? attn_launch<kv8_t>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st)
-           : kvt == KV_F16 ? attn_launch<kvh_t>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st)
-                           : attn_launch<float>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
+    return kv_ring(kvt, hd, [&](auto ring) {
+        return attn_launch<typename decltype(ring)::type>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
+    });
 }
 
-// AP: AttnPtrs, or AttnPtrsRag (per-slot ring capacity: cap is not read)
-template <class KT, class AP = AttnPtrs>
-static hipError_t attn_batch_fused(const AP& p, const AttnFuse& f, int nb, int cap, int window, float scale,
-                                   int H, int KVH, int splits, int maxs, hipStream_t st) {
-    if (g_attn_bsplit < 0) {
-        const char* e = getenv("VOX_HIP_ATT_BSPLIT");
-        g_attn_bsplit = e ? std::max(0, std::min(2, atoi(e))) : 1;
-    }
-    // contexts <= 256 keys: one 1024-thread block per (stream, kv head) -- unless those blocks
-    // cannot fill the chip (16 streams x 8 kv heads = 128 blocks on 256 CUs): then the 128-key
-    // blocks of the long path (two per (stream, kv head), last arriver merges);
-    // VOX_HIP_ATT_BSPLIT=2: the 128-key blocks at any row count
-    if (splits == 1 && (!g_attn_bsplit || (g_attn_bsplit == 1 && nb * KVH >= 256))) {
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p, cap, 0,
-                           window, scale, H, KVH, maxs, f);
-        LAUNCH_CHECK();
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AP>), dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb),
-                       dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window, scale, H, KVH, maxs, f, 1);
-    LAUNCH_CHECK();
-    return hipSuccess;
-}
-
-static bool attn_batch_args_ok(int hd, const AttnFuse& f, int nb, int nb_max, int window, int H, int KVH, int splits,
-                               int kvt) {
-    return kvt >= KV_F32 && kvt <= KV_FP8 && hd == 128 && H % KVH == 0 && H / KVH <= 4 &&
-           attn_maxch(window) <= ATT_MAX_PARTS && splits >= 1 && splits <= attn_maxsplits(window) && nb >= 1 &&
-           nb <= nb_max && f.qkv && f.rope && f.xs && f.N == (H + 2 * KVH) * hd;
-}
-
-hipError_t launch_attn_batch_fused_rag(int hd, const AttnPtrsRag& p, const AttnFuse& f, int nb, int window, float scale,
-                                       int H, int KVH, int splits, hipStream_t st, int kvt) {
+// The batched step's fused attention over its four argument types.  AttnPtrs / AttnPtrsRag: the
+// <= 32-row step (pointer arrays, any slab count).  AttnSlots / AttnSlotsRag: the wide step, the
+// same kernels over the compact slot-table argument (blockIdx.z up to VOX_MAX_SLOTS; f32 QKV
+// rows, f.S = 1; partials at part + z * part_ld).  The ragged forms take each ring's capacity
+// from p.caps: the shared cap is not read.
+template <class AP>
+static hipError_t attn_batch(int hd, const AP& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                             int KVH, int splits, hipStream_t st, int kvt) {
+    constexpr bool wide = std::is_base_of_v<AttnSlots, AP>;
+    constexpr bool ragged = std::is_base_of_v<AttnPtrsRag, AP> || std::is_base_of_v<AttnSlotsRag, AP>;
     const int maxs = attn_maxch(window);
-    if (!attn_batch_args_ok(hd, f, nb, VOX_MAX_BATCH, window, H, KVH, splits, kvt) || f.S < 1 || !p.slots || !p.caps)
+    if (hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 || splits > attn_maxsplits(window) ||
+        nb < 1 || nb > (wide ? VOX_MAX_SLOTS : VOX_MAX_BATCH) || !f.qkv || !f.rope || !f.xs || (wide ? f.S != 1 : f.S < 1) ||
+        f.N != (H + 2 * KVH) * hd || ((wide || ragged) && !p.slots))
         return hipErrorInvalidValue;
-    return kvt == KV_FP8   ? attn_batch_fused<kv8_t, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
-           : kvt == KV_F16 ? attn_batch_fused<kvh_t, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
-                           : attn_batch_fused<float, AttnPtrsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st);
+    if constexpr (ragged)
+        if (!p.caps) return hipErrorInvalidValue;
+    // part_ld: the partials of H heads, then one arrival count per kv head (attn_launch's layout)
+    if constexpr (wide)
+        if (!p.part || p.part_ld < (size_t)H * maxs * (hd + 2) + KVH) return hipErrorInvalidValue;
+    // contexts <= 256 keys: one 1024-thread block per (stream, kv head).  The <= 32-row step
+    // leaves that grid where its blocks cannot fill the chip (16 streams x 8 kv heads = 128 blocks
+    // on 256 CUs) for the 128-key blocks of the long path (two per (stream, kv head), last arriver
+    // merges; VOX_HIP_ATT_BSPLIT=2: at any row count, 0: never); 64 slots x 8 kv heads of the wide
+    // step already fill it.  Past 256 keys: the 128-key split grid.
+    bool whole = splits == 1;
+    if constexpr (!wide) {
+        if (g_attn_bsplit < 0) {
+            const char* e = getenv("VOX_HIP_ATT_BSPLIT");
+            g_attn_bsplit = e ? std::max(0, std::min(2, atoi(e))) : 1;
+        }
+        whole = whole && (!g_attn_bsplit || (g_attn_bsplit == 1 && nb * KVH >= 256));
+    }
+    return kv_ring(kvt, hd, [&](auto ring) {
+        using KT = typename decltype(ring)::type;
+        if (whole)
+            hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
+                               cap, 0, window, scale, H, KVH, maxs, f);
+        else
+            hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AP>),
+                               dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb), dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window,
+                               scale, H, KVH, maxs, f, 1);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_attn_batch_fused(int hd, const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window,
                                    float scale, int H, int KVH, int splits, hipStream_t st, int kvt) {
-    const int maxs = attn_maxch(window);
-    if (kvt < KV_F32 || kvt > KV_FP8 || hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 || splits > attn_maxsplits(window) ||
-        nb < 1 || nb > VOX_MAX_BATCH || !f.qkv || !f.rope || !f.xs || f.S < 1 || f.N != (H + 2 * KVH) * hd)
-        return hipErrorInvalidValue;
-    return kvt == KV_FP8   ? attn_batch_fused<kv8_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
-           : kvt == KV_F16 ? attn_batch_fused<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
-                           : attn_batch_fused<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
+    return attn_batch(hd, p, f, nb, cap, window, scale, H, KVH, splits, st, kvt);
 }
-// the wide step's instances: the fused kernels over the compact slot-table argument (blockIdx.z
-// up to VOX_MAX_SLOTS).  64 slots x 8 kv heads already fill the chip, so <= 256 keys always
-// take the 1024-thread block (no bsplit rule); past 256 keys the 128-key grid of the <= 32 step
-// AP: AttnSlots, or AttnSlotsRag (per-slot ring capacity: cap is not read)
-template <class KT, class AP = AttnSlots>
-static hipError_t attn_batch_wide(const AP& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
-                                  int KVH, int splits, int maxs, hipStream_t st) {
-    if (splits == 1)
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
-                           cap, 0, window, scale, H, KVH, maxs, f, 0);
-    else
-        hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_LWAVES, KT, AP>),
-                           dim3(splits * (ATT_BK / ATT_LBK) * KVH, 1, nb), dim3(ATT_LWAVES * 64), 0, st, p, cap, 0, window,
-                           scale, H, KVH, maxs, f, 1);
-    LAUNCH_CHECK();
-    return hipSuccess;
+hipError_t launch_attn_batch_fused_rag(int hd, const AttnPtrsRag& p, const AttnFuse& f, int nb, int window, float scale,
+                                       int H, int KVH, int splits, hipStream_t st, int kvt) {
+    return attn_batch(hd, p, f, nb, 0, window, scale, H, KVH, splits, st, kvt);
 }
-
 hipError_t launch_attn_batch_wide(int hd, const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window,
                                   float scale, int H, int KVH, int splits, hipStream_t st, int kvt) {
-    const int maxs = attn_maxch(window);
-    // part_ld: the partials of H heads, then one arrival count per kv head (attn_launch's layout)
-    if (kvt < KV_F32 || kvt > KV_FP8 || hd != 128 || H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 ||
-        splits > attn_maxsplits(window) || nb < 1 || nb > VOX_MAX_SLOTS || !p.slots || !p.part ||
-        p.part_ld < (size_t)H * maxs * (hd + 2) + KVH || !f.qkv || !f.rope || !f.xs || f.S != 1 ||
-        f.N != (H + 2 * KVH) * hd)
-        return hipErrorInvalidValue;
-    return kvt == KV_FP8   ? attn_batch_wide<kv8_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
-           : kvt == KV_F16 ? attn_batch_wide<kvh_t>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st)
-                           : attn_batch_wide<float>(p, f, nb, cap, window, scale, H, KVH, splits, maxs, st);
+    return attn_batch(hd, p, f, nb, cap, window, scale, H, KVH, splits, st, kvt);
 }
 hipError_t launch_attn_batch_wide_rag(int hd, const AttnSlotsRag& p, const AttnFuse& f, int nb, int window, float scale,
                                       int H, int KVH, int splits, hipStream_t st, int kvt) {
-    const int maxs = attn_maxch(window);
-    if (!attn_batch_args_ok(hd, f, nb, VOX_MAX_SLOTS, window, H, KVH, splits, kvt) || f.S != 1 || !p.slots || !p.caps ||
-        !p.part || p.part_ld < (size_t)H * maxs * (hd + 2) + KVH)
-        return hipErrorInvalidValue;
-    return kvt == KV_FP8   ? attn_batch_wide<kv8_t, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
-           : kvt == KV_F16 ? attn_batch_wide<kvh_t, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st)
-                           : attn_batch_wide<float, AttnSlotsRag>(p, f, nb, 0, window, scale, H, KVH, splits, maxs, st);
+    return attn_batch(hd, p, f, nb, 0, window, scale, H, KVH, splits, st, kvt);
 }
 // diagnostic variants for tools/kbench (not used by the engine)
 // the batched fused attention (128-key blocks, the bsplit grid) with per-wave phase stamps

@@ -3,7 +3,7 @@
  * infinities, S.1111.111 is NaN, largest finite value 448 (S.1111.110); subnormals m * 2^-9
  * below 2^-6.
  *
- * The host statement of the rule the kernels' ring stores follow (vox_hip_kernels.hip, kv8_t)
+ * The host statement of the rule the kernels' ring stores follow (vox_hip_dev.h, kv8_t)
  * byte for byte, for every f32 input:
  *   encode: clamp to +-448 (so +-Inf and everything at or above the overflow midpoint 464 give
  *           +-448: the ring saturates, it never stores a NaN for a finite or infinite input),
