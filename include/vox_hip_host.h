@@ -113,6 +113,11 @@ int vh_stream_kv_dtype(const vh_stream_t *s);
  * vh_sched_t serves streams of both types. */
 int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on);
 int vh_stream_enc_kv_fp16(const vh_stream_t *s);
+/* The same switch by element type (vox_hip_model_set_enc_kv_dtype, voxtral_hip.h): dtype 0 f32,
+ * 1 IEEE half, 2 FP8 E4M3 (a quarter of the f32 rings' bytes, no scale, quality not evaluated).
+ * 0, or -1 (vh_last_error).  One vh_sched_t serves streams of all three types. */
+int vh_set_enc_kv_dtype(vh_ctx_t *ctx, int dtype);
+int vh_stream_enc_kv_dtype(const vh_stream_t *s);
 /* Decoder K/V rings of streams initialised after this call start at slots0 slots and double as
  * the stream's position needs them, up to the full window + 64 (vox_hip_model_set_kv_grow,
  * voxtral_hip.h: lossless; a one-minute session holds 1024 slots of the 8256).  0: full rings

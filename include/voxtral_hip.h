@@ -128,9 +128,21 @@ int vox_hip_model_set_kv_dtype(vox_hip_model_t *m, int dtype);
  * Its effect on transcripts is NOT evaluated.  Opt-in: off unless VOX_HIP_ENC_KV_FP16 is set
  * nonzero at model creation or on = 1 is passed.  Every encoder path honours the stream's type
  * (one-row GEMV, the skinny chains, the long passes, the batched pass, vox_hip_encoder_full_step).
- * There is NO FP8 encoder ring.  head_dim 64 only (Voxtral's encoder); returns 0, or -1
+ * (FP8 encoder rings: vox_hip_model_set_enc_kv_dtype.)  head_dim 64 only (Voxtral's encoder); returns 0, or -1
  * (vox_hip_last_error) for another head_dim. */
 int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t *m, int on);
+/* The encoder ring element of the streams created after this call (no reference counterpart):
+ * dtype 0 f32 (default), 1 IEEE half (what vox_hip_model_set_enc_kv_fp16(m, 1) selects), 2 FP8
+ * E4M3 bytes by the decoder ring's rule (csrc/vox_kv8.h): no scale, each store clamps to +-448
+ * in f32 and rounds to nearest even, NaN is 0x7f | sign; loads widen exactly, the windowed
+ * attention keeps its f32 MFMA, f32 queries and the f32 ring's accumulation order.  A quarter
+ * of the f32 rings' bytes: 0.24 GB per stream, 31 GB at 128 streams.  Its effect on transcripts
+ * is NOT evaluated.  Opt-in: off unless VOX_HIP_ENC_KV_FP8 is set nonzero at model creation (it
+ * wins over VOX_HIP_ENC_KV_FP16; ignored unless the encoder's head_dim is 64) or dtype = 2 is
+ * passed.  Every encoder path honours the stream's type, and one batched call or scheduler
+ * serves streams of all three.  head_dim 64 only for 1 and 2; returns 0, or -1
+ * (vox_hip_last_error) for another head_dim or dtype. */
+int vox_hip_model_set_enc_kv_dtype(vox_hip_model_t *m, int dtype);
 /* Decoder K/V rings that grow with the stream (no reference counterpart; lossless).  A stream
  * created after this call with slots0 > 0 starts with decoder rings of slots0 slots (clamped to
  * [64, dec_window + 64]; 64 holds the longest prompt) in its own element type instead of the
@@ -298,6 +310,8 @@ int vox_hip_stream_kv_fp16(const vox_hip_stream_t *s);
 int vox_hip_stream_kv_dtype(const vox_hip_stream_t *s);
 /* 1 if the stream's encoder KV rings hold IEEE half (vox_hip_model_set_enc_kv_fp16), else 0 */
 int vox_hip_stream_enc_kv_fp16(const vox_hip_stream_t *s);
+/* the stream's encoder KV ring element: 0 f32, 1 IEEE half, 2 FP8 E4M3 (vox_hip_model_set_enc_kv_dtype) */
+int vox_hip_stream_enc_kv_dtype(const vox_hip_stream_t *s);
 /* Tests / diagnostics: the stream's own encoder passes since creation, by the path they took:
  * out5[0] one-row GEMV passes, [1] fused skinny chains (k_sklx), [2] slab skinny chains,
  * [3] M > 1 rows passes (GEMM), [4] fused-chain passes whose attention took a split key grid and
@@ -325,7 +339,7 @@ int vox_hip_stream_reserve_kv(vox_hip_stream_t *s, int positions);
 int vox_hip_stream_read_kv(vox_hip_stream_t *s, int layer, int first_logical_pos, int n, void *k_out, void *v_out);
 /* Tests / diagnostics: the encoder twin of vox_hip_stream_read_kv -- the raw ring elements of
  * encoder layer `layer` at logical encoder positions [first_logical_pos, first_logical_pos + n),
- * [n][enc_kv_heads * enc_head_dim] in the stream's element type (4 or 2 bytes each) to k_out /
+ * [n][enc_kv_heads * enc_head_dim] in the stream's element type (4, 2 or 1 bytes each) to k_out /
  * v_out (either may be null).  Waits for the stream's queue.  -1 (vox_hip_last_error) for
  * positions beyond the rows encoded so far or already overwritten by the ring's wrap. */
 int vox_hip_stream_read_enc_kv(vox_hip_stream_t *s, int layer, int first_logical_pos, int n, void *k_out, void *v_out);

@@ -203,7 +203,7 @@ struct vox_hip_model {
     std::vector<DecFragD> efrag;   // fragment-major encoder matrices (empty until a short chunk)
     uint8_t* lm_frag;              // fragment-major LM head (tied embeddings)
     int kvt;                       // decoder KV ring element of streams created from now on (KV_F32 / KV_F16 / KV_FP8)
-    int ekvt;                      // encoder KV ring element of streams created from now on (KV_F32 / KV_F16)
+    int ekvt;                      // encoder KV ring element of streams created from now on (KV_F32 / KV_F16 / KV_FP8)
     WPackD plm;                    // wpack13 copy of the LM head
     int wpack;                     // VOX_HIP_WPACK (default 1), read once at creation
     vox_hip_wpack_stats_t wstats;
@@ -594,6 +594,10 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         // vox_hip_model_set_enc_kv_fp16 overrides
         const char* ee = getenv("VOX_HIP_ENC_KV_FP16");
         m->ekvt = (ee && atoi(ee) != 0 && cfg->enc_head_dim == 64) ? KV_F16 : KV_F32;
+        // one-byte encoder rings (FP8 E4M3, vox_kv8.h) when VOX_HIP_ENC_KV_FP8 is set nonzero: before
+        // the 16-bit variable when both are set, head_dim 64 only; vox_hip_model_set_enc_kv_dtype overrides
+        const char* ee8 = getenv("VOX_HIP_ENC_KV_FP8");
+        if (ee8 && atoi(ee8) != 0 && cfg->enc_head_dim == 64) m->ekvt = KV_FP8;
         // decoder rings that start at VOX_HIP_KV_GROW slots and grow with the stream's position
         // (unset or 0: the full ring from the start); vox_hip_model_set_kv_grow overrides
         const char* eg = getenv("VOX_HIP_KV_GROW");
@@ -865,6 +869,15 @@ extern "C" int vox_hip_model_set_enc_kv_fp16(vox_hip_model_t* m, int on) {
     return 0;
 }
 
+extern "C" int vox_hip_model_set_enc_kv_dtype(vox_hip_model_t* m, int dtype) {
+    if (!m) return set_err("model_set_enc_kv_dtype: null model");
+    if (dtype < KV_F32 || dtype > KV_FP8) return set_err("encoder KV element type: 0 (f32), 1 (half) or 2 (fp8), got %d", dtype);
+    if (dtype != KV_F32 && m->c.enc_head_dim != 64)
+        return set_err("%s encoder KV: head_dim 64 only (got %d)", dtype == KV_FP8 ? "FP8" : "16-bit", m->c.enc_head_dim);
+    m->ekvt = dtype;
+    return 0;
+}
+
 extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s);
 
 // Streams created afterwards start with decoder rings of slots0 slots (clamped to [64, window +
@@ -899,7 +912,7 @@ struct vox_hip_stream {
     hipStream_t st;
     // rolling KV caches [layers][cap][kv_dim]
     float *ek, *ev, *dk, *dv;   // dk / dv: elements of type kvt (f32, IEEE half or FP8 E4M3 bytes)
-    int ecap, dcap;             // ek / ev: elements of type ekvt (f32 or IEEE half)
+    int ecap, dcap;             // ek / ev: elements of type ekvt (f32, IEEE half or FP8 E4M3 bytes)
     int kvt, ekvt;
     // growing decoder rings (vox_hip_model_set_kv_grow): the first capacity (0: the full ring from
     // the start, dcap never moves), an upper bound of the rows the ring holds (the last position + 1
@@ -1071,7 +1084,7 @@ extern "C" vox_hip_stream_t* vox_hip_stream_create(vox_hip_model_t* m) {
     if (s->dslots0) s->dcap = s->dslots0;
     s->kvt = m->kvt;
     s->ekvt = m->ekvt;
-    // (a half encoder ring has head_dim 64, so EKV is a multiple of 2)
+    // (a half or one-byte encoder ring has head_dim 64, so EKV is a multiple of 4)
     TRYH(dalloc(&s->ek, (size_t)c.enc_layers * s->ecap * EKV / (4 / kv_esize(s->ekvt))));
     TRYH(dalloc(&s->ev, (size_t)c.enc_layers * s->ecap * EKV / (4 / kv_esize(s->ekvt))));
     // (dalloc counts floats: a half ring takes half of them, a one-byte ring a quarter; the
@@ -1164,6 +1177,7 @@ extern "C" int vox_hip_stream_kv_fp16(const vox_hip_stream_t* s) { return s->kvt
 extern "C" int vox_hip_stream_kv_dtype(const vox_hip_stream_t* s) { return s->kvt; }
 
 extern "C" int vox_hip_stream_enc_kv_fp16(const vox_hip_stream_t* s) { return s && s->ekvt == KV_F16; }
+extern "C" int vox_hip_stream_enc_kv_dtype(const vox_hip_stream_t* s) { return s ? s->ekvt : -1; }
 extern "C" int vox_hip_stream_enc_paths(const vox_hip_stream_t* s, long long out5[5]) {
     if (!s || !out5) return set_err("stream_enc_paths: null argument");
     for (int i = 0; i < 5; i++) out5[i] = s->enc_paths[i];
@@ -2506,11 +2520,11 @@ static int encode_mel_batch_pass(vox_hip_stream_t* const* ss, const float* const
     return 0;
 }
 
-// A list that mixes encoder ring types (vox_hip_model_set_enc_kv_fp16 between the streams'
+// A list that mixes encoder ring types (vox_hip_model_set_enc_kv_dtype between the streams'
 // creations): one stacked pass per type, each over its streams in list order with the type's
-// first stream leading, the f32 group or the half group first by which the list names first.
+// first stream leading, the types (f32, half, FP8) in the order in which the list first names them.
 // Every stream's own queue carries its work as in a single pass, and added[] keeps list order.
-// Synchronous unless every listed stream, of either type, is in async-encode mode.
+// Synchronous unless every listed stream, of any type, is in async-encode mode.
 extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, const float* const* mels, const int* n,
                                                int B, int mel_on_device, int* added) {
     if (B < 1 || !ss || !mels || !n || !added) return set_err("encode_mel_batch: bad arguments");
@@ -2525,13 +2539,18 @@ extern "C" int vox_hip_stream_encode_mel_batch(vox_hip_stream_t* const* ss, cons
         mixed = mixed || ss[b]->ekvt != ss[0]->ekvt;
     }
     if (!mixed) return encode_mel_batch_pass(ss, mels, n, B, mel_on_device, added);
-    for (int pass = 0; pass < 2; pass++) {
-        // pass 0: the streams of ss[0]'s type; pass 1: the others
+    int order[3], ntypes = 0;  // the ring types in the order of their first stream
+    for (int b = 0; b < B; b++) {
+        int t = 0;
+        while (t < ntypes && order[t] != ss[b]->ekvt) t++;
+        if (t == ntypes) order[ntypes++] = ss[b]->ekvt;
+    }
+    for (int pass = 0; pass < ntypes; pass++) {
         std::vector<vox_hip_stream_t*> gs;
         std::vector<const float*> gm;
         std::vector<int> gn, gi;
         for (int b = 0; b < B; b++)
-            if ((ss[b]->ekvt == ss[0]->ekvt) == (pass == 0)) {
+            if (ss[b]->ekvt == order[pass]) {
                 gs.push_back(ss[b]);
                 gm.push_back(mels[b]);
                 gn.push_back(n[b]);
@@ -3083,7 +3102,7 @@ extern "C" int vox_hip_stream_read_kv(vox_hip_stream_t* s, int layer, int first,
 }
 
 // The encoder twin of vox_hip_stream_read_kv: raw ring elements of logical encoder positions
-// [first, first + n) of one encoder layer, in the stream's element type (f32 or IEEE half),
+// [first, first + n) of one encoder layer, in the stream's element type (f32, IEEE half or FP8 codes),
 // [n][enc_kv_heads * enc_head_dim] each.  Waits for the stream's queue.
 extern "C" int vox_hip_stream_read_enc_kv(vox_hip_stream_t* s, int layer, int first, int n, void* k_out, void* v_out) {
     if (!s) return set_err("read_enc_kv: null stream");

@@ -60,10 +60,11 @@ static inline size_t kv_esize(int kvt) { return kvt == KV_FP8 ? 1 : kvt == KV_F1
 // Which rings exist, for every launcher's kvt argument (the element type that Kc / Vc point at):
 // f32 rings at any head_dim; the decoder's 16-bit (VOX_DECODER_KV_FP16) and one-byte (VOX_HIP_KV_FP8,
 // vox_kv8.h) rings at head_dim 128 only; the encoder's opt-in 16-bit rings
-// (vox_hip_model_set_enc_kv_fp16) at head_dim 64.  KV_FP8 at head_dim 64 is refused: there is no
-// one-byte encoder ring.  The launchers pick their instance through kv_ring (vox_hip_kernels.hip).
+// and one-byte rings (vox_hip_model_set_enc_kv_dtype; FP8 by the same vox_kv8.h rule) at head_dim 64.
+// The launchers pick their instance through kv_ring (vox_hip_kernels.hip): at head_dim 64 a narrow
+// ring selects the encoder's instances (KvRing<.., 1>), at 128 the decoder's.
 static inline bool kv_ring_ok(int kvt, int hd) {
-    return kvt == KV_F32 || (kvt == KV_F16 && (hd == 128 || hd == 64)) || (kvt == KV_FP8 && hd == 128);
+    return kvt == KV_F32 || ((kvt == KV_F16 || kvt == KV_FP8) && (hd == 128 || hd == 64));
 }
 
 constexpr int VOX_MAX_BATCH = 32;    // streams per skinny batched decode step (two 16-row blocks of the MFMA B
@@ -362,7 +363,7 @@ struct SklFused {
     float* q = nullptr;
     float* Kc = nullptr;
     float* Vc = nullptr;
-    int kvt = 0;                  // SKX_EPI_QKV: the ring element, KV_F32 or KV_F16 (the encoder's rings)
+    int kvt = 0;                  // SKX_EPI_QKV: the encoder ring's element, KV_F32 / KV_F16 / KV_FP8
 };
 // column slices of a k_sklx launch (the ssq_out slices its consumer sums)
 int sklx_slices(int N, int K);

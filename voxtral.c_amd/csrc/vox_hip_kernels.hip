@@ -1716,7 +1716,7 @@ __global__ __launch_bounds__(256) void k_resid_slabs(float* __restrict__ x, int 
 // QKV slabs of row blockIdx.x summed in split order (+ bias), RoPE of q and k, K/V append at
 // ring slot (pos0 + i) % cap: k_slabs_rows + k_rope_kv in one pass with the same operations
 // in the same order (voxtral_encoder.c:570-607).  rope: the row of position pos0.  KT: the ring
-// element (float, or kvh_t for the encoder's opt-in 16-bit rings: kv_st2's rounding)
+// element (float, or kvh_t / kv8_t for the encoder's opt-in 16-bit / one-byte rings: kv_st2's rounding)
 template <class KT = float>
 __global__ __launch_bounds__(256) void k_slabs_rope_kv(const float* __restrict__ part, int S,
                                                        const float* __restrict__ bias, int qd, int kvd, int hd,
@@ -2552,8 +2552,8 @@ __global__ __launch_bounds__(256) void k_swiglu_fplanes(const float* __restrict_
 // projections.  Same grid, planes and MFMA loop as k_skl (bf16 weights, or the wmx4 fragment
 // plane for the batched decode step's W1|W3); see SklFused.
 // ============================================================================
-// KT: the ring element of the SKX_EPI_QKV append (float, or kvh_t for the encoder's opt-in 16-bit
-// rings; SklFused::kvt picks the instance)
+// KT: the ring element of the SKX_EPI_QKV append (float, or kvh_t / kv8_t for the encoder's opt-in
+// 16-bit / one-byte rings; SklFused::kvt picks the instance)
 template <int NW, int KS, int PRO, int EPI, int WF = WF_BF16, class KT = float>
 __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ xs, int K,
                                                   const uint8_t* __restrict__ W, int N, int nb, const SklFused f) {
@@ -2909,8 +2909,8 @@ __global__ void k_mel_reflect(float* __restrict__ buf, long long n, long long re
     do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
 
 // The ring element of a launch.  f is called with the KvRing tag of (kvt, head_dim): the element
-// type, and enc = 1 for the encoder's half rings (the instances that store kv_f32 values); a pair
-// without a ring (kv_ring_ok, vox_hip_internal.h) has no such instance and is refused.
+// type, and enc = 1 for the encoder's half and one-byte rings at head_dim 64 (the instances that
+// store kv_f32 values); a pair without a ring (kv_ring_ok, vox_hip_internal.h) has no such instance and is refused.
 template <class T, int ENC = 0>
 struct KvRing {
     using type = T;
@@ -2919,7 +2919,7 @@ struct KvRing {
 template <class F>
 static hipError_t kv_ring(int kvt, int hd, F&& f) {
     if (!kv_ring_ok(kvt, hd)) return hipErrorInvalidValue;
-    if (kvt == KV_FP8) return f(KvRing<kv8_t>{});
+    if (kvt == KV_FP8) return hd == 64 ? f(KvRing<kv8_t, 1>{}) : f(KvRing<kv8_t>{});
     if (kvt == KV_F16) return hd == 64 ? f(KvRing<kvh_t, 1>{}) : f(KvRing<kvh_t>{});
     return f(KvRing<float>{});
 }
@@ -3127,14 +3127,14 @@ static int attn_mf_splits(int nblk, int keys, int rows, int H, int hd, const flo
 
 // The k_attn_mf instance of (hd, kvt) over `grid`, then the combine of ns > 1 key ranges.  xs: the
 // output rows also as the wo input's planes: by the attention itself where its instance writes
-// them (f32 rings and the encoder's 16-bit ring), by the combine, or by k_split_fplanes after the
+// them (f32 rings and the encoder's 16-bit and one-byte rings), by the combine, or by k_split_fplanes after the
 // kernel (the decoder's 16-bit and one-byte rings; VOX_HIP_ATT_PLANES=0)
 template <int BAT>
 static hipError_t attn_mf_launch(int hd, int kvt, dim3 grid, const float* Q, int ldq, const float* Kc, const float* Vc,
                                  int cap, float* O, int ldo, int M, int H, int KVH, int q_pos0, int k_first, int window,
                                  float scale, int ns, float* ws, const EncRows& er, uint16_t* xs, hipStream_t st) {
     if (hd != 64 && hd != 128) return hipErrorInvalidValue;
-    const bool writes_planes = kvt == KV_F32 || (kvt == KV_F16 && hd == 64);
+    const bool writes_planes = kvt == KV_F32 || hd == 64;  // (kv_ring_ok: a narrow ring at 64 is the encoder's)
     uint16_t* kxs = ns == 1 && writes_planes && att_planes() ? xs : nullptr;
     const hipError_t e = kv_ring(kvt, hd, [&](auto ring) {
         using R = decltype(ring);
@@ -3214,9 +3214,10 @@ hipError_t launch_slabs_rope_kv(const float* part, int S, int M, const float* bi
     // kv_ring refuses a 16-bit ring at a head_dim other than 64 or 128 (kv_ring_ok), where this
     // launcher used to launch; the attention over such a ring always refused it
     return kv_ring(kvt, hd, [&](auto ring) {
-        using KT = typename decltype(ring)::type;
-        if constexpr (std::is_same_v<KT, kv8_t>) {
-            return hipErrorInvalidValue;  // no one-byte instance
+        using R = decltype(ring);
+        using KT = typename R::type;
+        if constexpr (std::is_same_v<KT, kv8_t> && !R::enc) {
+            return hipErrorInvalidValue;  // no one-byte instance at head_dim 128
         } else {
             hipLaunchKernelGGL(k_slabs_rope_kv<KT>, dim3((qd / 2 + kvd + 255) / 256, M), dim3(256), 0, st, part, S, bias,
                                qd, kvd, hd, rope, pos0, q, Kc, Vc, cap);
@@ -3772,8 +3773,9 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
     if (epi == SKX_EPI_QKV && (!f.q || !f.Kc || !f.Vc || !f.rope || f.hd % 2 || f.qd % f.hd || f.cap < 1 ||
                                N != f.qd + 2 * f.kvd))
         return hipErrorInvalidValue;
-    // the append's ring element: f32, or IEEE half with the QKV epilogue (no one-byte instance)
-    if (f.kvt != KV_F32 && (f.kvt != KV_F16 || epi != SKX_EPI_QKV || mx4 || f.kvd % 2)) return hipErrorInvalidValue;
+    // the append's ring element: f32, or the encoder's IEEE half or FP8 with the QKV epilogue
+    if (f.kvt != KV_F32 && ((f.kvt != KV_F16 && (f.kvt != KV_FP8 || f.hd != 64)) || epi != SKX_EPI_QKV || mx4 || f.kvd % 2))
+        return hipErrorInvalidValue;
 #define SKX_CFG(PP, EE) SKX_X(4, 4, PP, EE) SKX_X(4, 8, PP, EE) SKX_X(8, 4, PP, EE) SKX_X(8, 8, PP, EE)
     if (mx4) {
         // the wmx4 fragment plane: the batched decode step's W1|W3 only
@@ -3785,17 +3787,22 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
     }
 #define SKX_X(NWW, KSS, PP, EE) \
     if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE>(xs, K, Wf, N, nb, f, st);
-    if (f.kvt == KV_F16) {
-#define SKX_H(NWW, KSS, PP, EE) \
+#define SKX_H(NWW, KSS, PP, EE, KTT) \
     if (nw == NWW && ks == KSS && pro == PP && epi == EE) \
-        return sklx_launch<NWW, KSS, PP, EE, WF_BF16, kvh_t>(xs, K, Wf, N, nb, f, st);
-#define SKX_HCFG(PP, EE) SKX_H(4, 4, PP, EE) SKX_H(4, 8, PP, EE) SKX_H(8, 4, PP, EE) SKX_H(8, 8, PP, EE)
-        SKX_HCFG(SKX_PRO_PLANES, SKX_EPI_QKV)
-        SKX_HCFG(SKX_PRO_SCALE, SKX_EPI_QKV)
-#undef SKX_HCFG
-#undef SKX_H
+        return sklx_launch<NWW, KSS, PP, EE, WF_BF16, KTT>(xs, K, Wf, N, nb, f, st);
+#define SKX_HCFG(PP, EE, KTT) SKX_H(4, 4, PP, EE, KTT) SKX_H(4, 8, PP, EE, KTT) SKX_H(8, 4, PP, EE, KTT) SKX_H(8, 8, PP, EE, KTT)
+    if (f.kvt == KV_F16) {
+        SKX_HCFG(SKX_PRO_PLANES, SKX_EPI_QKV, kvh_t)
+        SKX_HCFG(SKX_PRO_SCALE, SKX_EPI_QKV, kvh_t)
         return hipErrorInvalidValue;
     }
+    if (f.kvt == KV_FP8) {
+        SKX_HCFG(SKX_PRO_PLANES, SKX_EPI_QKV, kv8_t)
+        SKX_HCFG(SKX_PRO_SCALE, SKX_EPI_QKV, kv8_t)
+        return hipErrorInvalidValue;
+    }
+#undef SKX_HCFG
+#undef SKX_H
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_SCALE, SKX_EPI_QKV)
     SKX_CFG(SKX_PRO_PLANES, SKX_EPI_RESID)

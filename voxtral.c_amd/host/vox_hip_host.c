@@ -1106,6 +1106,13 @@ int vh_set_enc_kv_fp16(vh_ctx_t *ctx, int on) {
 
 int vh_stream_enc_kv_fp16(const vh_stream_t *s) { return vox_hip_stream_enc_kv_fp16(s->st); }
 
+int vh_set_enc_kv_dtype(vh_ctx_t *ctx, int dtype) {
+    if (vox_hip_model_set_enc_kv_dtype(ctx->model, dtype)) return fail("%s", vox_hip_last_error());
+    return 0;
+}
+
+int vh_stream_enc_kv_dtype(const vh_stream_t *s) { return vox_hip_stream_enc_kv_dtype(s->st); }
+
 int vh_set_kv_grow(vh_ctx_t *ctx, int slots0) {
     if (vox_hip_model_set_kv_grow(ctx->model, slots0)) return fail("%s", vox_hip_last_error());
     return 0;

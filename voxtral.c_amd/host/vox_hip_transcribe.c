@@ -3,8 +3,8 @@
  * MI355X backend through the C host API (include/vox_hip_host.h):
  *
  *   vox_hip_transcribe -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms]
- *                      [--alt cutoff] [--continuous] [--mx4] [--kv8] [--enc-kv16] [--q8-gemmf]
- *                      [--kv-grow slots]
+ *                      [--alt cutoff] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8]
+ *                      [--q8-gemmf] [--kv-grow slots]
  *
  * The audio is fed in pieces of min(interval, 1 s) of samples, as main.c's feed_and_drain
  * does; every generated token id is printed to stdout (the tokenizer is out of scope) --
@@ -18,6 +18,9 @@
  * a quarter of the f32 rings' bytes, no scale, effect on transcripts not evaluated).
  * --enc-kv16 (no reference counterpart) keeps the encoder KV rings in IEEE half
  * (vh_set_enc_kv_fp16(ctx, 1): half of the f32 rings' bytes, effect on transcripts not evaluated).
+ * --enc-kv8 (no reference counterpart) keeps them in FP8 E4M3 instead (vh_set_enc_kv_dtype(ctx, 2): a
+ * quarter of the f32 rings' bytes, no scale, effect on transcripts not evaluated); giving both
+ * --enc-kv16 and --enc-kv8 is an error.
  * --kv-grow N (no reference counterpart) starts the decoder KV rings at N slots (clamped to 64..
  * window + 64) and lets them double as the stream's position needs them (vh_set_kv_grow(ctx, N):
  * lossless, the same tokens; one slot is 80 ms of audio).
@@ -51,7 +54,7 @@ static void drain(vh_stream_t *s, int *text_tokens, int alt) {
 int main(int argc, char **argv) {
     const char *model = NULL, *wav = NULL;
     float interval = -1.0f, alt_cutoff = -1.0f;
-    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, q8_gemmf = 0, kv_grow = 0;
+    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, enc_kv8 = 0, q8_gemmf = 0, kv_grow = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-d") && i + 1 < argc) model = argv[++i];
         else if (!strcmp(argv[i], "-i") && i + 1 < argc) wav = argv[++i];
@@ -62,6 +65,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--mx4")) mx4 = 1;
         else if (!strcmp(argv[i], "--kv8")) kv8 = 1;
         else if (!strcmp(argv[i], "--enc-kv16")) enc_kv16 = 1;
+        else if (!strcmp(argv[i], "--enc-kv8")) enc_kv8 = 1;
         else if (!strcmp(argv[i], "--q8-gemmf")) q8_gemmf = 1;
         else if (!strcmp(argv[i], "--kv-grow") && i + 1 < argc) kv_grow = atoi(argv[++i]);
         else {
@@ -69,9 +73,13 @@ int main(int argc, char **argv) {
             break;
         }
     }
+    if (enc_kv16 && enc_kv8) {
+        fprintf(stderr, "%s: --enc-kv16 and --enc-kv8 exclude each other\n", argv[0]);
+        model = NULL;
+    }
     if (!model || !wav || kv_grow < 0 || (alt_cutoff != -1.0f && (alt_cutoff < 0 || alt_cutoff > 1))) {
         fprintf(stderr, "usage: %s -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms] "
-                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16] [--q8-gemmf] [--kv-grow slots]\n",
+                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8] [--q8-gemmf] [--kv-grow slots]\n",
                 argv[0]);
         return 2;
     }
@@ -89,6 +97,7 @@ int main(int argc, char **argv) {
     }
     if (kv8 && vh_set_kv_dtype(ctx, 2)) return 1;
     if (enc_kv16 && vh_set_enc_kv_fp16(ctx, 1)) return 1;
+    if (enc_kv8 && vh_set_enc_kv_dtype(ctx, 2)) return 1;
     if (kv_grow && vh_set_kv_grow(ctx, kv_grow)) return 1;
     if (delay_ms > 0 && vh_set_delay(ctx, delay_ms)) return 1;
     vh_stream_t *s = vh_stream_init(ctx);

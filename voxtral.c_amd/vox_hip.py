@@ -124,6 +124,7 @@ EXPORTS = [
     "vox_hip_model_set_kv_dtype", "vox_hip_stream_kv_dtype", "vox_hip_stream_read_kv", "vox_hip_kv8_convert",
     "vox_hip_model_set_enc_kv_fp16", "vox_hip_stream_enc_kv_fp16", "vox_hip_stream_read_enc_kv",
     "vox_hip_stream_enc_kv_bytes", "vox_hip_stream_enc_paths",
+    "vox_hip_model_set_enc_kv_dtype", "vox_hip_stream_enc_kv_dtype",
     "vox_hip_model_set_kv_grow", "vox_hip_stream_kv_slots", "vox_hip_stream_kv_bytes",
     "vox_hip_stream_kv_grow_stats", "vox_hip_stream_reserve_kv", "vox_hip_batch_kv_grow_stats",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
@@ -178,6 +179,7 @@ def lib():
         "vox_hip_stream_read_kv": (I, [P, I, I, I, P, P]),
         "vox_hip_model_set_enc_kv_fp16": (I, [P, I]), "vox_hip_stream_enc_kv_fp16": (I, [P]),
         "vox_hip_stream_read_enc_kv": (I, [P, I, I, I, P, P]),
+        "vox_hip_model_set_enc_kv_dtype": (I, [P, I]), "vox_hip_stream_enc_kv_dtype": (I, [P]),
         "vox_hip_stream_enc_kv_bytes": (ctypes.c_longlong, [P]),
         "vox_hip_stream_enc_paths": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_model_set_kv_grow": (I, [P, I]), "vox_hip_stream_kv_slots": (I, [P]),
@@ -426,6 +428,13 @@ class Model:
         if lib().vox_hip_model_set_enc_kv_fp16(self.h, int(on)) != 0:
             _err("set_enc_kv_fp16")
 
+    def set_enc_kv_dtype(self, dtype: int):
+        """vox_hip_model_set_enc_kv_dtype: the encoder K/V ring element of streams created
+        afterwards: 0 f32, 1 IEEE half, 2 FP8 E4M3 (a quarter of the f32 rings' bytes, no scale;
+        f32 arithmetic; quality not evaluated)"""
+        if lib().vox_hip_model_set_enc_kv_dtype(self.h, int(dtype)) != 0:
+            _err("set_enc_kv_dtype")
+
     def set_kv_grow(self, slots0: int):
         """vox_hip_model_set_kv_grow: streams created afterwards start with decoder K/V rings of
         slots0 slots (clamped to [64, dec_window + 64]) that double as their position needs them,
@@ -584,6 +593,11 @@ class Stream:
         return bool(lib().vox_hip_stream_enc_kv_fp16(self.h))
 
     @property
+    def enc_kv_dtype(self) -> int:
+        """the stream's encoder K/V ring element: 0 f32, 1 IEEE half, 2 FP8 E4M3 (Model.set_enc_kv_dtype)"""
+        return int(lib().vox_hip_stream_enc_kv_dtype(self.h))
+
+    @property
     def enc_kv_bytes(self) -> int:
         """bytes of the stream's encoder K and V rings together"""
         return int(lib().vox_hip_stream_enc_kv_bytes(self.h))
@@ -598,14 +612,17 @@ class Stream:
     def read_enc_kv(self, layer: int, first: int, n: int, decoded: bool = False):
         """vox_hip_stream_read_enc_kv: the K and V ring elements of logical encoder positions
         [first, first + n) of one encoder layer, [n, enc_kv_heads * enc_head_dim] each: raw
-        (float32, or float16 on a half stream) or, decoded, widened to float32"""
-        dt = np.float16 if self.enc_kv_fp16 else np.float32
+        (float32, float16 on a half stream, uint8 E4M3 codes on an FP8 stream) or, decoded,
+        widened to float32 (exactly: kv8_decode for the codes)"""
+        dt = KV_NP_DTYPE[self.enc_kv_dtype]
         kvd = self.cfg.enc_kv_heads * self.cfg.enc_head_dim
         k, v = np.empty((n, kvd), dt), np.empty((n, kvd), dt)
         if lib().vox_hip_stream_read_enc_kv(self.h, int(layer), int(first), int(n), k.ctypes.data, v.ctypes.data) != 0:
             _err("read_enc_kv")
         if not decoded:
             return k, v
+        if dt is np.uint8:
+            return kv8_decode(k), kv8_decode(v)
         return k.astype(np.float32), v.astype(np.float32)
 
     def encode_mel(self, mel: np.ndarray) -> int:
@@ -862,6 +879,9 @@ class AudioSession(Session):
         super().__init__(stream, interval_s)
         self.mel = Mel(stream, 32 * RAW_AUDIO_LENGTH_PER_TOK)
         self.real_samples = 0
+        # the stream itself: a caller may put a wrapper with the encode / decode calls in self.s
+        # (bench.py --streaming times them that way), and the right pad needs the stream's delay
+        self.stream = stream
 
     def feed_samples(self, samples: np.ndarray, stop_at_eos=True):
         self.mel.feed(samples)
@@ -869,7 +889,7 @@ class AudioSession(Session):
         self.feed(self.mel, stop_at_eos)
 
     def flush_samples(self, stop_at_eos=True):
-        pad = right_pad_samples(self.real_samples, self.s.delay_tokens)
+        pad = right_pad_samples(self.real_samples, self.stream.delay_tokens)
         self.mel.feed(np.zeros(pad, np.float32))
         self.flush(self.mel, stop_at_eos)
 
@@ -1126,6 +1146,7 @@ def host_lib():
         "vh_sched_set_step_cap": (None, [P, I]), "vh_stream_pending": (I, [P]),
         "vh_stream_set_delay": (I, [P, I]), "vh_stream_delay_ms": (I, [P]),
         "vh_set_enc_kv_fp16": (I, [P, I]), "vh_stream_enc_kv_fp16": (I, [P]),
+        "vh_set_enc_kv_dtype": (I, [P, I]), "vh_stream_enc_kv_dtype": (I, [P]),
         "vh_set_kv_grow": (I, [P, I]), "vh_stream_kv_slots": (I, [P]),
         "vh_sched_debug_fail_next_encode": (None, [P]),
         "vh_stream_adapter_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
@@ -1156,6 +1177,12 @@ class HostCtx:
         """vh_set_kv_grow: streams initialised afterwards start with decoder rings of slots0 slots"""
         if host_lib().vh_set_kv_grow(self.h, int(slots0)) != 0:
             _herr("vh_set_kv_grow")
+
+    def set_enc_kv_dtype(self, dtype: int):
+        """vh_set_enc_kv_dtype: the encoder K/V ring element of streams initialised afterwards
+        (0 f32, 1 IEEE half, 2 FP8 E4M3)"""
+        if host_lib().vh_set_enc_kv_dtype(self.h, int(dtype)) != 0:
+            _herr("vh_set_enc_kv_dtype")
 
     def close(self):
         if self.h:
