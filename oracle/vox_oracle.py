@@ -74,8 +74,16 @@ def lib():
     return _lib
 
 
-def set_threads(n: int):
+def set_threads(n: int) -> int:
+    """n threads for the row-parallel loops (an OpenMP team) and for sgemm (OpenBLAS's own pool),
+    at most half the CPUs this process may run on: the two pools take turns within every linear
+    layer and the idle one busy-waits, so n threads need 2n CPUs -- with fewer they preempt each
+    other (16 threads on a 16-CPU host: the chunked full-size encoder runs 17x slower than with
+    8, and slower than with 1).  Returns the count in use."""
+    if n > 1:
+        n = max(1, min(n, len(os.sched_getaffinity(0)) // 2))
     lib().vo_set_threads(n)
+    return n
 
 
 def set_no_compaction(on: bool):
