@@ -42,6 +42,10 @@ void vh_free(vh_ctx_t *ctx);
 const vox_hip_config_t *vh_config(const vh_ctx_t *ctx);
 /* vox_set_delay (voxtral.c:1681-1687): clamp to 80..2400 ms, 80 ms per token */
 int vh_set_delay(vh_ctx_t *ctx, int delay_ms);
+/* Before vh_load: models loaded from now on also get the lossless wpack13 fragment planes that
+ * the batched decode step of 2..32 streams then reads instead of the bf16 fragment copies
+ * (vox_hip_set_wpack_batch, voxtral_hip.h: the same tokens; off by default).  Returns 0. */
+int vh_set_wpack_batch(int on);
 const char *vh_last_error(void);
 
 /* vox_stream_init (voxtral.c:1242-1286) */

@@ -253,6 +253,27 @@ int vox_hip_model_wmx4_batch_stats(const vox_hip_model_t *m, long long out4[4]);
  * Returns 0; -1 (vox_hip_last_error) on a bad shape, or with fmt = 1 for a matrix the wmx4 scan
  * refuses. */
 int vox_hip_skinny_wmx4(int N, int K, const uint16_t *W, const float *x, int nb, float *y, int fmt, int head);
+/* wpack13 for the batched MFMA step (opt-in; process-wide, read at vox_hip_model_create;
+ * VOX_HIP_WPACK_BATCH=1 gives the initial value; off by default).  When on, every bf16 decoder
+ * matrix that gets wpack13 GEMV planes (Q|K|V, wo, W1|W3, W2 per layer, the LM head) also gets a
+ * wpack13 fragment plane (csrc/vox_wpack.h: the same 13-bit codes and D in the MFMA A operand's
+ * order, 1664 B per 16 rows x 64 k against the copy's 2048), built on the host.  The batched
+ * step's projections and LM head then stream that plane instead of the 16-bit fragment-major
+ * copy and form the very bf16 fragments in registers (packed 16-bit integer arithmetic): same
+ * waves, splits, slabs and summation order, so the step's logits and ids are bit-identical to
+ * the step on the bf16 copies, and the model's values are unchanged.  A tensor outside the
+ * format's window keeps only its bf16 copy; Q8 models and VOX_HIP_WPACK=0 build nothing; the
+ * bf16 fragment copies stay (prefill reads them).  Prefill, the wide step, the encoder, the
+ * R-row GEMV step and the single-stream step are untouched.
+ * vox_hip_set_wpack_batch returns 0. */
+int vox_hip_set_wpack_batch(int on);
+int vox_hip_wpack_batch(void);
+/* out4: as vox_hip_model_wmx4_batch_stats, for the wpack13 fragment planes. */
+int vox_hip_model_wpack_batch_stats(const vox_hip_model_t *m, long long out4[4]);
+/* Test entry: vox_hip_skinny_wmx4 for the wpack13 fragment plane: fmt = 0 streams the bf16
+ * fragment-major copy, fmt = 1 the wpack13 fragment plane in the matrix's own D.  Returns 0; -1
+ * (vox_hip_last_error) on a bad shape, or with fmt = 1 for a matrix outside the wpack13 window. */
+int vox_hip_skinny_wpack(int N, int K, const uint16_t *W, const float *x, int nb, float *y, int fmt, int head);
 /* Arithmetic of the M > 1 GEMMs (encoder, adapter, prefill; no reference counterpart: the
  * CPU path's cblas_sgemm, voxtral_kernels.c:197-240, is f32): every f32 activation is split
  * into bf16 planes that multiply the exact bf16 weights on MFMA.  planes = 3 (hi + mid + lo,
@@ -602,6 +623,16 @@ int vox_hip_batch_gemv_wmx4_stats(const vox_hip_batch_t *b, long long out4[4]);
  * (vox_hip_last_error) when the model has no fragment plane, or between
  * vox_hip_batch_begin_rows and vox_hip_batch_finish. */
 int vox_hip_batch_set_wmx4(vox_hip_batch_t *b, int on);
+/* The same switch for the wpack13 fragment planes (vox_hip_set_wpack_batch): a batch on a model
+ * with such planes starts with it on; otherwise it is off and cannot be turned on.  Per tensor
+ * the step streams the wmx4 plane where that mode is on and the tensor has one, else the wpack13
+ * plane where this mode is on and the tensor has one, else the bf16 copy: the same bits every
+ * way.  Each combination of the two modes keeps step graphs of its own.  Returns 0; -1
+ * (vox_hip_last_error) when the model has no such plane, or between vox_hip_batch_begin_rows
+ * and vox_hip_batch_finish. */
+int vox_hip_batch_set_wpack(vox_hip_batch_t *b, int on);
+/* The switch in effect: 1 or 0; -1 for a null batch. */
+int vox_hip_batch_wpack(const vox_hip_batch_t *b);
 /* Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
  * bucket >= R (unused rows zero), from the raw rows (packed = 0), the wpack13 planes (1) or
  * the wmx4 plane built from W (2, as vox_hip_gemv_wpack).  Returns flags: bit 0 the wpack13

@@ -517,7 +517,12 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
-    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "skmx4")) {
+    if (getenv("VOX_KB_ONLY") && (!strcmp(getenv("VOX_KB_ONLY"), "skmx4") || !strcmp(getenv("VOX_KB_ONLY"), "skp13"))) {
+        // VOX_KB_ONLY=skp13: the same case for the wpack13 fragment planes (vox_wpack.h, 13 stored
+        // bits per weight): unrounded seeded weights in their own D, no convert probe
+        const bool p13 = !strcmp(getenv("VOX_KB_ONLY"), "skp13");
+        const char* const tag = p13 ? "skp13" : "skmx4";
+        const char* const fn = p13 ? "p13 " : "mx4 ";
         // wmx4 fragment planes (vox_wmx4.h, 4.5 stored bits per weight) against the bf16
         // fragment-major copies in the batched step's own launches: QKV (k_skl / k_skl2 with the
         // RMSNorm scale), wo and W2 (k_skl / k_skl2), W1|W3 (k_sklx with the SwiGLU epilogue)
@@ -527,7 +532,7 @@ int main(int argc, char** argv) {
         // and per shape and row count the outputs of both formats on a seeded random rounded
         // matrix, bit for bit.  VOX_KB_SKMX4_SHAPES=w13 (or any list of qkv,wo,w13,w2,lm) limits
         // the shapes.
-        {
+        if (!p13) {
             const int ns = 2 * VOX_WMX4_MAX_E + 1;
             std::vector<uint8_t> hs(ns);
             for (int i = 0; i < ns; i++) hs[i] = (uint8_t)(127 - VOX_WMX4_MAX_E + i);
@@ -572,21 +577,23 @@ int main(int argc, char** argv) {
         for (S o : {S{"qkv", DQ + 2 * DKV, D, 1, &wqkv, DQ + 2 * DKV}, S{"wo", D, DQ, 0, &wo, D}, S{"w13", 2 * DH, D, 2, &w13, 2 * DH},
                     S{"w2", D, DH, 0, &w2, D}, S{"lm", V, D, 3, &lm1, 32768}}) {
             if (only && !strstr(only, o.n)) continue;
-            const size_t fragb = (size_t)vox_wmx4_frag_words(o.N, o.K) * 4;
+            const size_t fragb = (size_t)(p13 ? vox_wpack13_frag_words(o.N, o.K) : vox_wmx4_frag_words(o.N, o.K)) * 4;
             size_t outb = 0;   // bytes of the output compared
-            auto run = [&](const void* W, int mx4, int nb, int rows) {
+            int p13d = 0;      // D of the plane the p13 launches read
+            auto run = [&](const void* W, int fmt, int nb, int rows) {
+                const int mx4 = fmt && !p13, p13c = fmt && p13 ? 112 + p13d : 0;
                 if (o.kind == 3) {
                     outb = (size_t)nb * rows * 4;
-                    if (nb > 16) CK(launch_gemm_skf2(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4));
-                    else CK(launch_gemm_skf(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4));
+                    if (nb > 16) CK(launch_gemm_skf2(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4, p13c));
+                    else CK(launch_gemm_skf(xp, o.K, W, nullptr, rows, nb, Cs, rows, st, mx4, p13c));
                 } else if (o.kind == 2) {
                     SklFused f;
                     f.ssq_in = ssq; f.nsl = 12; f.eps = 1e-5f; f.part = sp; f.ticket = tick; f.planes = xo;
                     outb = (size_t)Z * 3 * 16 * (rows / 2) * 2;
-                    CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, xp, o.K, W, rows, nb, f, st, mx4));
+                    CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, xp, o.K, W, rows, nb, f, st, mx4, p13c));
                 } else {
                     outb = (size_t)((nb + 15) / 16) * skl_splits(o.K, rows) * 16 * rows * 4;
-                    CK(launch_gemm_skl(xp, o.K, W, nullptr, rows, nb, sp, st, o.kind == 1 ? ssq : nullptr, o.kind == 1 ? 12 : 0, 1e-5f, 1, mx4));
+                    CK(launch_gemm_skl(xp, o.K, W, nullptr, rows, nb, sp, st, o.kind == 1 ? ssq : nullptr, o.kind == 1 ? 12 : 0, 1e-5f, 1, mx4, p13c));
                 }
             };
             {   // bit check on seeded random weights (uniform, std 1/sqrt(3072)), rounded, and random rows
@@ -600,16 +607,26 @@ int main(int argc, char** argv) {
                     memcpy(&u, &f, 4);
                     v = (uint16_t)(u >> 16);
                 }
-                vox_wmx4_round_(hw.data(), rows, o.K, hw.data());
-                if (!vox_wmx4_scan_(hw.data(), rows, o.K)) { printf("%s: rounded weights fail the scan\n", o.n); return 1; }
+                int emin, emax;
+                if (p13) {
+                    if (!vox_wpack13_scan_(hw.data(), hw.size(), &emin, &emax, &p13d)) { printf("%s: weights outside the wpack13 window\n", o.n); return 1; }
+                } else {
+                    vox_wmx4_round_(hw.data(), rows, o.K, hw.data());
+                    if (!vox_wmx4_scan_(hw.data(), rows, o.K)) { printf("%s: rounded weights fail the scan\n", o.n); return 1; }
+                }
                 std::vector<float> hx((size_t)Z * 16 * o.K);
                 for (auto& v : hx) v = rnd();
                 CK(hipMemcpy(xf, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
                 CK(launch_split_fplanes(xf, Z * 16, o.K, xp, st));
-                std::vector<uint32_t> nib((size_t)rows * o.K / 8), pl((size_t)vox_wmx4_frag_words(rows, o.K));
+                std::vector<uint32_t> nib((size_t)rows * o.K / 8),
+                    pl((size_t)(p13 ? vox_wpack13_frag_words(rows, o.K) : vox_wmx4_frag_words(rows, o.K)));
                 std::vector<uint8_t> scl((size_t)rows * o.K / 32);
-                vox_wmx4_pack_(hw.data(), rows, o.K, nib.data(), scl.data());
-                vox_wmx4_frag_layout_(nib.data(), scl.data(), rows, o.K, pl.data());
+                if (p13) {
+                    vox_wpack13_frag_layout_(hw.data(), rows, o.K, p13d, pl.data());
+                } else {
+                    vox_wmx4_pack_(hw.data(), rows, o.K, nib.data(), scl.data());
+                    vox_wmx4_frag_layout_(nib.data(), scl.data(), rows, o.K, pl.data());
+                }
                 uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
                 uint16_t* df = (uint16_t*)dmalloc(hw.size() * 2, 0);
                 uint32_t* dp = (uint32_t*)dmalloc(pl.size() * 4, 0);
@@ -633,12 +650,13 @@ int main(int argc, char** argv) {
                         for (size_t i = 0; i < outb / 4; i++, cnt++) sum += fabs((double)((const float*)o0.data())[i]);
                     size_t nz = 0;   // (W1|W3: the outputs are the SwiGLU planes, bf16 bits)
                     for (size_t i = 0; i < outb; i++) nz += o0[i] != 0;
-                    printf("skmx4 %-4s check nb%-2d: %d x %d, %zu output bytes (%zu nonzero), mean |y| %.4g: %s\n", o.n, nb, rows, o.K,
+                    printf("%s %-4s check nb%-2d: %d x %d, %zu output bytes (%zu nonzero), mean |y| %.4g: %s\n", tag, o.n, nb, rows, o.K,
                            outb, nz, cnt ? sum / cnt : 0.0, memcmp(o0.data(), o1.data(), outb) ? "BITS DIFFER" : "same bits");
                     fflush(stdout);
                 }
                 CK(hipFree(dw)); CK(hipFree(df)); CK(hipFree(dp));
                 CK(hipMemsetD32(xp, 0x3c003c01u, (size_t)Z * 3 * 16 * DH * 2 / 4));
+                p13d = 0;  // the constant planes below: every byte 0x78 decodes to a normal bf16 under D = 0
             }
             // timing: constant planes (values do not matter; every byte 0x78 is a valid scale and a
             // valid nibble pair); the bf16 launches read the per-layer buffers as fragment copies
@@ -656,10 +674,10 @@ int main(int argc, char** argv) {
                 t.bytes[1] = (double)fragb;
                 for (int r = 0; r < 3; r++) {
                     char nm[96];
-                    snprintf(nm, sizeof nm, "skmx4 %-4s nb%-2d bf16 run %d", o.n, nb, r);
+                    snprintf(nm, sizeof nm, "%s %-4s nb%-2d bf16 run %d", tag, o.n, nb, r);
                     t.us[0][r] = timeit([&] { run((*o.w)[layer++ % (int)o.w->size()], 0, nb, o.N); }, it, st);
                     add(nm, t.us[0][r], t.bytes[0]);
-                    snprintf(nm, sizeof nm, "skmx4 %-4s nb%-2d mx4  run %d", o.n, nb, r);
+                    snprintf(nm, sizeof nm, "%s %-4s nb%-2d %s run %d", tag, o.n, nb, fn, r);
                     t.us[1][r] = timeit([&] { run(mx[layer++ % nl], 1, nb, o.N); }, it, st);
                     add(nm, t.us[1][r], t.bytes[1]);
                 }
@@ -667,8 +685,8 @@ int main(int argc, char** argv) {
             }
             for (int l = 0; l < nl; l++) CK(hipFree(mx[l]));
         }
-        printf("\nskmx4 medians of three: us per launch, MB streamed, fraction of 8 TB/s\n");
-        printf("%-10s %9s %8s %6s   %9s %8s %6s   %s\n", "", "bf16 us", "MB", "of 8T", "mx4 us", "MB", "of 8T", "mx4 / bf16");
+        printf("\n%s medians of three: us per launch, MB streamed, fraction of 8 TB/s\n", tag);
+        printf("%-10s %9s %8s %6s   %6sus %8s %6s   %s/ bf16\n", "", "bf16 us", "MB", "of 8T", fn, "MB", "of 8T", fn);
         for (T& t : table) {
             double m[2];
             for (int f = 0; f < 2; f++) {

@@ -153,9 +153,12 @@ struct EncLayerD {
 };
 // wpack13 copy of a bf16 matrix for the single-stream GEMV (vox_wpack.h): 13 bits per
 // weight, decoded without loss.  main == null: the tensor stays raw.
+// frag: its wpack13 fragment plane for the batched MFMA step (vox_hip_set_wpack_batch), the same
+// codes and d; null: the step reads the tensor's bf16 fragment-major copy.
 struct WPackD {
     uint8_t *main, *side;
     int d;
+    uint8_t* frag;
 };
 // wmx4 plane of a bf16 matrix that is MXFP4-valued (vox_wmx4.h), for the single-stream GEMV:
 // 5 bits per weight, decoded without loss.  null: none (the tensor streams as wpack13 or raw).
@@ -212,6 +215,8 @@ struct vox_hip_model {
     vox_hip_wmx4_stats_t mstats;
     int wmx4_batch;                // vox_hip_wmx4_batch() at creation: fragment planes beside the GEMV planes
     long long fstats[4];           // fragment planes: tensors, plane bytes, their bf16 bytes, host microseconds
+    int wpack_batch;               // vox_hip_wpack_batch() at creation: wpack13 fragment planes beside the GEMV planes
+    long long pfstats[4];          // wpack13 fragment planes: as fstats
     int gemmf_q8;                  // vox_hip_gemmf_q8() at creation: k_gemmf streams the int8 fragment copies of Q8 tensors
     long long n_gemmf_q8;          // k_gemmf launches on int8 fragments (vox_hip_model_gemmf_q8_stats)
     int begun_calls;               // batched calls of this model between begin_rows and finish (their slots read ada_scale)
@@ -304,8 +309,11 @@ static void par_range(long long n, F f) {
 // The wpack13 planes of a bf16 matrix whose rows are in device order (host copy), for
 // k_gemv's row groups of this shape.  A tensor outside the format's window (vox_wpack.h),
 // or of a shape launch_gemv does not take, stays raw: P->main stays null.
-static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const uint16_t* w, int rows, int K, int swiglu) {
-    P->main = P->side = nullptr;
+// fstats != null (and rows % 16 == 0, K % 64 == 0): the tensor's fragment plane for the batched
+// step as well, in the same codes and D.
+static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const uint16_t* w, int rows, int K, int swiglu,
+                      long long* fstats = nullptr) {
+    P->main = P->side = P->frag = nullptr;
     P->d = 0;
     const size_t n = (size_t)rows * K;
     auto raw = [&] { S.raw_tensors++; S.raw_bytes += (long long)n * 2; return 0; };
@@ -336,6 +344,20 @@ static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const ui
     S.packed_bytes += (long long)(mainw + sidew) * 4;
     S.packed_raw_bytes += (long long)n * 2;
     S.pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const size_t fwords = fstats ? (size_t)vox_wpack13_frag_words(rows, K) : 0;
+    if (fwords) {
+        const auto t1 = std::chrono::steady_clock::now();
+        std::vector<uint32_t>().swap(hm);
+        std::vector<uint32_t>().swap(hs);
+        std::vector<uint32_t> fp(fwords);
+        par_range(rows / 16, [&](long long g0, long long g1) { vox_wpack13_frag_groups(w, g0, g1, K, d, fp.data()); });
+        CK(dalloc(&P->frag, fwords * 4));
+        if (upload(P->frag, fp.data(), fwords * 4)) return -1;
+        fstats[0]++;
+        fstats[1] += (long long)fwords * 4;
+        fstats[2] += (long long)n * 2;
+        fstats[3] += (long long)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() * 1000.0);
+    }
     return 0;
 }
 static void wpack_args(GemvArgs& a, const WPackD& P) {
@@ -376,6 +398,21 @@ extern "C" int vox_hip_set_wmx4_batch(int on) {
     return 0;
 }
 extern "C" int vox_hip_wmx4_batch(void) { return wmx4_batch_mode(); }
+// wpack13 fragment planes for the batched step, for models created from now on;
+// VOX_HIP_WPACK_BATCH=1 gives the initial value
+static int g_wpack_batch = -1;
+static int wpack_batch_mode() {
+    if (g_wpack_batch < 0) {
+        const char* e = getenv("VOX_HIP_WPACK_BATCH");
+        g_wpack_batch = e && atoi(e) == 1 ? 1 : 0;
+    }
+    return g_wpack_batch;
+}
+extern "C" int vox_hip_set_wpack_batch(int on) {
+    g_wpack_batch = on ? 1 : 0;
+    return 0;
+}
+extern "C" int vox_hip_wpack_batch(void) { return wpack_batch_mode(); }
 // k_gemmf over the int8 fragment copies of Q8 tensors, for models created from now on
 // (include/voxtral_hip.h); VOX_HIP_GEMMF_Q8=1 gives the initial value
 static int g_gemmf_q8 = -1;
@@ -625,6 +662,9 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
         const char* e = getenv("VOX_HIP_WPACK");
         m->wpack = (e && atoi(e) == 0) ? 0 : 1;
     }
+    m->wpack_batch = m->wpack ? wpack_batch_mode() : 0;
+    memset(m->pfstats, 0, sizeof m->pfstats);
+    long long* const pfst = m->wpack_batch ? m->pfstats : nullptr;
     const vox_hip_config_t& c = *cfg;
     const int ED = c.enc_dim, EQ = c.enc_heads * c.enc_head_dim, EKV = c.enc_kv_heads * c.enc_head_dim;
     const int EH = c.enc_hidden;
@@ -685,7 +725,7 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     // wpack13 copies of the bf16 matrices the single-stream decode step streams (made here,
     // not in the first step); the raw copies stay for every other path
     if (!w->tok_emb_s) {
-        TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0));
+        TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0, pfst));
         TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &m->mlm, (const uint16_t*)h_tok, c.vocab, DD, 0, fst));
     }
     rnd[0] = std::vector<uint16_t>();
@@ -714,11 +754,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
             memcpy(hrows.data(), h_wq, (size_t)DQ * DD * 2);
             memcpy(hrows.data() + (size_t)DQ * DD, h_wk, (size_t)DKV * DD * 2);
             memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, h_wv, (size_t)DKV * DD * 2);
-            TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0));
+            TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0, pfst));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mqkv, hrows.data(), DQ + 2 * DKV, DD, 0, fst));
         }
         if (!L.so) {
-            TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0));
+            TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0, pfst));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mo, (const uint16_t*)h_wo, DD, DQ, 0, fst));
         }
         if (!L.s13) {
@@ -728,11 +768,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
                 memcpy(hrows.data() + 2 * g * grp, (const uint16_t*)h_w1 + g * grp, grp * 2);
                 memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)h_w3 + g * grp, grp * 2);
             }
-            TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1));
+            TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1, pfst));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m13, hrows.data(), 2 * DH, DD, 1, fst));
         }
         if (!L.s2) {
-            TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0));
+            TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0, pfst));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m2, (const uint16_t*)h_w2, DD, DH, 0, fst));
         }
         TRYH(dalloc(&L.attn_norm, DD));
@@ -766,10 +806,10 @@ extern "C" void vox_hip_model_free(vox_hip_model_t* m) {
         dfree(L.wqkv); dfree(L.wo); dfree(L.w13); dfree(L.w2);
         dfree(L.sqkv); dfree(L.so); dfree(L.s13); dfree(L.s2);
         dfree(L.attn_norm); dfree(L.ffn_norm);
-        for (WPackD* P : {&L.pqkv, &L.po, &L.p13, &L.p2}) { dfree(P->main); dfree(P->side); }
+        for (WPackD* P : {&L.pqkv, &L.po, &L.p13, &L.p2}) { dfree(P->main); dfree(P->side); dfree(P->frag); }
         for (WMx4D* M : {&L.mqkv, &L.mo, &L.m13, &L.m2}) { dfree(M->plane); dfree(M->frag); }
     }
-    dfree(m->plm.main); dfree(m->plm.side); dfree(m->mlm.plane); dfree(m->mlm.frag);
+    dfree(m->plm.main); dfree(m->plm.side); dfree(m->plm.frag); dfree(m->mlm.plane); dfree(m->mlm.frag);
     for (auto& F : m->dfrag) {
         dfree(F.wqkv); dfree(F.wo); dfree(F.w13); dfree(F.w2);
     }
@@ -799,6 +839,12 @@ extern "C" int vox_hip_model_wmx4_stats(const vox_hip_model_t* m, vox_hip_wmx4_s
 extern "C" int vox_hip_model_wmx4_batch_stats(const vox_hip_model_t* m, long long out4[4]) {
     if (!m || !out4) return set_err("wmx4_batch_stats: null argument");
     memcpy(out4, m->fstats, sizeof m->fstats);
+    return 0;
+}
+
+extern "C" int vox_hip_model_wpack_batch_stats(const vox_hip_model_t* m, long long out4[4]) {
+    if (!m || !out4) return set_err("wpack_batch_stats: null argument");
+    memcpy(out4, m->pfstats, sizeof m->pfstats);
     return 0;
 }
 
@@ -3453,15 +3499,13 @@ extern "C" int vox_hip_gemv_q8(int rows, int K, const int8_t* W, const float* sc
 // launchers (include/voxtral_hip.h): planes by launch_split_fplanes, then launch_gemm_skl with
 // pair = 1 and its slabs summed in slab order on the host (head = 0), or launch_gemm_skf /
 // launch_gemm_skf2 (head = 1); fmt = 1 streams the wmx4 fragment plane.
-extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float* x, int nb, float* y, int fmt, int head) {
+// src: 0 the bf16 fragment copy, 1 the wmx4 fragment plane, 2 the wpack13 fragment plane in D = d
+static int skinny_entry(const char* who, int N, int K, const uint16_t* W, const float* x, int nb, float* y, int src, int head,
+                        int d) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
-    if (!W || !x || !y) return set_err("skinny_wmx4: null argument");
-    if (nb < 1 || nb > VOX_MAX_BATCH) return set_err("skinny_wmx4: %d rows (1..%d)", nb, VOX_MAX_BATCH);
-    if ((fmt != 0 && fmt != 1) || (head != 0 && head != 1)) return set_err("skinny_wmx4: fmt and head are 0 or 1");
-    if (N < 64 || N % 64 || K < 64 || K % 64 || (!head && !skl_splits(K, N)))
-        return set_err("skinny_wmx4: shape %d x %d is not a skinny GEMM shape", N, K);
-    if (fmt && !vox_wmx4_scan_(W, N, K))
-        return set_err("skinny_wmx4: the matrix is not MXFP4-valued inside the exponent window");
+    if (nb < 1 || nb > VOX_MAX_BATCH) return set_err("%s: %d rows (1..%d)", who, nb, VOX_MAX_BATCH);
+    if (!head && !skl_splits(K, N)) return set_err("%s: shape %d x %d is not a skinny GEMM shape", who, N, K);
+    const int fmt = src == 1, p13c = src == 2 ? 112 + d : 0;
     if (twin_init()) return -1;
     const int S = head ? 1 : skl_splits(K, N), Z = 2;
     uint8_t *dW = nullptr, *dF = nullptr;
@@ -3478,6 +3522,12 @@ extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float*
             par_range(N / 16, [&](long long g0, long long g1) { vox_wmx4_frag_groups(nib.data(), scl.data(), g0, g1, K, fp.data()); });
             CK(dalloc(&dF, words * 4));
             if (upload(dF, fp.data(), words * 4)) return -1;
+        } else if (p13c) {
+            const size_t words = (size_t)vox_wpack13_frag_words(N, K);
+            std::vector<uint32_t> fp(words);
+            par_range(N / 16, [&](long long g0, long long g1) { vox_wpack13_frag_groups(W, g0, g1, K, d, fp.data()); });
+            CK(dalloc(&dF, words * 4));
+            if (upload(dF, fp.data(), words * 4)) return -1;
         } else {
             CK(dalloc(&dW, (size_t)N * K * 2));
             if (upload(dW, W, (size_t)N * K * 2) || frag_copy(&dF, dW, N, K, 0)) return -1;
@@ -3488,11 +3538,11 @@ extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float*
         if (upload(dx, x, (size_t)nb * K * 4)) return -1;  // (dalloc zeroes: the planes of rows nb.. are 0)
         CK(launch_split_fplanes(dx, nb, K, dxs, g_twin_st));
         if (!head)
-            CK(launch_gemm_skl(dxs, K, dF, nullptr, N, nb, dout, g_twin_st, nullptr, 0, 0.f, 1, fmt));
+            CK(launch_gemm_skl(dxs, K, dF, nullptr, N, nb, dout, g_twin_st, nullptr, 0, 0.f, 1, fmt, p13c));
         else if (nb > SK_ROWS)
-            CK(launch_gemm_skf2(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt));
+            CK(launch_gemm_skf2(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt, p13c));
         else
-            CK(launch_gemm_skf(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt));
+            CK(launch_gemm_skf(dxs, K, dF, nullptr, N, nb, dout, N, g_twin_st, fmt, p13c));
         CK(hipStreamSynchronize(g_twin_st));
         CK(hipMemcpy(out.data(), dout, nout * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -3515,6 +3565,27 @@ extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float*
         }
     }
     return 0;
+}
+
+extern "C" int vox_hip_skinny_wmx4(int N, int K, const uint16_t* W, const float* x, int nb, float* y, int fmt, int head) {
+    if (!W || !x || !y) return set_err("skinny_wmx4: null argument");
+    if ((fmt != 0 && fmt != 1) || (head != 0 && head != 1)) return set_err("skinny_wmx4: fmt and head are 0 or 1");
+    if (N < 64 || N % 64 || K < 64 || K % 64) return set_err("skinny_wmx4: shape %d x %d is not a skinny GEMM shape", N, K);
+    if (fmt && !vox_wmx4_scan_(W, N, K))
+        return set_err("skinny_wmx4: the matrix is not MXFP4-valued inside the exponent window");
+    return skinny_entry("skinny_wmx4", N, K, W, x, nb, y, fmt, head, 0);
+}
+
+// The same for the wpack13 fragment plane (fmt = 1; fmt = 0: the bf16 fragment copy): the plane
+// in the tensor's own D, as the model builds it.  A matrix outside the format's window is refused.
+extern "C" int vox_hip_skinny_wpack(int N, int K, const uint16_t* W, const float* x, int nb, float* y, int fmt, int head) {
+    if (!W || !x || !y) return set_err("skinny_wpack: null argument");
+    if ((fmt != 0 && fmt != 1) || (head != 0 && head != 1)) return set_err("skinny_wpack: fmt and head are 0 or 1");
+    if (N < 64 || N % 64 || K < 64 || K % 64) return set_err("skinny_wpack: shape %d x %d is not a skinny GEMM shape", N, K);
+    int emin, emax, d = 0;
+    if (fmt && !vox_wpack13_scan_(W, (size_t)N * K, &emin, &emax, &d))
+        return set_err("skinny_wpack: the matrix is outside the wpack13 exponent window");
+    return skinny_entry("skinny_wpack", N, K, W, x, nb, y, fmt ? 2 : 0, head, d);
 }
 
 // Test entry: M rows x [M][K] against one Q8 matrix (Wq [N][K] int8, scales [N]) through the
@@ -3797,16 +3868,20 @@ struct vox_hip_batch {
     // step graphs [ring element type][slot bucket 1, 2, 4, 8, 16, 32][attention splits bucket]: their kernel
     // arguments point at the slot table and the batch's buffers only, so they stay valid as
     // streams come and go; captured again only when the model's rope table moves
-    // (wmx4: [3 wmx4 + element type], the two weight sources keep graphs of their own)
+    // (weight source: [3 (wmx4 + 2 wp13) + element type]: the bf16 copies, the wmx4 planes, the wpack13
+    // planes and both -- wmx4 where a tensor has one, else wpack13 -- keep graphs of their own)
     // [mixed]: the steps of a call in which a stream carries a delay of its own launch the per-slot
     // norm instances, so they keep graphs of their own beside the plain calls'
     // [mixed + 2 ragged]: likewise the steps of a call in which a stream's decoder rings are shorter
     // than window + slack (vox_hip_model_set_kv_grow) launch the ragged attention instances
-    hipGraphExec_t gexec[4][6][6][STEP_GRAPHS];
+    hipGraphExec_t gexec[4][12][6][STEP_GRAPHS];
     int grope_gen;
     // the MFMA step streams the wmx4 fragment planes of the tensors that have one
     // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
     int wmx4;
+    // likewise the wpack13 fragment planes (vox_hip_batch_set_wpack), for a tensor the wmx4 source
+    // does not cover
+    int wp13;
     // the R-row GEMV step (batch_step_gemv): steps whose slot bucket is <= gemv_rows take it
     // (0: off).  Its graphs [element type][bucket 1, 2, 4, 8][splits bucket] have keys of their own, so
     // the mode changes between calls without a capture being dropped.
@@ -4067,6 +4142,7 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
         if (r && model_gemv_q8_count(m) && batch_set_gemv_rows_q8(b, r)) return fail();
     }
     b->wmx4 = m->fstats[0] ? 1 : 0;
+    b->wp13 = m->pfstats[0] ? 1 : 0;
     // VOX_HIP_BATCH_GEMV_WMX4=1: the GEMV step's initial weight source (unset: 0; a model
     // without a wmx4 GEMV plane keeps 0)
     if (const char* e = getenv("VOX_HIP_BATCH_GEMV_WMX4"))
@@ -4081,20 +4157,31 @@ extern "C" vox_hip_batch_t* vox_hip_batch_create(vox_hip_model_t* m, int max_str
 }
 
 // the batched step's projections: k_skl, one burst of column groups per block
-// mx: the tensor's wmx4 fragment plane when the step streams it (null: Wf, the 16-bit copy)
-static hipError_t batch_gemm(const uint16_t* xs, int K, const void* Wf, const uint8_t* mx, const float* wscale, int N,
+// The weight source of one projection of the step: the tensor's wmx4 fragment plane (mx4), its
+// wpack13 fragment plane (p13c = 112 + D) or w = its 16-bit / int8 fragment-major copy.
+struct StepW {
+    const void* w;
+    int mx4, p13c;
+};
+static hipError_t batch_gemm(const uint16_t* xs, int K, const StepW& W, const float* wscale, int N,
                              int nb, float* part, hipStream_t st, const float* ssq = nullptr, int nsl = 0,
                              float eps = 0.f) {
-    return launch_gemm_skl(xs, K, mx ? mx : Wf, wscale, N, nb, part, st, ssq, nsl, eps, 1, mx != nullptr);
+    return launch_gemm_skl(xs, K, W.w, wscale, N, nb, part, st, ssq, nsl, eps, 1, W.mx4, W.p13c);
 }
 
 // one batched step over slots 0..nb-1 of the slot table (their input rows already in b->x)
 // mixed: the FFN norm's ada row per slot (k_resid_xw_fplanes_slot), from the slot table
 // ragged: each slot's ring capacity from b->dcaps (the ragged attention instances; the shared
 // cap and ring_off are not read)
-static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4, int mixed, int ragged) {
+// wmx4, wp13: the batch's weight-source modes; per tensor the wmx4 plane where the mode is on and
+// the tensor has one, else the wpack13 plane likewise, else the bf16 (or int8) copy
+static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4, int wp13, int mixed, int ragged) {
     vox_hip_model_t* m = b->m;
-    auto mx = [&](const WMx4D& M) -> const uint8_t* { return wmx4 ? M.frag : nullptr; };
+    auto src = [&](const void* Wf, const WMx4D& M, const WPackD& P) -> StepW {
+        if (wmx4 && M.frag) return StepW{M.frag, 1, 0};
+        if (wp13 && P.frag) return StepW{P.frag, 0, 112 + P.d};
+        return StepW{Wf, 0, 0};
+    };
     const vox_hip_config_t& c = m->c;
     const int DD = c.dec_dim, H = c.dec_heads, KVH = c.dec_kv_heads, hd = c.dec_head_dim;
     const int DQ = H * hd, DKV = KVH * hd, DH = c.dec_hidden;
@@ -4123,7 +4210,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
         // inverse RMS applied by the projection
         CK(launch_resid_xw_fplanes(b->x, nb, DD, L.attn_norm, nullptr, b->xp_d, b->part, l ? Sres : 0, nullptr,
                                    b->ssq, st));
-        CK(batch_gemm(b->xp_d, DD, F.wqkv, mx(L.mqkv), L.sqkv, DQ + 2 * DKV, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
+        CK(batch_gemm(b->xp_d, DD, src(F.wqkv, L.mqkv, L.pqkv), L.sqkv, DQ + 2 * DKV, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
         // RoPE + KV append + attention of every live slot, output into the wo planes (one
         // launch; past 256 keys the last key-range block of a kv head merges the partials)
         AttnFuse af;
@@ -4134,7 +4221,7 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
         } else {
             CK(launch_attn_batch_fused(hd, ap, af, nb, cap, c.dec_window, scale, H, KVH, splits, st, kvt));
         }
-        CK(batch_gemm(b->xp_q, DQ, F.wo, mx(L.mo), L.so, DD, nb, b->part, st));
+        CK(batch_gemm(b->xp_q, DQ, src(F.wo, L.mo, L.po), L.so, DD, nb, b->part, st));
         if (mixed)
             CK(launch_resid_xw_fplanes_slots(b->x, nb, DD, L.ffn_norm, b->slots, (size_t)l * DD, b->xp_d, b->part,
                                              skl_splits(DQ, DD), nullptr, b->ssq, st));
@@ -4148,14 +4235,14 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
             f.ssq_in = b->ssq; f.nsl = DD / 256; f.eps = c.dec_eps;
             f.part = b->part; f.ticket = b->ticket;
             f.planes = b->xp_h;
-            const uint8_t* m13 = mx(L.m13);
-            CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, b->xp_d, DD, m13 ? m13 : F.w13, 2 * DH, nb, f, st, m13 != nullptr));
+            const StepW w13 = src(F.w13, L.m13, L.p13);
+            CK(launch_gemm_sklx(SKX_PRO_SCALE, SKX_EPI_SWIGLU, b->xp_d, DD, w13.w, 2 * DH, nb, f, st, w13.mx4, w13.p13c));
         } else {
             // Q8: the int8 projection, then the SwiGLU rows
-            CK(batch_gemm(b->xp_d, DD, F.w13, nullptr, L.s13, 2 * DH, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
+            CK(batch_gemm(b->xp_d, DD, StepW{F.w13, 0, 0}, L.s13, 2 * DH, nb, b->part, st, b->ssq, DD / 256, c.dec_eps));
             CK(launch_swiglu_fplanes(b->part, skl_splits(DD, 2 * DH), DH, nb, b->xp_h, st));
         }
-        CK(batch_gemm(b->xp_h, DH, F.w2, mx(L.m2), L.s2, DD, nb, b->part, st));
+        CK(batch_gemm(b->xp_h, DH, src(F.w2, L.m2, L.p2), L.s2, DD, nb, b->part, st));
     }
     // final norm (after the last w2 residual) + LM head (tied embeddings) + per-slot argmax,
     // state, token log and next inputs (decoder.c:762-779)
@@ -4163,14 +4250,13 @@ static int batch_step(vox_hip_batch_t* b, int nb, int splits, int kvt, int wmx4,
     // 17..32 rows: both 16-row blocks in one k_skf launch (the embeddings read once;
     // VOX_HIP_SKF2=0: one launch per 16-row block)
     static const int skf2 = env_on("VOX_HIP_SKF2");
-    const uint8_t* mlm = mx(m->mlm);
-    const void* lmw = mlm ? mlm : m->lm_frag;
+    const StepW lm = src(m->lm_frag, m->mlm, m->plm);
     if (skf2 && nb > SK_ROWS)
-        CK(launch_gemm_skf2(b->xp_d, DD, lmw, m->tok_emb_s, c.vocab, nb, b->logits, c.vocab, st, mlm != nullptr));
+        CK(launch_gemm_skf2(b->xp_d, DD, lm.w, m->tok_emb_s, c.vocab, nb, b->logits, c.vocab, st, lm.mx4, lm.p13c));
     else
         for (int r0 = 0; r0 < nb; r0 += SK_ROWS)
-            CK(launch_gemm_skf(b->xp_d + (size_t)r0 * 3 * DD, DD, lmw, m->tok_emb_s, c.vocab,
-                               std::min(SK_ROWS, nb - r0), b->logits + (size_t)r0 * c.vocab, c.vocab, st, mlm != nullptr));
+            CK(launch_gemm_skf(b->xp_d + (size_t)r0 * 3 * DD, DD, lm.w, m->tok_emb_s, c.vocab,
+                               std::min(SK_ROWS, nb - r0), b->logits + (size_t)r0 * c.vocab, c.vocab, st, lm.mx4, lm.p13c));
     CK(launch_argmax_batch(b->logits, nb, c.vocab, b->pval, b->pidx, b->palt, b->slots, TOKENS_CAP, slot_toklog(b->slots, b->rows),
                            m->tok_emb, m->tok_emb_s, DD, b->x, st));
     return 0;
@@ -4351,6 +4437,20 @@ extern "C" int vox_hip_batch_set_wmx4(vox_hip_batch_t* b, int on) {
     return 0;
 }
 
+extern "C" int vox_hip_batch_set_wpack(vox_hip_batch_t* b, int on) {
+    if (!b) return set_err("batch_set_wpack: null batch");
+    if (b->call.active) return set_err("batch_set_wpack: a begun call was not finished");
+    if (on && !b->m->pfstats[0])
+        return set_err("batch_set_wpack: the model has no wpack13 fragment planes (vox_hip_set_wpack_batch before its creation)");
+    b->wp13 = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int vox_hip_batch_wpack(const vox_hip_batch_t* b) {
+    if (!b) return set_err("batch_wpack: null batch");
+    return b->wp13;
+}
+
 extern "C" int vox_hip_batch_set_prefill_kv(vox_hip_batch_t* b, int on) {
     if (!b) return set_err("batch_set_prefill_kv: null batch");
     if (b->call.active) return set_err("batch_set_prefill_kv: a begun call was not finished");
@@ -4444,11 +4544,12 @@ static int slot_bucket(int n, int* g) {
 static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int kvt, int steps, int gemv, int mixed,
                      int ragged) {
     const int wmx4 = b->wmx4;  // fixed while a begun call is unfinished (vox_hip_batch_set_wmx4)
+    const int wp13 = b->wp13;  // likewise (vox_hip_batch_set_wpack)
     const int gwmx4 = b->gemv_wmx4;  // likewise (vox_hip_batch_set_gemv_wmx4: on only with a plane to stream)
     const bool wide = nb > VOX_MAX_BATCH;  // buckets 64 and 128 (gemv == 0 there)
     auto step = [&]() {
         return wide ? batch_step_wide(b, nb, splits, kvt, mixed, ragged)
-               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4, mixed, ragged);
+               : gemv ? batch_step_gemv(b, nb, splits, kvt, gwmx4) : batch_step(b, nb, splits, kvt, wmx4, wp13, mixed, ragged);
     };
     if (ragged) b->n_ragged_replays += steps;
     if (gemv) b->n_gemv_replays += steps;
@@ -4465,7 +4566,7 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
     }
     const int mr = mixed + 2 * ragged;
     hipGraphExec_t& ge = wide ? b->gwexec[mr][kvt][gb - 6][gi]
-                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[mr][3 * wmx4 + kvt][gb][gi];
+                         : gemv ? b->gvexec[3 * gwmx4 + kvt][gb][gi] : b->gexec[mr][3 * (wmx4 + 2 * wp13) + kvt][gb][gi];
     if (!ge) {
         hipGraph_t g = nullptr;
         CK(hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));

@@ -15,7 +15,7 @@ constexpr int ALT_REC = 8;           // per-step alt record: p_best, (id, p) x 3
 enum { PRO_NONE = 0, PRO_NORM = 1, PRO_NORM_ADA = 2 };
 // k_gemv weight formats: bf16 rows, Q8 rows + row scales, wpack13 planes (vox_wpack.h), wmx4
 // plane (vox_wmx4.h).  The skinny MFMA kernels (k_skf, k_skl, k_skl2, k_sklx) take WF_BF16 and
-// WF_Q8 as fragment-major copies and WF_MX4 as the wmx4 fragment plane.
+// WF_Q8 as fragment-major copies, WF_MX4 as the wmx4 and WF_P13 as the wpack13 fragment plane.
 enum { WF_BF16 = 0, WF_Q8 = 1, WF_P13 = 2, WF_MX4 = 3 };
 
 constexpr int GEMV_MAX_BLOCKS = 1024;  // 4 blocks of 256 threads per CU on 256 CUs
@@ -305,11 +305,13 @@ hipError_t launch_swiglu_fplanes(const float* part, int S, int H, int nb, uint16
 // C[j][n] = sum_k x_j[k] W[n][k] (LM head: k_skf)
 // mx4 (here and in the launchers below): Wf is the wmx4 fragment plane (vox_wmx4.h) of a bf16
 // matrix instead of its fragment-major copy; same geometry, same bits
+// p13c != 0 (likewise): Wf is the tensor's wpack13 fragment plane (vox_wpack.h) and p13c its
+// 112 + D; same geometry, same bits
 hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                           int ldc, hipStream_t st, int mx4 = 0);
+                           int ldc, hipStream_t st, int mx4 = 0, int p13c = 0);
 // launch_gemm_skf for 17..32 rows (two 16-row blocks of planes, one weight read)
 hipError_t launch_gemm_skf2(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                            int ldc, hipStream_t st, int mx4 = 0);
+                            int ldc, hipStream_t st, int mx4 = 0, int p13c = 0);
 // split-K slabs part[s][16][N], s < skl_splits(K, N) (projections: k_skl; k_sklx and the
 // encoder's skinny chain use skl_splits(K))
 int skl_splits(int K, int N = 0);
@@ -319,7 +321,7 @@ constexpr int SKL_MAX_SLICES = 12;  // D <= 3072
 // configuration exists (the batched step)
 hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb,
                            float* part, hipStream_t st, const float* ssq = nullptr, int nsl = 0, float eps = 0.f,
-                           int pair = 0, int mx4 = 0);
+                           int pair = 0, int mx4 = 0, int p13c = 0);
 hipError_t launch_gemm_skl_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, int N, int nb, float* part,
                                hipStream_t st);  // tools/kbench sweep
 hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, int N, int nb, float* part,
@@ -364,13 +366,14 @@ struct SklFused {
     float* Kc = nullptr;
     float* Vc = nullptr;
     int kvt = 0;                  // SKX_EPI_QKV: the encoder ring's element, KV_F32 / KV_F16 / KV_FP8
+    uint32_t wc = 0;              // the wpack13 instances' (112 + D) << 7 | 1 in both halves (set by the launcher)
 };
 // column slices of a k_sklx launch (the ssq_out slices its consumer sums)
 int sklx_slices(int N, int K);
 constexpr int SKX_TICKETS = 4 * 1024;
-// mx4: SKX_PRO_SCALE / SKX_EPI_SWIGLU only (the batched decode step's W1|W3)
+// mx4, p13c: SKX_PRO_SCALE / SKX_EPI_SWIGLU only (the batched decode step's W1|W3)
 hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const void* Wf, int N, int nb,
-                            const SklFused& f, hipStream_t st, int mx4 = 0);
+                            const SklFused& f, hipStream_t st, int mx4 = 0, int p13c = 0);
 // k_gemmf (vox_hip_gemmf.hip): stream-K MFMA GEMM, planes x fragment-major bf16 (or int8) weights;
 // epi in {STORE, RESID, GELU, GELU_ERF, SWIGLU}; SWIGLU with xo writes the gate rows as
 // planes [rb][3][16][N / 2].  ws: gemmf_ws_floats(gemmf_grid()) floats of partial tiles,

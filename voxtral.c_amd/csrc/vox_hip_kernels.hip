@@ -18,6 +18,7 @@
 // exact and only the summation order differs from the CPU sgemm.
 #include "vox_hip_internal.h"
 #include "vox_hip_dev.h"
+#include "vox_wpack.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -2022,7 +2023,9 @@ __device__ __forceinline__ bf16x8 mx4x8_bf16(uint32_t w, float sc) {
 // one 64-k block of a 16-row group, by weight format.  WF_BF16: two 16-B halves of the
 // fragment-major copy (2048 B per block); WF_Q8: one 16-B piece of 16 int8 (1024 B); WF_MX4:
 // the wmx4 fragment plane's record (vox_wmx4.h, 576 B) -- 8 B of nibbles and the lane's scale
-// byte, turned into the bf16 instance's halves in registers.
+// byte, turned into the bf16 instance's halves in registers; WF_P13: the wpack13 fragment
+// plane's record (vox_wpack.h, 1664 B) -- 16 + 8 B of 12-bit fields and the lane's 16 sign
+// bits, likewise (p13x2_bf16; wc: the tensor's (112 + D) << 7 | 1 in both halves of a dword).
 template <int WF>
 struct SkA {
     u32x4 v[WF == WF_Q8 ? 1 : 2];
@@ -2032,24 +2035,71 @@ struct SkA<WF_MX4> {
     u32x2 nib;
     uint32_t sc;
 };
+template <>
+struct SkA<WF_P13> {
+    u32x4 a;     // fields of weights 0..7, nibbles of weights 12, 13 (x, y, z) and 14, 15 (w)
+    u32x2 b;     // fields of weights 8..11, the other nibbles of weights 14, 15
+    uint32_t s;  // signs: weight 2p in bit p, weight 2p + 1 in bit 8 + p
+};
 template <int WF>
-constexpr int ska_bytes() { return WF == WF_MX4 ? 576 : WF == WF_Q8 ? 1024 : 2048; }
+constexpr int ska_bytes() { return WF == WF_P13 ? 1664 : WF == WF_MX4 ? 576 : WF == WF_Q8 ? 1024 : 2048; }
+
+// Two wpack13 weights -> the two bf16 they stand for.  low: their 12-bit exponent-and-mantissa
+// fields in the two halves (bits 12..15 of each half clear); sg: their signs in bits 15 and 31
+// (other bits anything).  Per half, packed 16-bit: low + min(low, 1) * ((112 + D) << 7) -- the
+// field with the exponent rebased, or 0 for the code of +-0 -- then the sign on top: v_pk_min_u16,
+// v_pk_mad_u16, v_and_or_b32.  The clamp's 1 is bit 0 of each half of wc, a value the compiler
+// cannot see: against a literal 1 it rewrites the pair as compares and selects per half (8 VALU
+// instructions in place of 2).
+typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
+__device__ __forceinline__ uint32_t p13x2_bf16(uint32_t low, uint32_t sg, uint32_t wc) {
+    const u16x2 x = __builtin_bit_cast(u16x2, low);
+    const u16x2 m = __builtin_elementwise_min(x, __builtin_bit_cast(u16x2, wc & 0x00010001u));
+    const u16x2 r = m * __builtin_bit_cast(u16x2, wc & 0x7f807f80u) + x;
+    return __builtin_bit_cast(uint32_t, r) | (sg & 0x80008000u);
+}
+// the 12-bit fields of two weights from the spare nibbles of three dwords (n0 the low nibble)
+__device__ __forceinline__ uint32_t p13_nibbles(uint32_t n0, uint32_t n1, uint32_t n2) {
+    const u16x2 a = __builtin_bit_cast(u16x2, n0) >> 12, b = __builtin_bit_cast(u16x2, n1) >> 12,
+                c = __builtin_bit_cast(u16x2, n2) >> 12;
+    return (__builtin_bit_cast(uint32_t, c) << 4 | __builtin_bit_cast(uint32_t, b)) << 4 | __builtin_bit_cast(uint32_t, a);
+}
 // the lane's loads of the block at byte `soff` of the descriptor (non-temporal)
 template <int WF>
 __device__ __forceinline__ void ska_load(SkA<WF>& a, __amdgpu_buffer_rsrc_t W, int lane, int soff) {
     if constexpr (WF == WF_MX4) {
         a.nib = __builtin_amdgcn_raw_buffer_load_b64(W, lane * 8, soff, 2);
         a.sc = __builtin_amdgcn_raw_buffer_load_b8(W, 512 + lane, soff, 2);
+    } else if constexpr (WF == WF_P13) {
+        a.a = __builtin_amdgcn_raw_buffer_load_b128(W, lane * 16, soff, 2);
+        a.b = __builtin_amdgcn_raw_buffer_load_b64(W, 1024 + lane * 8, soff, 2);
+        a.s = __builtin_amdgcn_raw_buffer_load_b16(W, 1536 + lane * 2, soff, 2);
     } else {
 #pragma unroll
         for (int t = 0; t < (WF == WF_Q8 ? 1 : 2); t++) a.v[t] = __builtin_amdgcn_raw_buffer_load_b128(W, lane * 16 + t * 1024, soff, 2);
     }
 }
-// half t of the block as the MFMA's A fragment
+// half t of the block as the MFMA's A fragment (wc: WF_P13 only)
 template <int WF>
-__device__ __forceinline__ bf16x8 ska_frag(const SkA<WF>& a, int t) {
+__device__ __forceinline__ bf16x8 ska_frag(const SkA<WF>& a, int t, uint32_t wc = 0) {
     if constexpr (WF == WF_MX4) {
         return mx4x8_bf16(t ? a.nib.y : a.nib.x, __uint_as_float(a.sc << 23));
+    } else if constexpr (WF == WF_P13) {
+        // the signs of dword p's two weights reach bits 15 and 31 by a shift of 15 - p
+        const uint32_t sg = (a.s & 0xffu) | (a.s & 0xff00u) << 8, M = 0x0fff0fffu;
+        uint4 o;
+        if (t == 0) {
+            o.x = p13x2_bf16(a.a.x & M, sg << 15, wc);
+            o.y = p13x2_bf16(a.a.y & M, sg << 14, wc);
+            o.z = p13x2_bf16(a.a.z & M, sg << 13, wc);
+            o.w = p13x2_bf16(a.a.w & M, sg << 12, wc);
+        } else {
+            o.x = p13x2_bf16(a.b.x & M, sg << 11, wc);
+            o.y = p13x2_bf16(a.b.y & M, sg << 10, wc);
+            o.z = p13x2_bf16(p13_nibbles(a.a.x, a.a.y, a.a.z), sg << 9, wc);
+            o.w = p13x2_bf16(p13_nibbles(a.a.w, a.b.x, a.b.y), sg << 8, wc);
+        }
+        return __builtin_bit_cast(bf16x8, o);
     } else if constexpr (WF == WF_Q8) {
         const u32x4 q = a.v[0];
         return t ? i8x8_bf16(q.z, q.w) : i8x8_bf16(q.x, q.y);
@@ -2088,12 +2138,12 @@ __device__ __forceinline__ void skf_load(SkfRegs<WF, R, Z>& s, __amdgpu_buffer_r
 }
 
 template <int WF, int R, int Z>
-__device__ __forceinline__ void skf_mma(const SkfRegs<WF, R, Z>& s, f32x4 (&acc)[Z][R]) {
+__device__ __forceinline__ void skf_mma(const SkfRegs<WF, R, Z>& s, f32x4 (&acc)[Z][R], uint32_t wc) {
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            const bf16x8 af = ska_frag<WF>(s.a[r], t);
+            const bf16x8 af = ska_frag<WF>(s.a[r], t, wc);
 #pragma unroll
             for (int z = 0; z < Z; z++)
 #pragma unroll
@@ -2111,7 +2161,7 @@ __device__ __forceinline__ void skf_mma(const SkfRegs<WF, R, Z>& s, f32x4 (&acc)
 template <int WF, int R, int NW, int D, int Z = 1>
 __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs, int K,
                                                  const uint8_t* __restrict__ W, const float* __restrict__ wscale,
-                                                 int N, int nb, float* __restrict__ C, int ldc) {
+                                                 int N, int nb, float* __restrict__ C, int ldc, uint32_t wc) {
     __shared__ float red[NW][Z * R][4][64];
     constexpr bool WQ8 = WF == WF_Q8;
     constexpr int FB = ska_bytes<WF>();
@@ -2150,7 +2200,7 @@ __global__ __launch_bounds__(NW * 64) void k_skf(const uint16_t* __restrict__ xs
         for (int i = 0; i < D; i++) {
             SKF_LOAD((i + D - 1) % D, b + i + D - 1);
             __builtin_amdgcn_sched_barrier(0);
-            skf_mma<WF, R, Z>(s[i], acc);  // zeros past the range: acc + 0
+            skf_mma<WF, R, Z>(s[i], acc, wc);  // zeros past the range: acc + 0
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -2192,7 +2242,7 @@ template <int WF, int NW, int KS, int SC = 0>
 __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs, int K,
                                                  const uint8_t* __restrict__ W, const float* __restrict__ wscale,
                                                  int N, int nb, float* __restrict__ part,
-                                                 const float* __restrict__ ssq = nullptr, int nsl = 0, float eps = 0.f) {
+                                                 const float* __restrict__ ssq, int nsl, float eps, uint32_t wc) {
     __shared__ uint4 xb[KS * 6 * 64];  // [block][plane][half][lane]
     __shared__ float s_sq[SC ? SK_ROWS * SKL_MAX_SLICES : 1];
     constexpr bool WQ8 = WF == WF_Q8;
@@ -2247,7 +2297,7 @@ __global__ __launch_bounds__(NW * 64) void k_skl(const uint16_t* __restrict__ xs
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            const bf16x8 af = ska_frag<WF>(a[kb], t);
+            const bf16x8 af = ska_frag<WF>(a[kb], t, wc);
 #pragma unroll
             for (int p = 0; p < 3; p++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(bf16x8, xb[((kb * 3 + p) * 2 + t) * 64 + lane]),
@@ -2285,7 +2335,7 @@ template <int WF, int NW, int KS, int SC = 0>
 __global__ __launch_bounds__(NW * 64) void k_skl2(const uint16_t* __restrict__ xs, int K,
                                                   const uint8_t* __restrict__ W, const float* __restrict__ wscale,
                                                   int N, int nb, float* __restrict__ part,
-                                                  const float* __restrict__ ssq = nullptr, int nsl = 0, float eps = 0.f) {
+                                                  const float* __restrict__ ssq, int nsl, float eps, uint32_t wc) {
     __shared__ uint4 xb[2][KS * 6 * 64];  // [row block][block][plane][half][lane]
     __shared__ float s_sq[SC ? 2 * SK_ROWS * SKL_MAX_SLICES : 1];
     constexpr bool WQ8 = WF == WF_Q8;
@@ -2336,7 +2386,7 @@ __global__ __launch_bounds__(NW * 64) void k_skl2(const uint16_t* __restrict__ x
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            const bf16x8 af = ska_frag<WF>(a[kb], t);
+            const bf16x8 af = ska_frag<WF>(a[kb], t, wc);
 #pragma unroll
             for (int z = 0; z < 2; z++)
 #pragma unroll
@@ -2618,7 +2668,7 @@ __global__ __launch_bounds__(NW * 64) void k_sklx(const uint16_t* __restrict__ x
     for (int kb = 0; kb < KS; kb++)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-            const bf16x8 af = ska_frag<WF>(a[kb], t);
+            const bf16x8 af = ska_frag<WF>(a[kb], t, f.wc);
 #pragma unroll
             for (int p = 0; p < 3; p++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(bf16x8, xb[((kb * 3 + p) * 2 + t) * 64 + lane]),
@@ -3550,9 +3600,9 @@ VOX_KB_KNOB(g_skl_nw, 0);
 
 template <int Q, int R, int NW, int D, int Z = 1>
 static hipError_t skf_launch(const uint16_t* xs, int K, const void* W, const float* wscale, int N, int nb,
-                             float* C, int ldc, hipStream_t st) {
+                             float* C, int ldc, hipStream_t st, uint32_t wc = 0) {
     hipLaunchKernelGGL((k_skf<Q, R, NW, D, Z>), dim3(N / (16 * R)), dim3(NW * 64), 0, st, xs, K,
-                       static_cast<const uint8_t*>(W), wscale, N, nb, C, ldc);
+                       static_cast<const uint8_t*>(W), wscale, N, nb, C, ldc, wc);
     return hipGetLastError();
 }
 
@@ -3562,24 +3612,33 @@ static hipError_t skf_launch(const uint16_t* xs, int K, const void* W, const flo
 
 template <int Q>
 static hipError_t skf_cfg(const uint16_t* xs, int K, const void* W, const float* wscale, int N, int nb, float* C,
-                          int ldc, hipStream_t st) {
+                          int ldc, hipStream_t st, uint32_t wc = 0) {
     const int groups = N / 16;
     const int r = g_skf_r ? g_skf_r : (groups >= 2048 ? 4 : groups >= 512 ? 2 : 1);
     if (groups % r) return hipErrorInvalidValue;
     const int nw = g_skf_nw ? g_skf_nw : 4, d = g_skf_d ? g_skf_d : 2;
 #define SKF_X(RR, NWW, DD) \
-    if (r == RR && nw == NWW && d == DD) return skf_launch<Q, RR, NWW, DD>(xs, K, W, wscale, N, nb, C, ldc, st);
+    if (r == RR && nw == NWW && d == DD) return skf_launch<Q, RR, NWW, DD>(xs, K, W, wscale, N, nb, C, ldc, st, wc);
     SKF_CONFIGS(SKF_X)
 #undef SKF_X
     return hipErrorInvalidValue;
 }
 
-// mx4: Wf is the wmx4 fragment plane (vox_wmx4.h) of a bf16 matrix, every launcher below alike;
-// the geometry is the bf16 instance's, so the two give the same bits
+// the wpack13 instances' kernel argument: (112 + D) << 7 | 1 in both halves of a dword (p13x2_bf16)
+static uint32_t p13_wc(int p13c) { return ((uint32_t)p13c << 7 | 1u) * 0x00010001u; }
+// a launch streams at most one plane of a bf16 tensor; 112 + D of a packable tensor is 72..152
+static bool sk_plane_bad(int mx4, int p13c, const float* wscale) {
+    return ((mx4 || p13c) && wscale) || (mx4 && p13c) || (p13c && (p13c < 112 - VOX_WPACK_MAX_D || p13c > 112 + VOX_WPACK_MAX_D));
+}
+
+// mx4: Wf is the wmx4 fragment plane (vox_wmx4.h) of a bf16 matrix, p13c: its wpack13 fragment
+// plane (vox_wpack.h), every launcher below alike; the geometry is the bf16 instance's, so
+// the three give the same bits
 hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                           int ldc, hipStream_t st, int mx4) {
-    if (nb < 1 || nb > SK_ROWS || N % 64 || K % 64 || !C || (mx4 && wscale)) return hipErrorInvalidValue;
+                           int ldc, hipStream_t st, int mx4, int p13c) {
+    if (nb < 1 || nb > SK_ROWS || N % 64 || K % 64 || !C || sk_plane_bad(mx4, p13c, wscale)) return hipErrorInvalidValue;
     if (mx4) return skf_cfg<WF_MX4>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
+    if (p13c) return skf_cfg<WF_P13>(xs, K, Wf, nullptr, N, nb, C, ldc, st, p13_wc(p13c));
     return wscale ? skf_cfg<1>(xs, K, Wf, wscale, N, nb, C, ldc, st) : skf_cfg<0>(xs, K, Wf, wscale, N, nb, C, ldc, st);
 }
 
@@ -3589,14 +3648,20 @@ hipError_t launch_gemm_skf(const uint16_t* xs, int K, const void* Wf, const floa
 // launch at R = 1 / 2 / 4 328.1 / 192.1 / 149.3 us, the same bits
 VOX_KB_KNOB(g_skf2_r, 4);
 hipError_t launch_gemm_skf2(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb, float* C,
-                            int ldc, hipStream_t st, int mx4) {
-    if (nb <= SK_ROWS || nb > 2 * SK_ROWS || N % 64 || K % 64 || !C || (mx4 && wscale)) return hipErrorInvalidValue;
+                            int ldc, hipStream_t st, int mx4, int p13c) {
+    if (nb <= SK_ROWS || nb > 2 * SK_ROWS || N % 64 || K % 64 || !C || sk_plane_bad(mx4, p13c, wscale)) return hipErrorInvalidValue;
     const int r = g_skf2_r;
     if ((N / 16) % r) return hipErrorInvalidValue;
     if (mx4) {
         if (r == 1) return skf_launch<WF_MX4, 1, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
         if (r == 4) return skf_launch<WF_MX4, 4, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
         return skf_launch<WF_MX4, 2, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st);
+    }
+    if (p13c) {
+        const uint32_t wc = p13_wc(p13c);
+        if (r == 1) return skf_launch<WF_P13, 1, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st, wc);
+        if (r == 4) return skf_launch<WF_P13, 4, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st, wc);
+        return skf_launch<WF_P13, 2, 4, 2, 2>(xs, K, Wf, nullptr, N, nb, C, ldc, st, wc);
     }
     if (r == 1) return wscale ? skf_launch<1, 1, 4, 2, 2>(xs, K, Wf, wscale, N, nb, C, ldc, st)
                               : skf_launch<0, 1, 4, 2, 2>(xs, K, Wf, wscale, N, nb, C, ldc, st);
@@ -3608,16 +3673,16 @@ hipError_t launch_gemm_skf2(const uint16_t* xs, int K, const void* Wf, const flo
 
 template <int Q, int NW, int KS>
 static hipError_t skl_launch(const uint16_t* xs, int K, const void* W, const float* wscale, int N, int nb,
-                             float* part, hipStream_t st, const float* ssq, int nsl, float eps) {
+                             float* part, hipStream_t st, const float* ssq, int nsl, float eps, uint32_t wc = 0) {
     const int units = (N / (16 * NW)) * (K / (64 * KS));
     const int Z = (nb + SK_ROWS - 1) / SK_ROWS;
     const int grid = Z > 1 ? (units + 7) / 8 * 8 * Z : units;
     if (ssq)
         hipLaunchKernelGGL((k_skl<Q, NW, KS, 1>), dim3(grid), dim3(NW * 64), 0, st, xs, K, static_cast<const uint8_t*>(W),
-                           wscale, N, nb, part, ssq, nsl, eps);
+                           wscale, N, nb, part, ssq, nsl, eps, wc);
     else
         hipLaunchKernelGGL((k_skl<Q, NW, KS, 0>), dim3(grid), dim3(NW * 64), 0, st, xs, K, static_cast<const uint8_t*>(W),
-                           wscale, N, nb, part, nullptr, 0, 0.f);
+                           wscale, N, nb, part, nullptr, 0, 0.f, wc);
     return hipGetLastError();
 }
 
@@ -3670,26 +3735,28 @@ int skl_splits(int K, int N) {
 
 template <int Q, int NW, int KS>
 static hipError_t skl2_launch(const uint16_t* xs, int K, const void* W, const float* wscale, int N, int nb,
-                              float* part, hipStream_t st, const float* ssq, int nsl, float eps) {
+                              float* part, hipStream_t st, const float* ssq, int nsl, float eps, uint32_t wc = 0) {
     const int grid = (N / (16 * NW)) * (K / (64 * KS));
     if (ssq)
         hipLaunchKernelGGL((k_skl2<Q, NW, KS, 1>), dim3(grid), dim3(NW * 64), 0, st, xs, K, static_cast<const uint8_t*>(W),
-                           wscale, N, nb, part, ssq, nsl, eps);
+                           wscale, N, nb, part, ssq, nsl, eps, wc);
     else
         hipLaunchKernelGGL((k_skl2<Q, NW, KS, 0>), dim3(grid), dim3(NW * 64), 0, st, xs, K, static_cast<const uint8_t*>(W),
-                           wscale, N, nb, part, nullptr, 0, 0.f);
+                           wscale, N, nb, part, nullptr, 0, 0.f, wc);
     return hipGetLastError();
 }
 
 #define SKL2_CONFIGS(X) X(4, 4) X(8, 4) X(4, 6) X(4, 8) X(8, 8)
 static hipError_t skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const void* Wf, const float* wscale, int N,
-                           int nb, float* part, hipStream_t st, const float* ssq, int nsl, float eps, int mx4 = 0) {
+                           int nb, float* part, hipStream_t st, const float* ssq, int nsl, float eps, int mx4 = 0,
+                           int p13c = 0) {
     if (nb <= SK_ROWS || nb > 2 * SK_ROWS || K % 64 || (K / 64) % ks || N % (16 * nw) || (ks * 6) % nw ||
         (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)))
         return hipErrorInvalidValue;
 #define SKL2_X(NWW, KSS)                                                                                      \
     if (nw == NWW && ks == KSS)                                                                               \
         return mx4    ? skl2_launch<WF_MX4, NWW, KSS>(xs, K, Wf, nullptr, N, nb, part, st, ssq, nsl, eps)     \
+               : p13c ? skl2_launch<WF_P13, NWW, KSS>(xs, K, Wf, nullptr, N, nb, part, st, ssq, nsl, eps, p13_wc(p13c)) \
                : wscale ? skl2_launch<1, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps)         \
                         : skl2_launch<0, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
     SKL2_CONFIGS(SKL2_X)
@@ -3704,12 +3771,14 @@ hipError_t launch_gemm_skl2_cfg(int nw, int ks, const uint16_t* xs, int K, const
 }
 
 hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const float* wscale, int N, int nb,
-                           float* part, hipStream_t st, const float* ssq, int nsl, float eps, int pair, int mx4) {
+                           float* part, hipStream_t st, const float* ssq, int nsl, float eps, int pair, int mx4, int p13c) {
     const int S = skl_splits(K, N);
     // ssq: each row block's nsl x 16 sums ride with its planes (nsl * 16 <= the block's threads)
-    if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)) || (mx4 && wscale))
+    if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || (ssq && (nsl < 1 || nsl > SKL_MAX_SLICES)) ||
+        sk_plane_bad(mx4, p13c, wscale))
         return hipErrorInvalidValue;
-    const int wf = mx4 ? WF_MX4 : wscale ? WF_Q8 : WF_BF16;
+    const int wf = mx4 ? WF_MX4 : p13c ? WF_P13 : wscale ? WF_Q8 : WF_BF16;
+    const uint32_t wc = p13_wc(p13c);
     const int ks = K / 64 / S;
     const int nw = ks == 6 ? 4 : skl_nw_for(N, S);
     if (N % (16 * nw)) return hipErrorInvalidValue;
@@ -3717,14 +3786,15 @@ hipError_t launch_gemm_skl(const uint16_t* xs, int K, const void* Wf, const floa
     // waves and splits -- the same bits, each weight fragment loaded once (QKV 12.7 -> 11.4,
     // wo 9.8 -> 8.7, W2 17.7 -> 16.7 us at 32 rows, profiles/r6_kbench_skl2.txt)
     if (pair && nb > SK_ROWS && nb <= 2 * SK_ROWS) {
-        const hipError_t e = skl2_cfg(nw, ks, xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps, mx4);
+        const hipError_t e = skl2_cfg(nw, ks, xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps, mx4, p13c);
         if (e != hipErrorInvalidValue) return e;
     }
 #define SKL_X(Q, NWW, KSS) \
-    if (wf == Q && nw == NWW && ks == KSS) return skl_launch<Q, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps);
+    if (wf == Q && nw == NWW && ks == KSS) return skl_launch<Q, NWW, KSS>(xs, K, Wf, wscale, N, nb, part, st, ssq, nsl, eps, wc);
     SKL_X(0, 4, 8) SKL_X(0, 8, 8) SKL_X(0, 4, 4) SKL_X(0, 8, 4) SKL_X(0, 4, 6)
     SKL_X(1, 4, 8) SKL_X(1, 8, 8) SKL_X(1, 4, 4) SKL_X(1, 8, 4) SKL_X(1, 4, 6)
     SKL_X(WF_MX4, 4, 8) SKL_X(WF_MX4, 8, 8) SKL_X(WF_MX4, 4, 4) SKL_X(WF_MX4, 8, 4) SKL_X(WF_MX4, 4, 6)
+    SKL_X(WF_P13, 4, 8) SKL_X(WF_P13, 8, 8) SKL_X(WF_P13, 4, 4) SKL_X(WF_P13, 8, 4) SKL_X(WF_P13, 4, 6)
 #undef SKL_X
     return hipErrorInvalidValue;
 }
@@ -3760,7 +3830,7 @@ static hipError_t sklx_launch(const uint16_t* xs, int K, const void* W, int N, i
 }
 
 hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const void* Wf, int N, int nb,
-                            const SklFused& f, hipStream_t st, int mx4) {
+                            const SklFused& f, hipStream_t st, int mx4, int p13c) {
     const int S = skl_splits(K);
     if (nb < 1 || nb > SK_MAX_ROWS || K % 64 || !S || !f.part || !f.ticket) return hipErrorInvalidValue;
     const int ks = K / 64 / S, nw = sklx_nw(N, K);
@@ -3774,13 +3844,24 @@ hipError_t launch_gemm_sklx(int pro, int epi, const uint16_t* xs, int K, const v
                                N != f.qd + 2 * f.kvd))
         return hipErrorInvalidValue;
     // the append's ring element: f32, or the encoder's IEEE half or FP8 with the QKV epilogue
-    if (f.kvt != KV_F32 && ((f.kvt != KV_F16 && (f.kvt != KV_FP8 || f.hd != 64)) || epi != SKX_EPI_QKV || mx4 || f.kvd % 2))
+    if (f.kvt != KV_F32 && ((f.kvt != KV_F16 && (f.kvt != KV_FP8 || f.hd != 64)) || epi != SKX_EPI_QKV || mx4 || p13c || f.kvd % 2))
         return hipErrorInvalidValue;
+    if (sk_plane_bad(mx4, p13c, nullptr)) return hipErrorInvalidValue;
 #define SKX_CFG(PP, EE) SKX_X(4, 4, PP, EE) SKX_X(4, 8, PP, EE) SKX_X(8, 4, PP, EE) SKX_X(8, 8, PP, EE)
     if (mx4) {
         // the wmx4 fragment plane: the batched decode step's W1|W3 only
 #define SKX_X(NWW, KSS, PP, EE) \
     if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE, WF_MX4>(xs, K, Wf, N, nb, f, st);
+        SKX_CFG(SKX_PRO_SCALE, SKX_EPI_SWIGLU)
+#undef SKX_X
+        return hipErrorInvalidValue;
+    }
+    if (p13c) {
+        // the wpack13 fragment plane: likewise
+        SklFused fp = f;
+        fp.wc = p13_wc(p13c);
+#define SKX_X(NWW, KSS, PP, EE) \
+    if (nw == NWW && ks == KSS && pro == PP && epi == EE) return sklx_launch<NWW, KSS, PP, EE, WF_P13>(xs, K, Wf, N, nb, fp, st);
         SKX_CFG(SKX_PRO_SCALE, SKX_EPI_SWIGLU)
 #undef SKX_X
         return hipErrorInvalidValue;

@@ -23,6 +23,24 @@
  * chunk 0 there and meets x = 0).  Dword s / 4 holds slot s with q = s % 4 as
  *   low nibble at bits 12 - 4q .. 15 - 4q,  high nibble at bits 28 - 4q .. 31 - 4q
  * so that (dword << 4q) & 0xf000f000 lands both nibbles on top of the two halves.
+ *
+ * Fragment plane, laid out for the batched step's MFMA kernels (k_skl, k_skl2, k_sklx, k_skf):
+ * the A operand of a [N, K] tensor in device row order, N % 16 == 0, K % 64 == 0, in the same
+ * codes and D.  One record of VOX_WPACK13_FRAG_REC = 416 dwords (1664 B) per (16-row group g,
+ * 64-k block b) at dword (g * K / 64 + b) * 416.  Lane l = 16 q + j of the wave that streams the
+ * group owns row 16 g + j, k 64 b + 16 q + i, i = 0..15 (the 16 weights of the bf16 fragment
+ * copy's lane, frag_off in vox_hip_dev.h).  With low(i) = code(i) & 0xfff (exponent and
+ * mantissa) and s(i) = code(i) >> 12, the lane's 26 bytes are
+ *   dwords 4 l .. 4 l + 3 (p = 0..3) and 256 + 2 l, 256 + 2 l + 1 (p = 4, 5):
+ *       low(2p) | n(p, 0) << 12 | low(2p + 1) << 16 | n(p, 1) << 28
+ *     where the spare nibbles carry weights 12..15, nibble by nibble:
+ *       n(p, h) = (low(12 + h) >> 4 p) & 15 for p = 0..2,  (low(14 + h) >> 4 (p - 3)) & 15 for p = 3..5
+ *   the 16-bit word at byte 1536 + 2 l:  s(2p) << p | s(2p + 1) << (8 + p), p = 0..7.
+ * A lane fetches its block with a 16-B load at byte 16 l, an 8-B load at 1024 + 8 l and a 2-B
+ * load at 1536 + 2 l, each contiguous across the wave; the record does not depend on how many
+ * blocks a split takes.  The kernel turns a dword pair into the bf16 copy's two weights with
+ * packed 16-bit arithmetic: bits = s << 15 | (low + ((112 + D) << 7)), or s << 15 when low is 0
+ * (exact: a packable tensor has no nonzero subnormal).  13 stored bits per weight.
  */
 #ifndef VOX_WPACK_H
 #define VOX_WPACK_H
@@ -156,5 +174,43 @@ static inline void vox_wpack13_side_layout_(const uint8_t *side, long long rows,
                                             uint32_t *out) {
 #pragma omp parallel for schedule(static) num_threads(16)
     for (long long g = 0; g < rows / rb; g++) vox_wpack13_side_groups(side, g, g + 1, K, rb, swiglu, out);
+}
+/* ---- fragment plane (the batched step's A operand; layout in the header comment) ---- */
+#define VOX_WPACK13_FRAG_REC 416 /* dwords per (16-row group, 64-k block): 256 + 128 of fields, 32 of sign words */
+/* dwords of the fragment plane of a [N, K] tensor; 0 for a shape it does not take */
+static inline long long vox_wpack13_frag_words(long long N, long long K) {
+    if (N <= 0 || K <= 0 || N % 16 || K % 64) return 0;
+    return N / 16 * (K / 64) * VOX_WPACK13_FRAG_REC;
+}
+/* bf16 [N, K] of a packable tensor with its D -> 16-row groups g0..g1 of the fragment plane */
+static inline void vox_wpack13_frag_groups(const uint16_t *w, long long g0, long long g1, long long K, int D,
+                                           uint32_t *out) {
+    const long long nb = K / 64;
+    for (long long g = g0; g < g1; g++)
+        for (long long b = 0; b < nb; b++) {
+            uint32_t *rec = out + (g * nb + b) * VOX_WPACK13_FRAG_REC;
+            uint16_t *sg = (uint16_t *)(rec + 384);
+            for (int l = 0; l < 64; l++) {
+                const uint16_t *p = w + (g * 16 + (l & 15)) * K + b * 64 + (l >> 4) * 16;
+                uint32_t low[16], s = 0;
+                for (int i = 0; i < 16; i++) {
+                    const uint32_t c = vox_wpack13_code(p[i], D);
+                    low[i] = c & 0xfff;
+                    s |= (c >> 12) << ((i >> 1) + 8 * (i & 1));
+                }
+                for (int q = 0; q < 6; q++) {
+                    const int t = 12 + 2 * (q / 3), sh = 4 * (q % 3);
+                    const uint32_t d = low[2 * q] | ((low[t] >> sh) & 15) << 12 | low[2 * q + 1] << 16 |
+                                       ((low[t + 1] >> sh) & 15) << 28;
+                    rec[q < 4 ? 4 * l + q : 256 + 2 * l + q - 4] = d;
+                }
+                sg[l] = (uint16_t)s;
+            }
+        }
+}
+static inline void vox_wpack13_frag_layout_(const uint16_t *w, long long N, long long K, int D, uint32_t *out) {
+    if (!vox_wpack13_frag_words(N, K)) return;
+#pragma omp parallel for schedule(static) num_threads(16)
+    for (long long g = 0; g < N / 16; g++) vox_wpack13_frag_groups(w, g, g + 1, K, D, out);
 }
 #endif

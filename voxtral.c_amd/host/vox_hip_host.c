@@ -582,6 +582,8 @@ int vh_set_delay(vh_ctx_t *ctx, int delay_ms) {
     return vox_hip_model_set_delay(ctx->model, ctx->delay_tokens);
 }
 
+int vh_set_wpack_batch(int on) { return vox_hip_set_wpack_batch(on); }
+
 /* ------------------------------------------------------------------------
  * Streaming (voxtral.c:827-851, 1013-1145, 1288-1316, 1640-1667)
  * ------------------------------------------------------------------------ */

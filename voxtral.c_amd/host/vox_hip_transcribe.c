@@ -4,7 +4,7 @@
  *
  *   vox_hip_transcribe -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms]
  *                      [--alt cutoff] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8]
- *                      [--q8-gemmf] [--kv-grow slots]
+ *                      [--q8-gemmf] [--kv-grow slots] [--wpack-batch]
  *
  * The audio is fed in pieces of min(interval, 1 s) of samples, as main.c's feed_and_drain
  * does; every generated token id is printed to stdout (the tokenizer is out of scope) --
@@ -26,7 +26,11 @@
  * lossless, the same tokens; one slot is 80 ms of audio).
  * --q8-gemmf (no reference counterpart) puts a Q8 checkpoint's encoder passes and decoder
  * prefill on the stream-K MFMA GEMM over its int8 fragment copies (vox_hip_set_gemmf_q8(1),
- * voxtral_hip.h: the f32 summation order of those passes changes, nothing else).  The
+ * voxtral_hip.h: the f32 summation order of those passes changes, nothing else).
+ * --wpack-batch (no reference counterpart) also lays out the lossless wpack13 fragment planes a
+ * batched decode step of 2..32 streams reads in place of the bf16 fragment copies
+ * (vh_set_wpack_batch(1): the same tokens; this program's single stream does not read them, one
+ * stderr line reports what was built).  The
  * reference's stderr lines ("Audio:", "Encoder:", "Decoder:") are kept so its
  * benchmark.py regexes parse this program's output too.
  */
@@ -54,7 +58,7 @@ static void drain(vh_stream_t *s, int *text_tokens, int alt) {
 int main(int argc, char **argv) {
     const char *model = NULL, *wav = NULL;
     float interval = -1.0f, alt_cutoff = -1.0f;
-    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, enc_kv8 = 0, q8_gemmf = 0, kv_grow = 0;
+    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, enc_kv8 = 0, q8_gemmf = 0, kv_grow = 0, wpack_batch = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-d") && i + 1 < argc) model = argv[++i];
         else if (!strcmp(argv[i], "-i") && i + 1 < argc) wav = argv[++i];
@@ -68,6 +72,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--enc-kv8")) enc_kv8 = 1;
         else if (!strcmp(argv[i], "--q8-gemmf")) q8_gemmf = 1;
         else if (!strcmp(argv[i], "--kv-grow") && i + 1 < argc) kv_grow = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--wpack-batch")) wpack_batch = 1;
         else {
             model = NULL;
             break;
@@ -79,14 +84,21 @@ int main(int argc, char **argv) {
     }
     if (!model || !wav || kv_grow < 0 || (alt_cutoff != -1.0f && (alt_cutoff < 0 || alt_cutoff > 1))) {
         fprintf(stderr, "usage: %s -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms] "
-                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8] [--q8-gemmf] [--kv-grow slots]\n",
+                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8] [--q8-gemmf] [--kv-grow slots] [--wpack-batch]\n",
                 argv[0]);
         return 2;
     }
     if (mx4 && vox_hip_set_wmx4(2)) return 1;
     if (q8_gemmf && vox_hip_set_gemmf_q8(1)) return 1;
+    if (wpack_batch && vh_set_wpack_batch(1)) return 1;
     vh_ctx_t *ctx = vh_load(model);
     if (!ctx) return 1;
+    if (vox_hip_wpack_batch()) {
+        long long ps[4];
+        if (vox_hip_model_wpack_batch_stats(vh_model(ctx), ps)) return 1;
+        fprintf(stderr, "wpack batch: %lld tensors as wpack13 fragment planes, %.1f MB for %.1f MB of bf16; layout %.0f ms\n",
+                ps[0], ps[1] / 1e6, ps[2] / 1e6, ps[3] / 1e3);
+    }
     if (vox_hip_wmx4()) {
         vox_hip_wmx4_stats_t ms;
         if (vox_hip_model_wmx4_stats(vh_model(ctx), &ms)) return 1;

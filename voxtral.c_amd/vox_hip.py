@@ -131,6 +131,8 @@ EXPORTS = [
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
     "vox_hip_skinny_wmx4",
+    "vox_hip_set_wpack_batch", "vox_hip_wpack_batch", "vox_hip_model_wpack_batch_stats", "vox_hip_batch_set_wpack",
+    "vox_hip_batch_wpack", "vox_hip_skinny_wpack",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
@@ -195,6 +197,10 @@ def lib():
         "vox_hip_model_wmx4_batch_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_batch_set_wmx4": (I, [P, I]),
         "vox_hip_skinny_wmx4": (I, [I, I, P, fp, I, fp, I, I]),
+        "vox_hip_set_wpack_batch": (I, [I]), "vox_hip_wpack_batch": (I, []),
+        "vox_hip_model_wpack_batch_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_batch_set_wpack": (I, [P, I]), "vox_hip_batch_wpack": (I, [P]),
+        "vox_hip_skinny_wpack": (I, [I, I, P, fp, I, fp, I, I]),
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
         "vox_hip_set_gemmf_q8": (I, [I]), "vox_hip_gemmf_q8": (I, []),
@@ -326,11 +332,19 @@ def wmx4_batch() -> int:
     return lib().vox_hip_wmx4_batch()
 
 
-def skinny_wmx4(W_bf16, x, fmt: int, head: bool = False) -> np.ndarray:
-    """Test entry: y [nb, N] = x [nb, K] @ W^T for nb <= 32 rows through the batched step's
-    launchers (vox_hip_skinny_wmx4): the projection kernels and their slab sum, or the LM-head
-    kernel (head).  fmt 0: the bf16 fragment-major copy, fmt 1: the wmx4 fragment plane (raises
-    for a matrix that is not MXFP4-valued)"""
+def set_wpack_batch(on: bool):
+    """wpack13 fragment planes for the batched MFMA step, for models created from now on
+    (lossless, off by default; include/voxtral_hip.h)"""
+    if lib().vox_hip_set_wpack_batch(int(bool(on))) != 0:
+        _err("set_wpack_batch")
+
+
+def wpack_batch() -> int:
+    return lib().vox_hip_wpack_batch()
+
+
+def _skinny(name, W_bf16, x, fmt, head) -> np.ndarray:
+    """y [nb, N] = x [nb, K] @ W^T through the test entry vox_hip_<name>"""
     init()
     W = np.ascontiguousarray(W_bf16, np.uint16)
     xv = np.ascontiguousarray(x, np.float32)
@@ -338,9 +352,24 @@ def skinny_wmx4(W_bf16, x, fmt: int, head: bool = False) -> np.ndarray:
     assert xv.ndim == 2 and xv.shape[1] == K
     nb = xv.shape[0]
     y = np.empty((nb, N), np.float32)
-    if lib().vox_hip_skinny_wmx4(N, K, W.ctypes.data, fptr(xv), nb, fptr(y), int(fmt), int(bool(head))) != 0:
-        _err("skinny_wmx4")
+    if getattr(lib(), "vox_hip_" + name)(N, K, W.ctypes.data, fptr(xv), nb, fptr(y), int(fmt), int(bool(head))) != 0:
+        _err(name)
     return y
+
+
+def skinny_wpack(W_bf16, x, fmt: int, head: bool = False) -> np.ndarray:
+    """Test entry: skinny_wmx4 for the wpack13 fragment plane (vox_hip_skinny_wpack).  fmt 0: the
+    bf16 fragment-major copy, fmt 1: the wpack13 fragment plane (raises for a matrix outside the
+    format's exponent window)"""
+    return _skinny("skinny_wpack", W_bf16, x, fmt, head)
+
+
+def skinny_wmx4(W_bf16, x, fmt: int, head: bool = False) -> np.ndarray:
+    """Test entry: y [nb, N] = x [nb, K] @ W^T for nb <= 32 rows through the batched step's
+    launchers (vox_hip_skinny_wmx4): the projection kernels and their slab sum, or the LM-head
+    kernel (head).  fmt 0: the bf16 fragment-major copy, fmt 1: the wmx4 fragment plane (raises
+    for a matrix that is not MXFP4-valued)"""
+    return _skinny("skinny_wmx4", W_bf16, x, fmt, head)
 
 
 def set_gemmf_wait(ticks: int) -> int:
@@ -464,6 +493,14 @@ class Model:
         out = (ctypes.c_longlong * 4)()
         if lib().vox_hip_model_wmx4_batch_stats(self.h, out) != 0:
             _err("wmx4_batch_stats")
+        return dict(zip(("tensors", "plane_bytes", "bf16_bytes", "host_us"), (int(v) for v in out)))
+
+    def wpack_batch_stats(self) -> dict:
+        """The wpack13 fragment planes the batched step may stream (vox_hip_model_wpack_batch_stats):
+        tensors, plane bytes, the bf16 bytes they stand for, host microseconds"""
+        out = (ctypes.c_longlong * 4)()
+        if lib().vox_hip_model_wpack_batch_stats(self.h, out) != 0:
+            _err("wpack_batch_stats")
         return dict(zip(("tensors", "plane_bytes", "bf16_bytes", "host_us"), (int(v) for v in out)))
 
     def gemmf_q8_stats(self) -> list:
@@ -1008,6 +1045,16 @@ class Batch:
         fragment copies (off); the same bits.  Returns 0, or -1 with last_error() set (the model
         has no fragment planes, a begun call)."""
         return lib().vox_hip_batch_set_wmx4(self.h, int(bool(on)))
+
+    def set_wpack(self, on: bool) -> int:
+        """vox_hip_batch_set_wpack: the MFMA step streams the wpack13 fragment planes (on) or the
+        bf16 fragment copies (off); the same bits.  Returns 0, or -1 with last_error() set (the
+        model has no such planes, a begun call)."""
+        return lib().vox_hip_batch_set_wpack(self.h, int(bool(on)))
+
+    def wpack(self) -> int:
+        """vox_hip_batch_wpack: 1 while the MFMA step streams the wpack13 fragment planes, else 0"""
+        return lib().vox_hip_batch_wpack(self.h)
 
     def set_gemv_wmx4(self, on: bool) -> int:
         """vox_hip_batch_set_gemv_wmx4: the R-row GEMV step streams the wmx4 GEMV plane of every
