@@ -46,6 +46,10 @@ int vh_set_delay(vh_ctx_t *ctx, int delay_ms);
  * the batched decode step of 2..32 streams then reads instead of the bf16 fragment copies
  * (vox_hip_set_wpack_batch, voxtral_hip.h: the same tokens; off by default).  Returns 0. */
 int vh_set_wpack_batch(int on);
+/* Decode attention over FP8 decoder rings (vh_set_kv_dtype(ctx, 2)) on the matrix pipe past 256 keys
+ * (vox_hip_set_attn_mf8, voxtral_hip.h: exact products, another f32 summation order; off by default).
+ * Returns 0; -1 inside a begun batched call. */
+int vh_set_attn_mf8(int on);
 const char *vh_last_error(void);
 
 /* vox_stream_init (voxtral.c:1242-1286) */

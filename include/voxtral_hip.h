@@ -321,6 +321,33 @@ int vox_hip_model_gemmf_q8_stats(const vox_hip_model_t *m, long long out4[4]);
 int vox_hip_gemmf_q8_rows(int M, int N, int K, const float *x, const int8_t *Wq, const float *scales, float *y,
                           int fmt);
 
+/* Decode attention over FP8 (E4M3) decoder KV rings on the matrix pipe (k_attn_decode_mf8, DESIGN.md
+ * 35): process-wide, off by default, VOX_HIP_ATTN_MF8=1 gives the initial value.  With it on, every
+ * decode attention launch over FP8 rings at head_dim 128 with GQA groups of <= 4 heads that provides
+ * more than 256 keys -- one stream past the short-context kernel, the R-row GEMV step, the <= 32-slot
+ * step and the wide step, with shared or per-slot (kv_grow) ring capacities -- takes the MFMA kernel:
+ * every E4M3 code is a bf16 value and queries and softmax weights enter as three bf16 planes, so each
+ * product is exact and only the f32 summation order differs from the default kernel.  Launches of
+ * <= 256 keys, half and f32 rings and head_dim 64 are what they were.  Step graphs carry the mode, so a
+ * change between calls recaptures; inside a begun batched call (vox_hip_batch_begin_rows ..
+ * vox_hip_batch_finish) vox_hip_set_attn_mf8 is refused (-1).  Returns 0. */
+int vox_hip_set_attn_mf8(int on);
+int vox_hip_attn_mf8(void);
+/* out6: launches of the MFMA kernel enqueued by this process, per form: [0] one stream, [1] the
+ * unfused batch (R-row GEMV step), [2] the <= 32-slot step, [3] the same over per-slot capacities,
+ * [4] the wide step, [5] the same over per-slot capacities.  A launch captured into a step graph
+ * counts once, at capture. */
+int vox_hip_attn_mf8_stats(long long out6[6]);
+/* Test entry: the unfused decode attention of nb <= 32 streams over caller-supplied FP8 ring codes
+ * (host pointers): q[nb][H][128] f32, kcodes / vcodes[nb][cap][KVH][128], pos[nb] the streams' last
+ * positions, out[nb][H][128].  The launch provides the key splits of the longest context, at least
+ * two (the long-context grid).  mode 0: the default kernel; 1: k_attn_decode_mf8, whatever the
+ * switch says. */
+int vox_hip_attn_decode_kv8(float *out, const float *q, const uint8_t *kcodes, const uint8_t *vcodes, int nb, int cap,
+                            const int *pos, int window, int H, int KVH, int mode);
+/* Test entry: bits[256] = every E4M3 code as the bf16 that k_attn_decode_mf8's convert makes of it. */
+int vox_hip_attn_mf8_codes(uint16_t *bits);
+
 /* Per-stream device state: encoder/decoder rolling KV, conv-stem tails, adapter buffer,
  * scratch and a HIP stream.  One model serves many streams. */
 vox_hip_stream_t *vox_hip_stream_create(vox_hip_model_t *m);

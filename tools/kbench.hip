@@ -15,7 +15,7 @@
 #include "../voxtral.c_amd/csrc/vox_wpack.h"
 
 using namespace vox;
-namespace vox { extern int g_skf_r, g_skf_nw, g_skf_d, g_skl_nw, g_gemv_rb, g_attn_lw, g_attn_blocks, g_attn_short, g_gemmf_rb, g_gemmf_minu, g_gemmf_wr, g_gemmf_order, g_mel_fpb, g_skf2_r, g_attn_kvfast, g_attn_bsplit, g_gemv_maxb; }
+namespace vox { extern int g_skf_r, g_skf_nw, g_skf_d, g_skl_nw, g_gemv_rb, g_attn_lw, g_attn_blocks, g_attn_short, g_gemmf_rb, g_gemmf_minu, g_gemmf_wr, g_gemmf_order, g_mel_fpb, g_skf2_r, g_attn_kvfast, g_attn_bsplit, g_gemv_maxb, g_attn_mf8_range; }
 #ifdef VOX_GEMV_STAMPS
 namespace vox { hipError_t gemv_set_stamps(unsigned long long* p); }
 #endif
@@ -1525,6 +1525,20 @@ int main(int argc, char** argv) {
                                               part, y, splits, st, kvt));
                         l++;
                     }, 260, st), (double)L * DKV * 2 * esz);
+                // the same FP8 rings through k_attn_decode_mf8 (past 256 keys), per key-range length
+                for (int rk : {128, 256, 512, 1024}) {
+                    if (kvt != 2 || splits < 2) continue;
+                    g_attn_mf8_range = rk;
+                    attn_mf8_set(1);
+                    snprintf(nm, sizeof nm, "attn decode L=%d mf8 range %d 26 layers", L, rk);
+                    add(nm, timeit([&] {
+                            CK(launch_attn_decode(HD, x, Ks[l % NLd], Vs[l % NLd], rcap, state, 0, 8192, 0.088f, H, KVH,
+                                                  part, y, splits, st, kvt));
+                            l++;
+                        }, 260, st), (double)L * DKV * 2 * esz);
+                    attn_mf8_set(0);
+                    g_attn_mf8_range = 256;
+                }
             }
             for (int l = 0; l < NLd; l++) {
                 CK(hipFree(Ks[l]));

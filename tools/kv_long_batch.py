@@ -8,6 +8,8 @@ count in --streams (the largest is primed, the smaller counts time a prefix of t
 Weights are read once per step for all rows, every row reads its own rings: the KV bytes per step
 are streams x keys x 212,992 / 106,496 / 53,248 B.  VOX_HIP_WMX4=2 VOX_HIP_WMX4_BATCH=1 in the
 environment selects the MXFP4 fragment planes for the weights (read at model creation).
+--attn-mf8 times every FP8 stream count twice, with vox_hip.set_attn_mf8 off and on (k_attn_decode_mf8,
+DESIGN.md 35; the "attn_mf8" column).
 
 Prints one JSON line per (element type, stream count)."""
 import argparse
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--keys", type=int, default=8192)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--attn-mf8", action="store_true")
     args = ap.parse_args()
     import vox_hip
     from vox_weights import VOXTRAL_4B, synth_weights
@@ -40,7 +43,7 @@ def main():
     model = vox_hip.Model(cfg, w)
     del w
     nmax = max(args.streams)
-    rows = args.keys + args.steps * len(args.streams) + 64
+    rows = args.keys + (args.steps + 4) * len(args.streams) * (2 if args.attn_mf8 else 1) + 64
     rng = np.random.default_rng(77)
     mel = rng.uniform(-0.6, 1.4, size=(8 * rows, cfg.mel_bins)).astype(np.float32)
     mel_dev = vox_hip.DeviceArray(mel)
@@ -60,7 +63,9 @@ def main():
             n = min(4096, prime - done)
             b.decode(ss, max_steps=n, stop_at_eos=False)
             done += n
-        for n in sorted(args.streams, reverse=True):
+        modes = [0, 1] if args.attn_mf8 and t == 2 else [0]
+        for n, mf8 in [(n, f) for n in sorted(args.streams, reverse=True) for f in modes]:
+            vox_hip.set_attn_mf8(bool(mf8))
             sub = ss[:n]
             b.decode(sub, max_steps=4, stop_at_eos=False)            # this bucket's graphs
             for s in sub:
@@ -78,7 +83,8 @@ def main():
                 "ms_per_step": round(dt * 1e3 / args.steps, 4), "tokens_per_s": round(n * args.steps / dt, 1),
                 "kv_bytes_per_step": kv_step, "kv_gbs": round(kv_step / (dt / args.steps) / 1e9, 1),
                 "ring_gb_per_stream": round((cfg.dec_window + 64) * kvb[t] / 1e9, 3),
-                "wmx4": vox_hip.wmx4(), "wmx4_batch": vox_hip.wmx4_batch()}), flush=True)
+                "attn_mf8": mf8, "wmx4": vox_hip.wmx4(), "wmx4_batch": vox_hip.wmx4_batch()}), flush=True)
+        vox_hip.set_attn_mf8(False)
         b.close()
         for s in ss:
             s.close()

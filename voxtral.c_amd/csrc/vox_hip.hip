@@ -37,6 +37,7 @@ static thread_local std::string g_err;
 static int g_inited = 0;
 static size_t g_mem_used = 0;
 
+static int g_begun_calls = 0;  // begun, unfinished batched calls of the process (vox_hip_set_attn_mf8 refuses inside one)
 static int set_err(const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1011,6 +1012,7 @@ struct vox_hip_stream {
     float alt_cutoff;
     int graph_alt;           // alt mode the step graphs were captured with
     int graph_rope_gen;      // model rope table generation the step graphs were captured with
+    int graph_attn_mf8;      // vox_hip_attn_mf8() the step graphs were captured with
     int *pidx, *state, *tokens;   // tokens: ring of tokens_cap ids, index = step % tokens_cap
     int* twin_state;              // decoder_full_step's argmax state (the graph state stays untouched)
     int dec_rows_cap, tokens_cap;
@@ -2897,6 +2899,7 @@ static int build_step_graph(vox_hip_stream_t* s, int gi) {
     s->graph_ready |= 1 << gi;
     s->graph_alt = s->n_alt > 1;
     s->graph_rope_gen = s->m->rope_gen;
+    s->graph_attn_mf8 = attn_mf8_mode();
     return 0;
 }
 
@@ -2949,7 +2952,9 @@ static int run_steps(vox_hip_stream_t* s, int n, int pos0) {
             if (enqueue_graph_step(s, splits)) return -1;
         return 0;
     }
-    if (s->graph_ready && (s->graph_alt != (s->n_alt > 1) || s->graph_rope_gen != s->m->rope_gen)) s->graph_ready = 0;
+    if (s->graph_ready && (s->graph_alt != (s->n_alt > 1) || s->graph_rope_gen != s->m->rope_gen ||
+                           s->graph_attn_mf8 != attn_mf8_mode()))
+        s->graph_ready = 0;
     if (!(s->graph_ready & (1 << gi)) && build_step_graph(s, gi)) return -1;
     for (int i = 0; i < n; i++) CK(hipGraphLaunch(s->step_exec[gi], s->st));
     return 0;
@@ -3207,6 +3212,99 @@ extern "C" int vox_hip_kv8_convert(const float* x, int n, uint8_t* codes, float*
     if (db) hipFree(db);
     if (dc) hipFree(dc);
     return rc;
+}
+
+// Decode attention over FP8 rings on the matrix pipe (k_attn_decode_mf8): process-wide
+// and off by default (VOX_HIP_ATTN_MF8=1 gives the initial value).  Every step graph carries the
+// mode it was captured with, so a change between calls recaptures; inside a begun batched call
+// (whose steps replay one graph) the setter is refused.
+extern "C" int vox_hip_set_attn_mf8(int on) {
+    if (g_begun_calls > 0) return set_err("set_attn_mf8: a begun batched call was not finished");
+    attn_mf8_set(on);
+    return 0;
+}
+extern "C" int vox_hip_attn_mf8(void) { return attn_mf8_mode(); }
+extern "C" int vox_hip_attn_mf8_stats(long long out6[6]) {
+    if (!out6) return set_err("attn_mf8_stats: null argument");
+    static_assert(ATTN_MF8_FORMS == 6, "vox_hip_attn_mf8_stats: six forms");
+    attn_mf8_counts(out6);
+    return 0;
+}
+
+// The unfused decode attention over caller-supplied FP8 ring codes (tests): stream b of nb has the
+// f32 query rows q[b][H][128], the rings kcodes / vcodes[b][cap][KVH][128] and the position pos[b];
+// out[b][H][128].  The launch provides the key splits of the longest context, at least 2 (the
+// long-context grid).  mode 0: k_attn_decode<.., kv8_t>; 1: k_attn_decode_mf8.
+extern "C" int vox_hip_attn_decode_kv8(float* out, const float* q, const uint8_t* kcodes, const uint8_t* vcodes, int nb,
+                                       int cap, const int* pos, int window, int H, int KVH, int mode) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (!out || !q || !kcodes || !vcodes || !pos) return set_err("attn_decode_kv8: null argument");
+    if (nb < 1 || nb > VOX_MAX_BATCH || KVH < 1 || H % KVH || H / KVH > 4 || window < 1 || cap < window || cap < 32 ||
+        (mode != 0 && mode != 1))
+        return set_err("attn_decode_kv8: bad arguments");
+    if (g_begun_calls > 0) return set_err("attn_decode_kv8: a begun batched call was not finished");
+    const int hd = 128;
+    int need = 2;
+    for (int b = 0; b < nb; b++) {
+        if (pos[b] < 0) return set_err("attn_decode_kv8: negative position");
+        need = std::max(need, (std::min(pos[b] + 1, window) + ATT_BLOCK_KEYS - 1) / ATT_BLOCK_KEYS);
+    }
+    if (need > attn_maxsplits(window)) return set_err("attn_decode_kv8: window %d has no %d key splits", window, need);
+    const size_t ring = (size_t)cap * KVH * hd, qn = (size_t)H * hd;
+    const size_t partn = (size_t)H * attn_maxch(window) * (hd + 2) + KVH;
+    uint8_t *dk = nullptr, *dv = nullptr;
+    float *dq = nullptr, *dout = nullptr, *dpart = nullptr;
+    int* dpos = nullptr;
+    const int was = attn_mf8_mode();
+    int rc = -1;
+    do {
+        if (hipMalloc((void**)&dk, ring * nb) != hipSuccess || hipMalloc((void**)&dv, ring * nb) != hipSuccess ||
+            hipMalloc((void**)&dq, qn * nb * 4) != hipSuccess || hipMalloc((void**)&dout, qn * nb * 4) != hipSuccess ||
+            hipMalloc((void**)&dpart, partn * nb * 4) != hipSuccess || hipMalloc((void**)&dpos, (size_t)nb * 4) != hipSuccess) {
+            set_err("attn_decode_kv8: out of device memory");
+            break;
+        }
+        AttnPtrs p;
+        memset(&p, 0, sizeof p);
+        for (int b = 0; b < nb; b++) {
+            p.q[b] = dq + b * qn;
+            p.Kc[b] = reinterpret_cast<const float*>(dk + b * ring);
+            p.Vc[b] = reinterpret_cast<const float*>(dv + b * ring);
+            p.state[b] = dpos + b;
+            p.part[b] = dpart + b * partn;
+            p.out[b] = dout + b * qn;
+        }
+        attn_mf8_set(mode);
+        const bool ok = hipMemcpy(dk, kcodes, ring * nb, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dv, vcodes, ring * nb, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dq, q, qn * nb * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dpos, pos, (size_t)nb * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemset(dpart, 0, partn * nb * 4) == hipSuccess && hipMemset(dout, 0, qn * nb * 4) == hipSuccess &&
+                        launch_attn_decode_batch(hd, p, nb, cap, window, 1.0f / sqrtf((float)hd), H, KVH, need, nullptr,
+                                                 KV_FP8) == hipSuccess &&
+                        hipDeviceSynchronize() == hipSuccess &&
+                        hipMemcpy(out, dout, qn * nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        attn_mf8_set(was);
+        if (!ok) {
+            set_err("attn_decode_kv8: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+        rc = 0;
+    } while (0);
+    for (void* d : {(void*)dk, (void*)dv, (void*)dq, (void*)dout, (void*)dpart, (void*)dpos})
+        if (d) hipFree(d);
+    return rc;
+}
+// bits[256]: every E4M3 code through k_attn_decode_mf8's FP8 -> bf16 convert
+extern "C" int vox_hip_attn_mf8_codes(uint16_t* bits) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (!bits) return set_err("attn_mf8_codes: null argument");
+    uint16_t* d = nullptr;
+    if (hipMalloc((void**)&d, 512) != hipSuccess) return set_err("attn_mf8_codes: out of device memory");
+    const bool ok = launch_attn_mf8_codes(d, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(bits, d, 512, hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(d);
+    return ok ? 0 : set_err("attn_mf8_codes: %s", hipGetErrorString(hipGetLastError()));
 }
 
 extern "C" int vox_hip_stream_set_profiling(vox_hip_stream_t* s, int enable) {
@@ -3876,6 +3974,7 @@ struct vox_hip_batch {
     // than window + slack (vox_hip_model_set_kv_grow) launch the ragged attention instances
     hipGraphExec_t gexec[4][12][6][STEP_GRAPHS];
     int grope_gen;
+    int gattn_mf8;                 // vox_hip_attn_mf8() the step graphs (every bucket and step kind) were captured with
     // the MFMA step streams the wmx4 fragment planes of the tensors that have one
     // (vox_hip_batch_set_wmx4); the graphs hold the weight pointers, hence the key above
     int wmx4;
@@ -3965,11 +4064,13 @@ static int batch_park(vox_hip_batch_t* b, float* p) {
 static void batch_hold(vox_hip_batch_t* b) {
     for (int i = 0; i < b->call.n; i++) b->call.streams[i]->held = b;
     b->m->begun_calls++;
+    g_begun_calls++;
 }
 static void batch_release(vox_hip_batch_t* b) {
     for (int i = 0; i < b->call.n; i++)
         if (b->call.streams[i]->held == b) b->call.streams[i]->held = nullptr;
     b->m->begun_calls--;
+    g_begun_calls--;
     for (int i = 0; i < b->n_parked; i++) dfree(b->parked[i]);
     b->n_parked = 0;
 }
@@ -4560,9 +4661,10 @@ static int batch_run(vox_hip_batch_t* b, int nb, int gb, int gi, int splits, int
         b->n_replays += steps;
         return 0;
     }
-    if (b->grope_gen != b->m->rope_gen) {
+    if (b->grope_gen != b->m->rope_gen || b->gattn_mf8 != attn_mf8_mode()) {
         batch_drop_graphs(b);
         b->grope_gen = b->m->rope_gen;
+        b->gattn_mf8 = attn_mf8_mode();
     }
     const int mr = mixed + 2 * ragged;
     hipGraphExec_t& ge = wide ? b->gwexec[mr][kvt][gb - 6][gi]

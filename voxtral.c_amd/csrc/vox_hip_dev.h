@@ -346,6 +346,22 @@ __device__ __forceinline__ void kv_st2_rt(float* base, size_t e, float a, float 
     else kv_st2(base + e, a, b);
 }
 
+// per-row operands of the decode attention kernels (k_attn_decode, k_attn_decode_mf8) by argument
+// type: AttnPtrs (pointer arrays; rings from the arrays or, with slots, from the slot table) or
+// AttnSlots (slot table only, base + stride)
+__device__ __forceinline__ const float* attn_q(const AttnPtrs& P, int z) { return P.q[z]; }
+__device__ __forceinline__ float* attn_part(const AttnPtrs& P, int z) { return P.part[z]; }
+__device__ __forceinline__ float* attn_out(const AttnPtrs& P, int z) { return P.out[z]; }
+__device__ __forceinline__ const char* attn_k(const AttnPtrs& P, int z) { return (const char*)P.Kc[z]; }
+__device__ __forceinline__ const char* attn_v(const AttnPtrs& P, int z) { return (const char*)P.Vc[z]; }
+__device__ __forceinline__ const int* attn_state(const AttnPtrs& P, int z) { return P.state[z]; }
+__device__ __forceinline__ const float* attn_q(const AttnSlots& P, int z) { return P.q + (size_t)z * P.q_ld; }
+__device__ __forceinline__ float* attn_part(const AttnSlots& P, int z) { return P.part + (size_t)z * P.part_ld; }
+__device__ __forceinline__ float* attn_out(const AttnSlots& P, int z) { return P.out + (size_t)z * P.out_ld; }
+__device__ __forceinline__ const char* attn_k(const AttnSlots&, int) { return nullptr; }
+__device__ __forceinline__ const char* attn_v(const AttnSlots&, int) { return nullptr; }
+__device__ __forceinline__ const int* attn_state(const AttnSlots&, int) { return nullptr; }
+
 // stream_fill_alts (voxtral.c:955-1010) partials for one logit: running max / sum of
 // exp for the softmax, and an ascending-id-stable top-4 of ids >= TOKEN_TEXT_MIN (rows
 // arrive in ascending order, so a strict '>' keeps the lower id first on ties).

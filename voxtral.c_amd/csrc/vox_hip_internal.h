@@ -250,6 +250,26 @@ hipError_t launch_rope_kv_rows(const float* qkv, int N, int qd, int kvd, int hd,
 hipError_t launch_attn_rows(int hd, const float* Q, const EncRows& er, int N, int cap, float* O, int H, int KVH,
                             int window, float scale, float* ws, size_t ws_elems, hipStream_t st, uint16_t* xs = nullptr,
                             int kvt = 0);
+constexpr int ATT_MAX_PARTS = 128;  // partials per head the merging block combines
+// Decode attention over FP8 rings on the matrix pipe (k_attn_decode_mf8, vox_hip_attn_mf8.hip):
+// the process-wide opt-in (VOX_HIP_ATTN_MF8=1 gives the initial value) and the launchers that
+// attn_launch<kv8_t> / attn_batch take with it on at head_dim 128 and splits > 1.  Partials, arrival counts
+// and outputs are k_attn_decode's; the counts are enqueued launches per form (a captured launch counts once).
+enum { ATTN_MF8_SINGLE = 0, ATTN_MF8_BATCH, ATTN_MF8_PTRS, ATTN_MF8_PTRS_RAG, ATTN_MF8_SLOTS, ATTN_MF8_SLOTS_RAG, ATTN_MF8_FORMS };
+int attn_mf8_mode();
+void attn_mf8_set(int on);
+void attn_mf8_counts(long long* out);  // ATTN_MF8_FORMS entries
+hipError_t launch_attn_mf8(const AttnPtrs& p, int nb, int cap, int pos_host, int window, float scale, int H, int KVH,
+                           int splits, hipStream_t st, int form);
+hipError_t launch_attn_mf8_fused(const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                                 int KVH, int splits, hipStream_t st);
+hipError_t launch_attn_mf8_fused(const AttnPtrsRag& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                                 int KVH, int splits, hipStream_t st);
+hipError_t launch_attn_mf8_fused(const AttnSlots& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                                 int KVH, int splits, hipStream_t st);
+hipError_t launch_attn_mf8_fused(const AttnSlotsRag& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
+                                 int KVH, int splits, hipStream_t st);
+hipError_t launch_attn_mf8_codes(uint16_t* bits, hipStream_t st);  // bits[256]: every code through the kernel's convert
 constexpr int STEP_GRAPHS = 8;       // step graphs by attention split count 1, 2, 4, ..., 128
 hipError_t launch_attn_batch_dbg(const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
                                  int KVH, int splits, hipStream_t st);

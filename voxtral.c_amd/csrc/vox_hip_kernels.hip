@@ -721,23 +721,8 @@ constexpr int ATT_BK = ATT_CH * ATT_WAVES;  // keys per short-context block
 constexpr int ATT_LWAVES = 8;   // waves per long-context block (512 threads)
 constexpr int ATT_LBK = ATT_CH * ATT_LWAVES;  // keys per long-context block
 constexpr int ATT_MIN_BK = 64;      // smallest block (kbench variant): sizes the partials
-constexpr int ATT_MAX_PARTS = 128;  // partials per head the merging block combines
 
-// per-row operands of k_attn_decode by argument type: AttnPtrs (pointer arrays; rings from the
-// arrays or, with slots, from the slot table) or AttnSlots (slot table only, base + stride)
-__device__ __forceinline__ const float* attn_q(const AttnPtrs& P, int z) { return P.q[z]; }
-__device__ __forceinline__ float* attn_part(const AttnPtrs& P, int z) { return P.part[z]; }
-__device__ __forceinline__ float* attn_out(const AttnPtrs& P, int z) { return P.out[z]; }
-__device__ __forceinline__ const char* attn_k(const AttnPtrs& P, int z) { return (const char*)P.Kc[z]; }
-__device__ __forceinline__ const char* attn_v(const AttnPtrs& P, int z) { return (const char*)P.Vc[z]; }
-__device__ __forceinline__ const int* attn_state(const AttnPtrs& P, int z) { return P.state[z]; }
-__device__ __forceinline__ const float* attn_q(const AttnSlots& P, int z) { return P.q + (size_t)z * P.q_ld; }
-__device__ __forceinline__ float* attn_part(const AttnSlots& P, int z) { return P.part + (size_t)z * P.part_ld; }
-__device__ __forceinline__ float* attn_out(const AttnSlots& P, int z) { return P.out + (size_t)z * P.out_ld; }
-__device__ __forceinline__ const char* attn_k(const AttnSlots&, int) { return nullptr; }
-__device__ __forceinline__ const char* attn_v(const AttnSlots&, int) { return nullptr; }
-__device__ __forceinline__ const int* attn_state(const AttnSlots&, int) { return nullptr; }
-
+// (the per-row operand accessors attn_q .. attn_state by argument type: vox_hip_dev.h)
 template <int HD, int HPB, int DBG = 0, int FUSE = 0, int NWV = ATT_WAVES, class KT = float, class AP = AttnPtrs>
 __global__ __launch_bounds__(NWV * 64) void k_attn_decode(const AP P, int cap, int pos_host,
                                                           int window, float scale, int H, int KVH,
@@ -3307,11 +3292,15 @@ static void attn_long(const AttnPtrs& p, int nb, int cap, int pos_host, int wind
 // block per CU had read K/V at the per-CU rate (L = 1000: 32 blocks, 12.3 us; now 10.0).
 template <class KT>
 static hipError_t attn_launch(int hd, const AttnPtrs& p, int nb, int cap, int pos_host, int window, float scale,
-                              int H, int KVH, int splits, hipStream_t st) {
+                              int H, int KVH, int splits, hipStream_t st, int mf8_form) {
     const int maxs = attn_maxch(window);
     if (H % KVH || H / KVH > 4 || maxs > ATT_MAX_PARTS || splits < 1 || splits > attn_maxsplits(window) || nb < 1 ||
         nb > VOX_MAX_BATCH)
         return hipErrorInvalidValue;
+    // FP8 rings past 256 keys with vox_hip_set_attn_mf8: the MFMA kernel
+    if constexpr (std::is_same_v<KT, kv8_t>)
+        if (hd == 128 && splits > 1 && attn_mf8_mode())
+            return launch_attn_mf8(p, nb, cap, pos_host, window, scale, H, KVH, splits, st, mf8_form);
     // batches of >= 4 streams: one block per (stream, kv head), K/V read once for its query
     // heads (16 streams: 15.8 -> ~10 us per layer); a single stream needs the 32 blocks
 #define VOX_ATT(HD)                                                                                        \
@@ -3369,14 +3358,14 @@ hipError_t launch_attn_decode(int hd, const float* q, const float* Kc, const flo
         AttnPtrs p;
         memset(&p, 0, sizeof p);
         p.q[0] = q; p.Kc[0] = Kc; p.Vc[0] = Vc; p.state[0] = state; p.part[0] = part; p.out[0] = out;
-        return attn_launch<KT>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st);
+        return attn_launch<KT>(hd, p, 1, cap, pos_host, window, scale, H, KVH, splits, st, ATTN_MF8_SINGLE);
     });
 }
 
 hipError_t launch_attn_decode_batch(int hd, const AttnPtrs& p, int nb, int cap, int window, float scale,
                                     int H, int KVH, int splits, hipStream_t st, int kvt) {
     return kv_ring(kvt, hd, [&](auto ring) {
-        return attn_launch<typename decltype(ring)::type>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st);
+        return attn_launch<typename decltype(ring)::type>(hd, p, nb, cap, 0, window, scale, H, KVH, splits, st, ATTN_MF8_BATCH);
     });
 }
 
@@ -3415,6 +3404,9 @@ static hipError_t attn_batch(int hd, const AP& p, const AttnFuse& f, int nb, int
     }
     return kv_ring(kvt, hd, [&](auto ring) {
         using KT = typename decltype(ring)::type;
+        // FP8 rings past 256 keys with vox_hip_set_attn_mf8: the MFMA kernel
+        if constexpr (std::is_same_v<KT, kv8_t>)
+            if (splits > 1 && attn_mf8_mode()) return launch_attn_mf8_fused(p, f, nb, cap, window, scale, H, KVH, splits, st);
         if (whole)
             hipLaunchKernelGGL((k_attn_decode<128, 4, 0, 1, ATT_WAVES, KT, AP>), dim3(1, KVH, nb), dim3(1024), 0, st, p,
                                cap, 0, window, scale, H, KVH, maxs, f);

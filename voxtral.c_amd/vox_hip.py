@@ -134,6 +134,7 @@ EXPORTS = [
     "vox_hip_set_wpack_batch", "vox_hip_wpack_batch", "vox_hip_model_wpack_batch_stats", "vox_hip_batch_set_wpack",
     "vox_hip_batch_wpack", "vox_hip_skinny_wpack",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
+    "vox_hip_set_attn_mf8", "vox_hip_attn_mf8", "vox_hip_attn_mf8_stats", "vox_hip_attn_decode_kv8", "vox_hip_attn_mf8_codes",
     "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -204,6 +205,9 @@ def lib():
         "vox_hip_set_gemm_planes": (I, [I]), "vox_hip_gemm_planes": (I, []),
         "vox_hip_set_gemmf_wait": (I, [I]),
         "vox_hip_set_gemmf_q8": (I, [I]), "vox_hip_gemmf_q8": (I, []),
+        "vox_hip_set_attn_mf8": (I, [I]), "vox_hip_attn_mf8": (I, []),
+        "vox_hip_attn_mf8_stats": (I, [ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_attn_decode_kv8": (I, [fp, fp, P, P, I, I, P, I, I, I, I]), "vox_hip_attn_mf8_codes": (I, [P]),
         "vox_hip_model_gemmf_q8_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_gemmf_q8_rows": (I, [I, I, I, fp, P, fp, fp, I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -383,6 +387,55 @@ def set_gemmf_q8(on: bool):
     (vox_hip_set_gemmf_q8; off by default, VOX_HIP_GEMMF_Q8=1 gives the initial value)"""
     if lib().vox_hip_set_gemmf_q8(int(bool(on))) != 0:
         _err("set_gemmf_q8")
+
+
+def set_attn_mf8(on: bool):
+    """decode attention over FP8 decoder rings past 256 keys on the matrix pipe, process-wide
+    (vox_hip_set_attn_mf8; off by default, VOX_HIP_ATTN_MF8=1 gives the initial value; refused
+    inside a begun batched call)"""
+    if lib().vox_hip_set_attn_mf8(int(bool(on))) != 0:
+        _err("set_attn_mf8")
+
+
+def attn_mf8() -> int:
+    return lib().vox_hip_attn_mf8()
+
+
+ATTN_MF8_FORMS = ("single", "batch", "ptrs", "ptrs_rag", "slots", "slots_rag")
+
+
+def attn_mf8_stats() -> dict:
+    """vox_hip_attn_mf8_stats: launches of k_attn_decode_mf8 enqueued per form (a captured launch
+    counts once)"""
+    out = (ctypes.c_longlong * 6)()
+    if lib().vox_hip_attn_mf8_stats(out) != 0:
+        _err("attn_mf8_stats")
+    return dict(zip(ATTN_MF8_FORMS, out))
+
+
+def attn_decode_kv8(q, kcodes, vcodes, pos, window: int, mode: int) -> np.ndarray:
+    """vox_hip_attn_decode_kv8: the unfused decode attention over FP8 ring codes.  q [nb, H, 128]
+    f32, kcodes / vcodes [nb, cap, KVH, 128] uint8, pos [nb]; mode 0 the default kernel, 1
+    k_attn_decode_mf8 -> [nb, H, 128]"""
+    q = np.ascontiguousarray(q, np.float32)
+    kc, vc = np.ascontiguousarray(kcodes, np.uint8), np.ascontiguousarray(vcodes, np.uint8)
+    ps = np.ascontiguousarray(pos, np.int32)
+    nb, H, _ = q.shape
+    _, cap, KVH, _ = kc.shape
+    assert q.shape[2] == 128 and kc.shape == vc.shape == (nb, cap, KVH, 128) and ps.shape == (nb,)
+    out = np.empty_like(q)
+    if lib().vox_hip_attn_decode_kv8(fptr(out), fptr(q), kc.ctypes.data, vc.ctypes.data, nb, cap, ps.ctypes.data,
+                                     int(window), H, KVH, int(mode)) != 0:
+        _err("attn_decode_kv8")
+    return out
+
+
+def attn_mf8_codes() -> np.ndarray:
+    """vox_hip_attn_mf8_codes: every E4M3 code as the bf16 bits k_attn_decode_mf8's convert gives"""
+    bits = np.empty(256, np.uint16)
+    if lib().vox_hip_attn_mf8_codes(bits.ctypes.data) != 0:
+        _err("attn_mf8_codes")
+    return bits
 
 
 def gemmf_q8() -> int:
