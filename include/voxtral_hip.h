@@ -182,6 +182,19 @@ int vox_hip_model_wpack_stats(const vox_hip_model_t *m, vox_hip_wpack_stats_t *o
  * one did (packed = 0, W outside the wpack13 window, or W refused by the wmx4 scan), -1 on
  * error. */
 int vox_hip_gemv_wpack(int rows, int K, const uint16_t *W, const float *x, float *y, int packed);
+/* Compact side planes (on by default).  A wpack13 tensor whose rows span more than one K round
+ * of 256 chunks and end inside the last one (K = 3072: 1.5 rounds, K = 9216: 4.5) keeps side
+ * slots only for the chunks that exist (csrc/vox_wpack.h): its planes are 0.8125 of the bf16 bytes
+ * (W2, in 2-row groups: half a spare dword per lane of the last round above that) instead of
+ * 0.833.  The GEMV's registers, arithmetic and outputs are the padded plane's.  Shapes with one
+ * round or whole rounds keep the padded plane.  vox_hip_set_wpack_compact(0) keeps every side
+ * plane of models created from now on padded (VOX_HIP_WPACK_COMPACT=0 gives that initial value);
+ * it returns 0.  vox_hip_gemv_wpack_rb: vox_hip_gemv_wpack in row groups of rb = 2, 4 or 8 rows
+ * (0: the shape's own; not with packed = 2) and with the side plane compact or padded. */
+int vox_hip_set_wpack_compact(int on);
+int vox_hip_wpack_compact(void);
+int vox_hip_gemv_wpack_rb(int rows, int K, const uint16_t *W, const float *x, float *y, int packed, int rb,
+                          int compact);
 /* wmx4 (no reference counterpart; opt-in): MXFP4 weight streaming for the single-stream decode
  * GEMVs, 5 stored bits per weight.
  *

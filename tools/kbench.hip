@@ -337,6 +337,8 @@ int main(int argc, char** argv) {
         // one run so that the spread between repeats of one format is on the same page.
         // First, per shape, a seeded random matrix is packed on the host and the two kernels'
         // outputs are compared bit for bit (the LM head at 65536 rows).
+        // A shape with a compact side plane (vox_wpack.h) is checked and timed with both planes:
+        // "packed" is the compact plane (the product's), "padded" the padded one.
         // VOX_KB_WPACK_SHAPES=w13 (or any list of qkv,wo,w13,w2,lm) limits the shapes.
         struct S { const char* n; int pro, epi, K, rows, crows; std::vector<uint16_t*>* w; };
         const char* only = getenv("VOX_KB_WPACK_SHAPES");
@@ -347,10 +349,14 @@ int main(int argc, char** argv) {
                     S{"lm", PRO_NORM, EPI_LOGITS, D, V, 65536, &lm1}}) {
             if (only && !strstr(only, o.n)) continue;
             const int rb = gemv_rowgroup(o.rows), sw = vox_wpack13_side_words(o.K, rb), swiglu = o.epi == EPI_SWIGLU;
-            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sideb = (size_t)o.rows / rb * 256 * sw * 4;
-            auto run = [&](const uint16_t* W, const void* pm, const void* ps, int d, int rows, float* out) {
+            const int cpt = vox_wpack13_side_is_compact(o.K, rb);
+            const size_t gwc = (size_t)vox_wpack13_side_compact_group_words(o.K, rb);
+            const size_t mainb = (size_t)o.rows * o.K / 8 * 12, sidepb = (size_t)o.rows / rb * 256 * sw * 4;
+            const size_t sideb = (size_t)o.rows / rb * gwc * 4;  // the compact plane (the padded one where there is none)
+            auto run = [&](const uint16_t* W, const void* pm, const void* ps, int d, int rows, float* out, int compact = 0) {
                 GemvArgs a;
                 memset(&a, 0, sizeof a);
+                a.wp_compact = compact;
                 a.x = x; a.K = o.K; a.W = W; a.wp_main = pm; a.wp_side = ps; a.wp_d = d; a.rows = rows; a.norm_w = normw;
                 a.ada = ada; a.eps = 1e-5f; a.y = out; a.qd = DQ; a.kvd = DKV; a.hd = HD; a.rope = rope; a.state = state;
                 a.Kc = Kc; a.Vc = Vc; a.cap = cap; a.part_val = pv; a.part_idx = pi;
@@ -374,39 +380,49 @@ int main(int argc, char** argv) {
                 CK(hipMemcpy(x, hx.data(), DH * 4, hipMemcpyHostToDevice));
                 int emin, emax;
                 if (!vox_wpack13_scan_(hw.data(), hw.size(), &emin, &emax, &d)) { printf("%s: not packable\n", o.n); return 1; }
-                std::vector<uint32_t> hm((size_t)rows * o.K / 8 * 3), hs((size_t)rows / rb * 256 * sw);
+                std::vector<uint32_t> hm((size_t)rows * o.K / 8 * 3), hs((size_t)rows / rb * 256 * sw), hc((size_t)rows / rb * gwc);
                 std::vector<uint8_t> hb((size_t)rows * o.K / 8);
                 vox_wpack13_pack_(hw.data(), rows, o.K, d, hm.data(), hb.data());
                 vox_wpack13_side_layout_(hb.data(), rows, o.K, rb, swiglu, hs.data());
+                vox_wpack13_side_compact_layout_(hb.data(), rows, o.K, rb, swiglu, hc.data());
                 uint16_t* dw = (uint16_t*)dmalloc(hw.size() * 2, 0);
                 uint32_t* dm = (uint32_t*)dmalloc(hm.size() * 4, 0);
                 uint32_t* ds = (uint32_t*)dmalloc(hs.size() * 4, 0);
+                uint32_t* dc = (uint32_t*)dmalloc(hc.size() * 4, 0);
+                CK(hipMemcpy(dc, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
                 CK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
                 CK(hipMemcpy(dm, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
                 CK(hipMemcpy(ds, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
                 const int ny = swiglu ? rows / 2 : rows;
                 float* y2 = (float*)dmalloc((size_t)V * 4, 0);
-                std::vector<float> y0(ny), y1(ny);
+                float* y3 = (float*)dmalloc((size_t)V * 4, 0);
+                std::vector<float> y0(ny), y1(ny), yc(ny);
                 CK(hipMemset(y, 0, (size_t)ny * 4));
                 run(dw, nullptr, nullptr, 0, rows, y);
                 run(dw, dm, ds, d, rows, y2);
+                run(dw, dm, dc, d, rows, y3, cpt);
                 CK(hipStreamSynchronize(st));
                 CK(hipMemcpy(y0.data(), y, (size_t)ny * 4, hipMemcpyDeviceToHost));
                 CK(hipMemcpy(y1.data(), y2, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                CK(hipMemcpy(yc.data(), y3, (size_t)ny * 4, hipMemcpyDeviceToHost));
+                if (cpt)
+                    printf("wpack %-4s check: compact side plane %zu B (padded %zu B): %s\n", o.n, hc.size() * 4, hs.size() * 4,
+                           memcmp(y0.data(), yc.data(), (size_t)ny * 4) ? "BITS DIFFER" : "same bits");
                 double sum = 0;
                 for (float v : y0) sum += fabs((double)v);
                 printf("wpack %-4s check: exponents %d..%d D %d, %d outputs, mean |y| %.4g: %s\n", o.n, emin, emax, d, ny,
                        sum / ny, memcmp(y0.data(), y1.data(), (size_t)ny * 4) ? "BITS DIFFER" : "same bits");
                 fflush(stdout);
-                CK(hipFree(dw)); CK(hipFree(dm)); CK(hipFree(ds)); CK(hipFree(y2));
+                CK(hipFree(dw)); CK(hipFree(dm)); CK(hipFree(ds)); CK(hipFree(dc)); CK(hipFree(y2)); CK(hipFree(y3));
                 CK(hipMemsetD32(x, 0x3c003c01u, DH));
             }
             // timing: constant planes (values do not matter), one pair of planes per layer
             const int nl = (int)o.w->size();
-            std::vector<void*> pm(nl), ps(nl);
+            std::vector<void*> pm(nl), ps(nl), pp(nl);
             for (int l = 0; l < nl; l++) {
                 pm[l] = dmalloc(mainb, 1);
                 ps[l] = dmalloc(sideb, 0);
+                pp[l] = cpt ? dmalloc(sidepb, 0) : nullptr;
             }
             const int it = nl == 1 ? iters / 10 + 1 : iters;
             for (int r = 0; r < 5; r++) {
@@ -414,10 +430,14 @@ int main(int argc, char** argv) {
                 snprintf(nm, sizeof nm, "wpack %-4s raw    run %d", o.n, r);
                 add(nm, timeit([&] { run((*o.w)[layer++ % nl], nullptr, nullptr, 0, o.rows, y); }, it, st), (double)o.rows * o.K * 2);
                 snprintf(nm, sizeof nm, "wpack %-4s packed run %d", o.n, r);
-                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], pm[l], ps[l], d, o.rows, y); }, it, st),
+                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], pm[l], ps[l], d, o.rows, y, cpt); }, it, st),
                     (double)mainb + sideb);
+                if (!cpt) continue;
+                snprintf(nm, sizeof nm, "wpack %-4s padded run %d", o.n, r);
+                add(nm, timeit([&] { const int l = layer++ % nl; run((*o.w)[l], pm[l], pp[l], d, o.rows, y, 0); }, it, st),
+                    (double)mainb + sidepb);
             }
-            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); }
+            for (int l = 0; l < nl; l++) { CK(hipFree(pm[l])); CK(hipFree(ps[l])); if (pp[l]) CK(hipFree(pp[l])); }
         }
         return 0;
     }

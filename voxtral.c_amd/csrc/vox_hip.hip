@@ -160,6 +160,7 @@ struct WPackD {
     uint8_t *main, *side;
     int d;
     uint8_t* frag;
+    int compact;  // side is the compact side plane (vox_wpack.h)
 };
 // wmx4 plane of a bf16 matrix that is MXFP4-valued (vox_wmx4.h), for the single-stream GEMV:
 // 5 bits per weight, decoded without loss.  null: none (the tensor streams as wpack13 or raw).
@@ -312,10 +313,12 @@ static void par_range(long long n, F f) {
 // or of a shape launch_gemv does not take, stays raw: P->main stays null.
 // fstats != null (and rows % 16 == 0, K % 64 == 0): the tensor's fragment plane for the batched
 // step as well, in the same codes and D.
+// compact: the side plane in its compact layout where the shape has one (vox_wpack13_side_is_compact);
+// rb: the row group (0: gemv_rowgroup(rows))
 static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const uint16_t* w, int rows, int K, int swiglu,
-                      long long* fstats = nullptr) {
+                      long long* fstats = nullptr, int compact = 0, int rb_ = 0) {
     P->main = P->side = P->frag = nullptr;
-    P->d = 0;
+    P->d = P->compact = 0;
     const size_t n = (size_t)rows * K;
     auto raw = [&] { S.raw_tensors++; S.raw_bytes += (long long)n * 2; return 0; };
     if (!w) return set_err("null weight pointer");
@@ -331,12 +334,17 @@ static int wpack_make(int enabled, vox_hip_wpack_stats_t& S, WPackD* P, const ui
     });
     int d;
     if (!vox_wpack13_choose(lo, hi, bad, &d)) return raw();
-    const int rb = gemv_rowgroup(rows), sw = vox_wpack13_side_words(K, rb);
-    const size_t mainw = n / 8 * 3, sidew = (size_t)rows / rb * 256 * sw;
+    const int rb = rb_ ? rb_ : gemv_rowgroup(rows), sw = vox_wpack13_side_words(K, rb);
+    P->compact = compact && vox_wpack13_side_is_compact(K, rb);
+    const size_t mainw = n / 8 * 3;
+    const size_t sidew = (size_t)rows / rb * (P->compact ? (size_t)vox_wpack13_side_compact_group_words(K, rb) : (size_t)256 * sw);
     std::vector<uint32_t> hm(mainw), hs(sidew);
     std::vector<uint8_t> hb(n / 8);
     par_range(rows, [&](long long r0, long long r1) { vox_wpack13_pack_rows(w, r0, r1, K, d, hm.data(), hb.data()); });
-    par_range(rows / rb, [&](long long g0, long long g1) { vox_wpack13_side_groups(hb.data(), g0, g1, K, rb, swiglu, hs.data()); });
+    par_range(rows / rb, [&](long long g0, long long g1) {
+        if (P->compact) vox_wpack13_side_compact_groups(hb.data(), g0, g1, K, rb, swiglu, hs.data());
+        else vox_wpack13_side_groups(hb.data(), g0, g1, K, rb, swiglu, hs.data());
+    });
     CK(dalloc(&P->main, mainw * 4));
     CK(dalloc(&P->side, sidew * 4));
     if (upload(P->main, hm.data(), mainw * 4) || upload(P->side, hs.data(), sidew * 4)) return -1;
@@ -365,6 +373,7 @@ static void wpack_args(GemvArgs& a, const WPackD& P) {
     a.wp_main = P.main;
     a.wp_side = P.side;
     a.wp_d = P.d;
+    a.wp_compact = P.compact;
 }
 
 // wmx4 mode of models created from now on (include/voxtral_hip.h); VOX_HIP_WMX4 gives the
@@ -399,6 +408,21 @@ extern "C" int vox_hip_set_wmx4_batch(int on) {
     return 0;
 }
 extern "C" int vox_hip_wmx4_batch(void) { return wmx4_batch_mode(); }
+// compact wpack13 side planes (vox_wpack.h), for models created from now on; on by default,
+// VOX_HIP_WPACK_COMPACT=0 gives the initial value 0: every side plane in the padded layout
+static int g_wpack_compact = -1;
+static int wpack_compact_mode() {
+    if (g_wpack_compact < 0) {
+        const char* e = getenv("VOX_HIP_WPACK_COMPACT");
+        g_wpack_compact = e && atoi(e) == 0 ? 0 : 1;
+    }
+    return g_wpack_compact;
+}
+extern "C" int vox_hip_set_wpack_compact(int on) {
+    g_wpack_compact = on ? 1 : 0;
+    return 0;
+}
+extern "C" int vox_hip_wpack_compact(void) { return wpack_compact_mode(); }
 // wpack13 fragment planes for the batched step, for models created from now on;
 // VOX_HIP_WPACK_BATCH=1 gives the initial value
 static int g_wpack_batch = -1;
@@ -666,6 +690,7 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     m->wpack_batch = m->wpack ? wpack_batch_mode() : 0;
     memset(m->pfstats, 0, sizeof m->pfstats);
     long long* const pfst = m->wpack_batch ? m->pfstats : nullptr;
+    const int wpc = wpack_compact_mode();  // compact side planes (the padded layout with VOX_HIP_WPACK_COMPACT=0)
     const vox_hip_config_t& c = *cfg;
     const int ED = c.enc_dim, EQ = c.enc_heads * c.enc_head_dim, EKV = c.enc_kv_heads * c.enc_head_dim;
     const int EH = c.enc_hidden;
@@ -726,7 +751,7 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
     // wpack13 copies of the bf16 matrices the single-stream decode step streams (made here,
     // not in the first step); the raw copies stay for every other path
     if (!w->tok_emb_s) {
-        TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0, pfst));
+        TRY(wpack_make(m->wpack, m->wstats, &m->plm, (const uint16_t*)h_tok, c.vocab, DD, 0, pfst, wpc));
         TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &m->mlm, (const uint16_t*)h_tok, c.vocab, DD, 0, fst));
     }
     rnd[0] = std::vector<uint16_t>();
@@ -755,11 +780,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
             memcpy(hrows.data(), h_wq, (size_t)DQ * DD * 2);
             memcpy(hrows.data() + (size_t)DQ * DD, h_wk, (size_t)DKV * DD * 2);
             memcpy(hrows.data() + (size_t)(DQ + DKV) * DD, h_wv, (size_t)DKV * DD * 2);
-            TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0, pfst));
+            TRY(wpack_make(m->wpack, m->wstats, &L.pqkv, hrows.data(), DQ + 2 * DKV, DD, 0, pfst, wpc));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mqkv, hrows.data(), DQ + 2 * DKV, DD, 0, fst));
         }
         if (!L.so) {
-            TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0, pfst));
+            TRY(wpack_make(m->wpack, m->wstats, &L.po, (const uint16_t*)h_wo, DD, DQ, 0, pfst, wpc));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.mo, (const uint16_t*)h_wo, DD, DQ, 0, fst));
         }
         if (!L.s13) {
@@ -769,11 +794,11 @@ extern "C" vox_hip_model_t* vox_hip_model_create(const vox_hip_config_t* cfg,
                 memcpy(hrows.data() + 2 * g * grp, (const uint16_t*)h_w1 + g * grp, grp * 2);
                 memcpy(hrows.data() + (2 * g + 1) * grp, (const uint16_t*)h_w3 + g * grp, grp * 2);
             }
-            TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1, pfst));
+            TRY(wpack_make(m->wpack, m->wstats, &L.p13, hrows.data(), 2 * DH, DD, 1, pfst, wpc));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m13, hrows.data(), 2 * DH, DD, 1, fst));
         }
         if (!L.s2) {
-            TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0, pfst));
+            TRY(wpack_make(m->wpack, m->wstats, &L.p2, (const uint16_t*)h_w2, DD, DH, 0, pfst, wpc));
             TRY(wmx4_make(m->wmx4 && m->wpack, m->mstats, &L.m2, (const uint16_t*)h_w2, DD, DH, 0, fst));
         }
         TRYH(dalloc(&L.attn_norm, DD));
@@ -3464,10 +3489,12 @@ static int twin_sgemm(int M, int N, int K, const float* A, const void* B, const 
 // wpack13 planes (packed = 1), the wmx4 plane (packed = 2) or the raw rows.  Returns 1 when the
 // wpack13 instance ran, 2 when the wmx4 instance ran, 0 when the raw one did (packed = 0, or W
 // outside the format's window / not MXFP4-valued), -1 on error.
-extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const float* x, float* y, int packed) {
+static int gemv_wpack_entry(int rows, int K, const uint16_t* W, const float* x, float* y, int packed, int rb, int compact) {
     std::lock_guard<std::mutex> lk(g_twin_mu);
     if (!W || !x || !y) return set_err("gemv_wpack: null argument");
     if (!gemv_ok(rows, K, 0)) return set_err("gemv_wpack: shape %d x %d is not a GEMV shape", rows, K);
+    if (rb && ((rb != 2 && rb != 4 && rb != 8) || rows % rb || packed == 2))
+        return set_err("gemv_wpack: row group %d (0, 2, 4 or 8 dividing %d rows; not with the wmx4 plane)", rb, rows);
     if (twin_init()) return -1;
     uint8_t* dW = nullptr;
     float *dx = nullptr, *dy = nullptr;
@@ -3483,11 +3510,11 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
         CK(dalloc(&dx, (size_t)K));
         CK(dalloc(&dy, (size_t)rows));
         if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)K * 4)) return -1;
-        if (wpack_make(packed == 1, S, &P, W, rows, K, 0)) return -1;
+        if (wpack_make(packed == 1, S, &P, W, rows, K, 0, nullptr, compact, rb)) return -1;
         if (wmx4_make(packed == 2, MS, &M, W, rows, K, 0)) return -1;
         GemvArgs a;
         memset(&a, 0, sizeof a);
-        a.x = dx; a.K = K; a.W = dW; a.rows = rows; a.y = dy;
+        a.x = dx; a.K = K; a.W = dW; a.rows = rows; a.y = dy; a.rb = rb;
         wpack_args(a, P);
         a.wm_plane = M.plane;
         CK(launch_gemv(PRO_NONE, EPI_STORE, a, g_twin_st));
@@ -3499,6 +3526,16 @@ extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const floa
     const int ran = M.plane ? 2 : P.main ? 1 : 0;
     dfree(dW); dfree(dx); dfree(dy); dfree(P.main); dfree(P.side); dfree(M.plane);
     return rc ? -1 : ran;
+}
+
+extern "C" int vox_hip_gemv_wpack(int rows, int K, const uint16_t* W, const float* x, float* y, int packed) {
+    return gemv_wpack_entry(rows, K, W, x, y, packed, 0, wpack_compact_mode());
+}
+// The same in row groups of rb = 2, 4 or 8 rows (0: the shape's own) and, for packed = 1, with the
+// side plane compact (compact != 0, where the shape has a compact layout) or padded.
+extern "C" int vox_hip_gemv_wpack_rb(int rows, int K, const uint16_t* W, const float* x, float* y, int packed, int rb,
+                                     int compact) {
+    return gemv_wpack_entry(rows, K, W, x, y, packed, rb, compact);
 }
 
 // Test entry: y[R][rows] = W x[r] for R in 1..8 rows through k_gemvr's STORE instance of the
@@ -3530,7 +3567,7 @@ extern "C" int vox_hip_gemv_rows(int rows, int K, const uint16_t* W, const float
         CK(dalloc(&dy, (size_t)Rb * rows));
         CK(hipMemset(dx, 0, (size_t)Rb * K * 4));
         if (upload(dW, W, (size_t)rows * K * 2) || upload(dx, x, (size_t)R * K * 4)) return -1;
-        if (wpack_make(packed == 1, S, &P, W, rows, K, 0)) return -1;
+        if (wpack_make(packed == 1, S, &P, W, rows, K, 0, nullptr, wpack_compact_mode())) return -1;
         if (wmx4_make(packed == 2 && gemvr_ok_mx4(PRO_NONE, EPI_STORE, rows, K), MS, &M, W, rows, K, 0)) return -1;
         GemvRArgs a;
         memset(&a, 0, sizeof a);

@@ -75,8 +75,9 @@ static __device__ unsigned long long* g_gemv_stamps;
 // or beyond, past anything an RMSNorm output, an attention output or a SwiGLU product of
 // this model reaches.  Every output is then bit-identical to the bf16 instance's.
 template <int SW>
-__device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int voff, int soff, uint32_t (&sd)[SW]) {
-    if constexpr (SW == 1) {
+__device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int voff, int soff, uint32_t* sd) {
+    if constexpr (SW == 0) {
+    } else if constexpr (SW == 1) {
         sd[0] = __builtin_amdgcn_raw_buffer_load_b32(S, voff, soff, 2);
     } else if constexpr (SW == 2) {
         const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(S, voff, soff, 2);
@@ -98,6 +99,35 @@ __device__ __forceinline__ void gemv_load_side(__amdgpu_buffer_rsrc_t S, int vof
         }
     }
 }
+
+// Where a thread's side dwords are.  Its SW registers are the padded record's, slot j * RB + i
+// in dword (j * RB + i) / 4.  Where the last round's slots start a dword (SPLIT) they come in
+// through two loads: section A, the SWA dwords of the whole rounds, and section B, the SWB
+// dwords of the last round.  A lane without a chunk in the last round takes section B through
+// an offset past every plane: the range check returns zeros without a memory access, as
+// the zero-length descriptor does past the last group.  Padded plane: A and B are the two parts
+// of the thread's record; compact plane (vox_wpack.h): the group's 256 A sections, then the B
+// sections of the nr lanes that have one.  Everything here is an offset, no branch.
+constexpr int GEMV_OFF_NONE = 0x7fff0000;  // past every plane (their bytes stay below 2^31)
+template <int RB, int KQ>
+struct WpSide {
+    static constexpr int SW = (KQ * RB + 3) / 4;
+    static constexpr bool SPLIT = KQ > 1 && ((KQ - 1) * RB) % 4 == 0;
+    static constexpr int SWA = SPLIT ? (KQ - 1) * RB / 4 : SW, SWB = SW - SWA;
+    int va, vb, gbytes;  // byte offsets of the thread's sections in a group's record; a group's bytes
+    __device__ __forceinline__ WpSide(int tid, int KC, int compact) {
+        const int nr = KC - (KQ - 1) * 256;  // lanes with a chunk in the last round
+        const bool cp = SPLIT && compact;
+        gbytes = cp ? (256 * SWA + nr * SWB) * 4 : 256 * SW * 4;
+        va = tid * ((cp ? SWA : SW) * 4);
+        const int vb0 = (cp ? 256 * SWA : SWA) * 4 + tid * ((cp ? SWB : SW) * 4);
+        vb = tid < nr ? vb0 : GEMV_OFF_NONE;
+    }
+    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t S, int g, uint32_t* sd) const {
+        gemv_load_side<SWA>(S, va, g * gbytes, sd);  // first: every chunk needs it
+        gemv_load_side<SWB>(S, vb, g * gbytes, sd + SWA);
+    }
+};
 
 // wmx4 plane (WF_MX4, vox_wmx4.h): one record of RW = RB + ceil(RB / 4) dwords per (group,
 // chunk): the RB rows' nibble dwords of that chunk and their blocks' e8m0 scale bytes, so the
@@ -139,21 +169,24 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
         __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
     void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
+    const WpSide<RB, KQ> ws(tid, KC, a.wp_compact);
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * ws.gbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
     uint32_t sd[SW];
     // chunk offsets per K round; chunks past K (K not a multiple of 16 B * 256) re-load
     // chunk 0 and meet x = 0: every load is unconditional, so hipcc issues them all before
-    // the first wait (a guarded load makes it wait vmcnt(0) at each branch join)
+    // the first wait (a guarded load makes it wait vmcnt(0) at each branch join).  wpack13: such
+    // a lane's offset is past the plane instead, so its loads return zeros without a memory
+    // access and 0 meets x = 0
     int voff[KQ];
 #pragma unroll
     for (int j = 0; j < KQ; j++) {
         const int c0 = (j * 4 + wave) * 64 + lane;
-        voff[j] = (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
+        voff[j] = WP && c0 >= KC ? GEMV_OFF_NONE : (c0 < KC ? c0 : 0) * (WM ? RW * 4 : WP ? 12 : 16);
     }
     // first group's weights are independent of x: issue them before the prologue
     gemv_rows<EPI, RB>(g, rows);
-    if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);  // first: every chunk needs it
+    if constexpr (WP) ws.load(srs, g, sd);
     if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
     else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
     if ((EPI == EPI_LOGITS || EPI == EPI_LOGITS_ALT) && WQ8 && wave == 0) {
@@ -321,7 +354,7 @@ __global__ __launch_bounds__(256) void k_gemv(GemvArgs a) {
         {
             const bool more = g < ngroups;
             gemv_rows<EPI, RB>(more ? g : 0, rows);
-            if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
+            if constexpr (WP) ws.load(more ? srs : snone, more ? g : 0, sd);
             if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
             else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
             if (LOGIT && WQ8 && wave == 0) {
@@ -462,7 +495,8 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
         __builtin_amdgcn_make_buffer_rsrc(wbase, 0, (WM ? ngroups : a.rows) * rowbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, 0, 0x00020000);
     void* const sbase = const_cast<void*>(WP ? a.wp_side : a.W);
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * (256 * SW * 4), 0x00020000);
+    const WpSide<RB, KQ> ws(tid, KC, a.wp_compact);  // the side plane's layout is the model's: k_gemv's fetch
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, ngroups * ws.gbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t snone = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, 0, 0x00020000);
     // chunk offsets per K round, as k_gemv: chunks past K re-load chunk 0 and meet x = 0
     int voff[KQ];
@@ -486,7 +520,7 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
         uint32_t sd[SW];
         // first group's weights are independent of x: issue them before the prologue
         gemv_rows<EPI, RB>(g, rows);
-        if (WP) gemv_load_side<SW>(srs, tid * (SW * 4), g * (256 * SW * 4), sd);
+        if constexpr (WP) ws.load(srs, g, sd);
         if constexpr (WM) gemv_load_mx4<RW, KQ>(wrs, g * rowbytes, voff, mr);
         else gemv_load<RB, KQ, WP>(wrs, rowbytes, rows, voff, wv);
 
@@ -678,7 +712,7 @@ __global__ __launch_bounds__(256) void k_gemvr(GemvRArgs ra) {
             {
                 const bool more = g < ngroups;
                 gemv_rows<EPI, RB>(more ? g : 0, rows);
-                if (WP) gemv_load_side<SW>(more ? srs : snone, tid * (SW * 4), (more ? g : 0) * (256 * SW * 4), sd);
+                if constexpr (WP) ws.load(more ? srs : snone, more ? g : 0, sd);
                 if constexpr (WM) gemv_load_mx4<RW, KQ>(more ? wrs : wnone, (more ? g : 0) * rowbytes, voff, mr);
                 else gemv_load<RB, KQ, WP>(more ? wrs : wnone, rowbytes, rows, voff, wv);
             }

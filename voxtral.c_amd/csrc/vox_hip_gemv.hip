@@ -93,11 +93,16 @@ static int gemv_wf(const GemvArgs& a) { return a.wscale ? WF_Q8 : a.wm_plane ? W
 // row group, grid and K rounds of a launch: the wmx4 plane has its own group size, Q8 rows 16-weight chunks
 static int gemv_rb_wf(int rows, int wf) { return wf == WF_MX4 ? gemv_rb_mx4(rows) : gemv_rb(rows); }
 static int gemv_grid_wf(int rows, int wf) { return gemv_grid_rb(rows, gemv_rb_wf(rows, wf)); }
+// the same of a k_gemv launch, which may name its bf16 / wpack13 row group itself (a.rb)
+static int gemv_rb_of(const GemvArgs& a, int wf) {
+    return a.rb && (wf == WF_BF16 || wf == WF_P13) ? a.rb : gemv_rb_wf(a.rows, wf);
+}
+static int gemv_grid_of(const GemvArgs& a, int wf) { return gemv_grid_rb(a.rows, gemv_rb_of(a, wf)); }
 static int gemv_kq(int K, int wf) { return ((wf == WF_Q8 ? K >> 4 : K >> 3) + 255) / 256; }
 
 // kernel instance launch_gemv uses (also tools, occupancy queries)
 const void* gemv_kernel(int pro, int epi, const GemvArgs& a) {
-    const int wf = gemv_wf(a), rb = gemv_rb_wf(a.rows, wf), kq = gemv_kq(a.K, wf);
+    const int wf = gemv_wf(a), rb = gemv_rb_of(a, wf), kq = gemv_kq(a.K, wf);
 #define GEMV_PICK(WF, name) \
     if (wf == WF) return gemv_pick_##name(pro, epi, rb, kq);
     GEMV_FORMATS(GEMV_PICK)
@@ -114,18 +119,19 @@ hipError_t launch_gemv_timed(int pro, int epi, const GemvArgs& a, hipEvent_t sta
     if (!fn) return hipErrorInvalidValue;
     GemvArgs args = a;
     void* kargs[] = {&args};
-    return hipExtLaunchKernel(fn, dim3(gemv_grid_wf(a.rows, gemv_wf(a))), dim3(256), kargs, 0, st, start, stop, 0);
+    return hipExtLaunchKernel(fn, dim3(gemv_grid_of(a, gemv_wf(a))), dim3(256), kargs, 0, st, start, stop, 0);
 }
 
 hipError_t launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t st) {
     if (!gemv_ok(a.rows, a.K, a.wscale != nullptr)) return hipErrorInvalidValue;
     if (gemv_wf(a) == WF_MX4 && !gemv_ok_mx4(a.rows, a.K)) return hipErrorInvalidValue;
     if (epi == EPI_QKV_BIAS && !a.bias) return hipErrorInvalidValue;
+    if (a.rb && ((a.rb != 2 && a.rb != 4 && a.rb != 8) || a.rows % a.rb)) return hipErrorInvalidValue;
     const void* fn = gemv_kernel(pro, epi, a);
     if (!fn) return hipErrorInvalidValue;
     GemvArgs args = a;
     void* kargs[] = {&args};
-    return hipLaunchKernel(fn, dim3(gemv_grid_wf(a.rows, gemv_wf(a))), dim3(256), kargs, 0, st);
+    return hipLaunchKernel(fn, dim3(gemv_grid_of(a, gemv_wf(a))), dim3(256), kargs, 0, st);
 }
 
 static const void* gemvr_pick(int pro, int epi, int rows, int K, int wf, int R) {

@@ -30,6 +30,8 @@ struct GemvArgs {
     const void* wp_main = nullptr;
     const void* wp_side = nullptr;
     int wp_d = 0;
+    int wp_compact = 0;    // wp_side is the compact side plane (vox_wpack13_side_is_compact shapes only)
+    int rb = 0;            // rows per group of the bf16 / wpack13 instances (0: gemv_rowgroup(rows))
     // wmx4 copy of W (vox_wmx4.h; null: none), laid out for gemv_rowgroup_mx4(rows); streamed
     // in preference to the wpack13 planes
     const void* wm_plane = nullptr;

@@ -117,6 +117,14 @@ int vox_wpack13_side_words_of(long long K, int rb) { return vox_wpack13_side_wor
 void vox_wpack13_side_layout(const uint8_t *side, long long rows, long long K, int rb, int swiglu, uint32_t *out) {
     vox_wpack13_side_layout_(side, rows, K, rb, swiglu, out);
 }
+int vox_wpack13_side_compact_of(long long K, int rb) { return vox_wpack13_side_is_compact(K, rb); }
+long long vox_wpack13_side_compact_group_words_of(long long K, int rb) {
+    return vox_wpack13_side_compact_group_words(K, rb);
+}
+void vox_wpack13_side_compact_layout(const uint8_t *side, long long rows, long long K, int rb, int swiglu,
+                                     uint32_t *out) {
+    vox_wpack13_side_compact_layout_(side, rows, K, rb, swiglu, out);
+}
 long long vox_wpack13_frag_words_of(long long N, long long K) { return vox_wpack13_frag_words(N, K); }
 void vox_wpack13_frag_layout(const uint16_t *w, long long N, long long K, int D, uint32_t *out) {
     vox_wpack13_frag_layout_(w, N, K, D, out);

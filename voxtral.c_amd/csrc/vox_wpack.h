@@ -19,8 +19,8 @@
  * Side plane, laid out for the GEMV kernel's geometry: one record of SW dwords per (row
  * group g, thread t of the 256), SW = ceil(KQ * RB / 4), at dword (g * 256 + t) * SW.
  * Slot s = j * RB + i of a record is the side byte of row gemv_row(g, i), chunk
- * (j * 4 + t / 64) * 64 + t % 64 (chunk 0 when that is past the row: the kernel re-loads
- * chunk 0 there and meets x = 0).  Dword s / 4 holds slot s with q = s % 4 as
+ * (j * 4 + t / 64) * 64 + t % 64 (chunk 0 when that is past the row: the kernel meets x = 0
+ * there; see the compact plane below).  Dword s / 4 holds slot s with q = s % 4 as
  *   low nibble at bits 12 - 4q .. 15 - 4q,  high nibble at bits 28 - 4q .. 31 - 4q
  * so that (dword << 4q) & 0xf000f000 lands both nibbles on top of the two halves.
  *
@@ -174,6 +174,60 @@ static inline void vox_wpack13_side_layout_(const uint8_t *side, long long rows,
                                             uint32_t *out) {
 #pragma omp parallel for schedule(static) num_threads(16)
     for (long long g = 0; g < rows / rb; g++) vox_wpack13_side_groups(side, g, g + 1, K, rb, swiglu, out);
+}
+/* ---- compact side plane ----
+ * A row of K / 8 chunks that spans more than one K round of 256 chunks and ends inside its last
+ * round (K = 3072: 384 chunks, 1.5 rounds) leaves the lanes past the row end without a chunk in
+ * that round; the record above still gives each of them RB slots (of chunk 0).  The compact plane
+ * holds no slot without a chunk.  A group's record has two sections:
+ *   A: SWA = (KQ - 1) * RB / 4 dwords per thread t of the 256 at dword t * SWA: slots s = j * RB + i
+ *      of the whole rounds j < KQ - 1, as above;
+ *   B: SWB = ceil(RB / 4) dwords per thread t < NR = K / 8 - (KQ - 1) * 256 (the lanes with a chunk
+ *      in the last round) at dword 256 * SWA + t * SWB: slot i of chunk (KQ - 1) * 256 + t.
+ * Groups follow each other at 256 * SWA + NR * SWB dwords; a dword holds its four slots as above.
+ * A thread's registers are the padded record's: section A, then section B (zeros without a
+ * chunk).  It takes (KQ - 1) * RB % 4 == 0, so that the last round's slots start a dword; every
+ * other shape -- one round, whole rounds, or a last round that shares a dword -- keeps the padded
+ * plane, byte for byte. */
+static inline int vox_wpack13_side_is_compact(long long K, int rb) {
+    const int kq = vox_wpack13_kq(K);
+    return kq > 1 && (K / 8) % 256 != 0 && ((kq - 1) * rb) % 4 == 0;
+}
+/* dwords of one group's record in the compact plane (the padded 256 * SW where it does not apply) */
+static inline long long vox_wpack13_side_compact_group_words(long long K, int rb) {
+    const int kq = vox_wpack13_kq(K);
+    if (!vox_wpack13_side_is_compact(K, rb)) return 256LL * vox_wpack13_side_words(K, rb);
+    return 256LL * ((kq - 1) * rb / 4) + (K / 8 - (kq - 1) * 256LL) * ((rb + 3) / 4);
+}
+/* side bytes [rows][K / 8] -> groups g0..g1 of the compact side plane ((rows / rb) *
+ * vox_wpack13_side_compact_group_words dwords in all) */
+static inline void vox_wpack13_side_compact_groups(const uint8_t *side, long long g0, long long g1, long long K, int rb,
+                                                   int swiglu, uint32_t *out) {
+    if (!vox_wpack13_side_is_compact(K, rb)) {
+        vox_wpack13_side_groups(side, g0, g1, K, rb, swiglu, out);
+        return;
+    }
+    const long long kc = K / 8, gw = vox_wpack13_side_compact_group_words(K, rb);
+    const int kq = vox_wpack13_kq(K), swa = (kq - 1) * rb / 4, swb = (rb + 3) / 4;
+    const int nr = (int)(kc - (kq - 1) * 256LL);
+    for (long long g = g0; g < g1; g++) {
+        uint32_t *rec = out + g * gw;
+        memset(rec, 0, (size_t)gw * 4);
+        for (int t = 0; t < 256; t++)
+            for (int j = 0; j < (t < nr ? kq : kq - 1); j++)
+                for (int i = 0; i < rb; i++) {
+                    const int last = j == kq - 1, s = last ? i : j * rb + i, q = s & 3;
+                    const long long c = (long long)(j * 4 + t / 64) * 64 + t % 64;
+                    const uint32_t b = side[vox_wpack13_row(g, i, rb, swiglu) * kc + c];
+                    uint32_t *d = last ? rec + 256 * swa + t * swb : rec + t * swa;
+                    d[s >> 2] |= (b & 15) << (12 - 4 * q) | (b >> 4) << (28 - 4 * q);
+                }
+    }
+}
+static inline void vox_wpack13_side_compact_layout_(const uint8_t *side, long long rows, long long K, int rb, int swiglu,
+                                                    uint32_t *out) {
+#pragma omp parallel for schedule(static) num_threads(16)
+    for (long long g = 0; g < rows / rb; g++) vox_wpack13_side_compact_groups(side, g, g + 1, K, rb, swiglu, out);
 }
 /* ---- fragment plane (the batched step's A operand; layout in the header comment) ---- */
 #define VOX_WPACK13_FRAG_REC 416 /* dwords per (16-row group, 64-k block): 256 + 128 of fields, 32 of sign words */

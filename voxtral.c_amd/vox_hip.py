@@ -64,6 +64,21 @@ def gemv_wpack(W_bf16, x, packed):
     return y, (rc if int(packed) == 2 else bool(rc))
 
 
+def gemv_wpack_rb(W_bf16, x, packed, rb=0, compact=True):
+    """gemv_wpack in row groups of rb rows (0: the shape's own), the wpack13 side plane compact or
+    padded (vox_hip_gemv_wpack_rb)"""
+    init()
+    W = np.ascontiguousarray(W_bf16, np.uint16)
+    xv = np.ascontiguousarray(x, np.float32)
+    rows, K = W.shape
+    assert xv.shape == (K,)
+    y = np.empty(rows, np.float32)
+    rc = lib().vox_hip_gemv_wpack_rb(rows, K, W.ctypes.data, fptr(xv), fptr(y), int(packed), int(rb), int(bool(compact)))
+    if rc < 0:
+        _err("gemv_wpack_rb")
+    return y, bool(rc)
+
+
 def gemv_rows(W_bf16, x, packed):
     """Test entry: (y [R, rows], flags) of y[r] = W x[r] for R <= 8 rows through the R-row GEMV
     (vox_hip_gemv_rows); packed: 0 raw rows, 1 (or True) wpack13 planes, 2 the wmx4 plane.
@@ -128,6 +143,7 @@ EXPORTS = [
     "vox_hip_model_set_kv_grow", "vox_hip_stream_kv_slots", "vox_hip_stream_kv_bytes",
     "vox_hip_stream_kv_grow_stats", "vox_hip_stream_reserve_kv", "vox_hip_batch_kv_grow_stats",
     "vox_hip_model_wpack_stats", "vox_hip_gemv_wpack",
+    "vox_hip_set_wpack_compact", "vox_hip_wpack_compact", "vox_hip_gemv_wpack_rb",
     "vox_hip_set_wmx4", "vox_hip_wmx4", "vox_hip_model_wmx4_stats",
     "vox_hip_set_wmx4_batch", "vox_hip_wmx4_batch", "vox_hip_model_wmx4_batch_stats", "vox_hip_batch_set_wmx4",
     "vox_hip_skinny_wmx4",
@@ -193,6 +209,8 @@ def lib():
         "vox_hip_kv8_convert": (I, [fp, I, P, fp]),
         "vox_hip_model_wpack_stats": (I, [P, P]),
         "vox_hip_gemv_wpack": (I, [I, I, P, fp, fp, I]),
+        "vox_hip_set_wpack_compact": (I, [I]), "vox_hip_wpack_compact": (I, []),
+        "vox_hip_gemv_wpack_rb": (I, [I, I, P, fp, fp, I, I, I]),
         "vox_hip_set_wmx4": (I, [I]), "vox_hip_wmx4": (I, []), "vox_hip_model_wmx4_stats": (I, [P, P]),
         "vox_hip_set_wmx4_batch": (I, [I]), "vox_hip_wmx4_batch": (I, []),
         "vox_hip_model_wmx4_batch_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
