@@ -361,6 +361,28 @@ int vox_hip_attn_decode_kv8(float *out, const float *q, const uint8_t *kcodes, c
 /* Test entry: bits[256] = every E4M3 code as the bf16 that k_attn_decode_mf8's convert makes of it. */
 int vox_hip_attn_mf8_codes(uint16_t *bits);
 
+/* The M > 1 causal / windowed attention over FP8 (E4M3) encoder K/V rings on the bf16 matrix pipe
+ * (k_attn_rows_mf8): process-wide, off by default, VOX_HIP_ENC_ATTN_MF8=1 gives the
+ * initial value.  With it on, every encoder attention launch over FP8 rings (head_dim 64) -- the
+ * one-shot passes, the streaming chunks with or without key splits, the one-row chunks and the batched
+ * pass of encode_mel_batch and the scheduler -- takes the MFMA kernel: every E4M3 code is a bf16 value
+ * and queries and softmax weights enter as three bf16 planes, so each product is exact and only the
+ * f32 summation order differs from the default kernel.  f32 and half rings and head_dim 128 launch
+ * what they launched.  No captured graph holds an encoder attention, so nothing is recaptured; inside
+ * a begun batched call (vox_hip_batch_begin_rows .. vox_hip_batch_finish) the setter is refused (-1).
+ * Returns 0. */
+int vox_hip_set_enc_attn_mf8(int on);
+int vox_hip_enc_attn_mf8(void);
+/* *launches: launches of k_attn_rows_mf8 enqueued by this process, single-stream and batched form */
+int vox_hip_enc_attn_mf8_stats(long long *launches);
+/* Test entry: the M > 1 attention over caller-supplied FP8 ring codes (host pointers): Q[M][H * hd]
+ * f32 rows at positions q_pos0 + i, Kring / Vring[cap][KVH * hd] codes with position p at slot
+ * p % cap, out[M][H * hd]; hd = 64, cap >= 32.  Query i sees keys max(0, q_pos0 + i - window + 1) ..
+ * q_pos0 + i.  use_splits 0 passes no workspace (one key range), 1 lets the launcher split the key
+ * range and combine.  mf8 0: the default kernel; 1: k_attn_rows_mf8, whatever the switch says. */
+int vox_hip_enc_attn_kv8(float *out, const float *Q, const uint8_t *Kring, const uint8_t *Vring, int cap, int M, int H,
+                         int KVH, int hd, float scale, int window, int q_pos0, int use_splits, int mf8);
+
 /* Per-stream device state: encoder/decoder rolling KV, conv-stem tails, adapter buffer,
  * scratch and a HIP stream.  One model serves many streams. */
 vox_hip_stream_t *vox_hip_stream_create(vox_hip_model_t *m);

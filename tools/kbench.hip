@@ -1520,6 +1520,48 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "encattn")) {
+        // the encoder's M > 1 attention (32 heads of 64, window 750, rings of 1838 slots) per ring type
+        // as an encoder pass sees it: 32 layers' rings, one launch per layer in turn; f32 rings, FP8
+        // rings through k_attn_mf<64, kv8_t> and through k_attn_rows_mf8.  The 1500-row
+        // case spans more positions than the ring holds (the product's passes stop at 1024 rows): its
+        // slots alias, which costs what distinct slots cost.
+        const int EHn = 32, Ehd = 64, EQn = EHn * Ehd, NLe = 32, ecp = 1838, Mmax = 1500;
+        float* eq = (float*)dmalloc((size_t)Mmax * EQn * 4, 1);
+        float* eo = (float*)dmalloc((size_t)Mmax * EQn * 4, 0);
+        const size_t wsn = (size_t)EHn * 25 * 16 * (Ehd + 2);
+        float* ews = (float*)dmalloc(wsn * 4, 0);
+        struct C { const char* n; int M, q0; bool split; };
+        for (int kvt : {0, 2}) {
+            const size_t esz = kvt == 2 ? 1 : 4, per = (size_t)ecp * EQn;
+            std::vector<float*> Ks(NLe), Vs(NLe);
+            for (int l = 0; l < NLe; l++) {
+                Ks[l] = (float*)dmalloc(per * esz, 1);
+                Vs[l] = (float*)dmalloc(per * esz, 1);
+            }
+            for (int mf8 = 0; mf8 <= (kvt == 2); mf8++) {
+                enc_attn_mf8_set(mf8);
+                for (C c : {C{"677 rows from 0", 677, 0, false}, C{"25 rows x 775 keys + combine", 25, 2000, true},
+                            C{"1500 rows full window", 1500, 750, false}}) {
+                    int l = 0;
+                    char nm[96];
+                    snprintf(nm, sizeof nm, "enc attn %s %s", c.n, kvt == 0 ? "f32" : mf8 ? "fp8 mf8" : "fp8");
+                    const int keys = c.q0 + c.M - std::max(0, c.q0 - 749);
+                    add(nm, timeit([&] {
+                            CK(launch_attn_rows_mf(Ehd, eq, EQn, Ks[l % NLe], Vs[l % NLe], ecp, eo, EQn, c.M, EHn, EHn, c.q0, 0, 750,
+                                                   0.125f, st, c.split ? ews : nullptr, c.split ? wsn : 0, nullptr, kvt));
+                            l++;
+                        }, c.M > 100 ? 160 : 320, st), (double)keys * EQn * 2 * esz);
+                }
+            }
+            enc_attn_mf8_set(0);
+            for (int l = 0; l < NLe; l++) {
+                CK(hipFree(Ks[l]));
+                CK(hipFree(Vs[l]));
+            }
+        }
+        return 0;
+    }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "attnkv")) {
         // decode attention per ring element type (f32 / half / FP8 E4M3) as the decode step sees it:
         // 26 layers' rings, one launch per layer in turn, the default grids (256 keys: k_attn_short)

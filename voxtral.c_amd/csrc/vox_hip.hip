@@ -3332,6 +3332,68 @@ extern "C" int vox_hip_attn_mf8_codes(uint16_t* bits) {
     return ok ? 0 : set_err("attn_mf8_codes: %s", hipGetErrorString(hipGetLastError()));
 }
 
+// The M > 1 attention over the encoder's FP8 rings on the bf16 matrix pipe (k_attn_rows_mf8, DESIGN.md
+// 36): process-wide and off by default (VOX_HIP_ENC_ATTN_MF8=1 gives the initial value).  No captured
+// graph holds an encoder attention (the step graphs are the decoder's), so nothing is recaptured;
+// inside a begun batched call, where the scheduler's encoder passes run, the setter is refused.
+extern "C" int vox_hip_set_enc_attn_mf8(int on) {
+    if (g_begun_calls > 0) return set_err("set_enc_attn_mf8: a begun batched call was not finished");
+    enc_attn_mf8_set(on);
+    return 0;
+}
+extern "C" int vox_hip_enc_attn_mf8(void) { return enc_attn_mf8_mode(); }
+extern "C" int vox_hip_enc_attn_mf8_stats(long long* launches) {
+    if (!launches) return set_err("enc_attn_mf8_stats: null argument");
+    *launches = enc_attn_mf8_count();
+    return 0;
+}
+
+// The M > 1 attention over caller-supplied FP8 ring codes (tests): Q [M][H * hd] f32 rows at
+// positions q_pos0 + i, rings [cap][KVH * hd] codes holding position p at slot p % cap; out
+// [M][H * hd].  use_splits 0 passes no workspace (one key range); mf8 picks the kernel of this
+// call whatever the process switch says (0: k_attn_mf<64, kv8_t>, 1: k_attn_rows_mf8).
+extern "C" int vox_hip_enc_attn_kv8(float* out, const float* Q, const uint8_t* Kring, const uint8_t* Vring, int cap, int M,
+                                    int H, int KVH, int hd, float scale, int window, int q_pos0, int use_splits, int mf8) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (!out || !Q || !Kring || !Vring) return set_err("enc_attn_kv8: null argument");
+    if (hd != 64 || M < 1 || cap < 32 || KVH < 1 || H % KVH || window < 1 || q_pos0 < 0 || (mf8 != 0 && mf8 != 1))
+        return set_err("enc_attn_kv8: bad arguments");
+    if (g_begun_calls > 0) return set_err("enc_attn_kv8: a begun batched call was not finished");
+    const size_t ring = (size_t)cap * KVH * hd, qn = (size_t)M * H * hd;
+    const size_t wsn = use_splits ? (size_t)H * M * 16 * (hd + 2) : 0;  // twin_attention's workspace
+    uint8_t *dk = nullptr, *dv = nullptr;
+    float *dq = nullptr, *dout = nullptr, *dws = nullptr;
+    const int was = enc_attn_mf8_mode();
+    int rc = -1;
+    do {
+        if (hipMalloc((void**)&dk, ring) != hipSuccess || hipMalloc((void**)&dv, ring) != hipSuccess ||
+            hipMalloc((void**)&dq, qn * 4) != hipSuccess || hipMalloc((void**)&dout, qn * 4) != hipSuccess ||
+            (wsn && hipMalloc((void**)&dws, wsn * 4) != hipSuccess)) {
+            set_err("enc_attn_kv8: out of device memory");
+            break;
+        }
+        enc_attn_mf8_set(mf8);
+        const bool ok = hipMemcpy(dk, Kring, ring, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dv, Vring, ring, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dq, Q, qn * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemset(dout, 0, qn * 4) == hipSuccess &&
+                        launch_attn_rows_mf(hd, dq, H * hd, reinterpret_cast<const float*>(dk),
+                                            reinterpret_cast<const float*>(dv), cap, dout, H * hd, M, H, KVH, q_pos0, 0, window,
+                                            scale, nullptr, dws, wsn, nullptr, KV_FP8) == hipSuccess &&
+                        hipDeviceSynchronize() == hipSuccess &&
+                        hipMemcpy(out, dout, qn * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        enc_attn_mf8_set(was);
+        if (!ok) {
+            set_err("enc_attn_kv8: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+        rc = 0;
+    } while (0);
+    for (void* d : {(void*)dk, (void*)dv, (void*)dq, (void*)dout, (void*)dws})
+        if (d) hipFree(d);
+    return rc;
+}
+
 extern "C" int vox_hip_stream_set_profiling(vox_hip_stream_t* s, int enable) {
     s->profiling = enable;
     s->prof_ms = 0;

@@ -45,41 +45,12 @@ VOX_KB_KNOB(g_attn_mf8_range, 256);
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
-// two E4M3 codes (the low or high half of w) as two bf16: gfx950's packed convert at scale 1, exact
-template <bool HI>
-__device__ __forceinline__ uint32_t mf8_cvt2(uint32_t w) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-// eight codes (two dwords, ascending) as the 8 bf16 of an MFMA operand
-__device__ __forceinline__ bf16x8 mf8_cvt8(uint32_t lo, uint32_t hi) {
-    return __builtin_bit_cast(bf16x8, make_uint4(mf8_cvt2<false>(lo), mf8_cvt2<true>(lo), mf8_cvt2<false>(hi), mf8_cvt2<true>(hi)));
-}
-// eight f32 as three bf16x8 planes (split3)
-__device__ __forceinline__ void mf8_split8(const float (&v)[8], bf16x8& ph, bf16x8& pm, bf16x8& pl) {
-    uint32_t h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        uint16_t h0, m0, l0, h1, m1, l1;
-        split3(v[e], h0, m0, l0);
-        split3(v[e + 1], h1, m1, l1);
-        h[e / 2] = h0 | ((uint32_t)h1 << 16);
-        m[e / 2] = m0 | ((uint32_t)m1 << 16);
-        l[e / 2] = l0 | ((uint32_t)l1 << 16);
-    }
-    ph = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
-    pm = __builtin_bit_cast(bf16x8, make_uint4(m[0], m[1], m[2], m[3]));
-    pl = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
-}
-
 // the codes one lane holds of a 32-key tile: its key row's 32 K bytes in each 16-key half, and
 // 8 V bytes of each of its eight key rows
 struct Mf8Tile {
     uint4 k[2][2];
     uint2 v[8];
 };
-// key of the tile that k-index 8 g + i of P.V means
-__device__ __forceinline__ int mf8_key(int g, int i) { return i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4); }
-
 template <int FUSE, class AP>
 __global__ __launch_bounds__(MF8_WAVES * 64) void k_attn_decode_mf8(const AP P, int cap, int pos_host, int window,
                                                                     float scale, int H, int KVH, int maxs, int rk,

@@ -263,6 +263,35 @@ __device__ __forceinline__ bf16x8 i8x8_bf16(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(bf16x8, make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)));
 }
 
+// FP8 (E4M3) codes and f32 values as bf16 MFMA operands (k_attn_decode_mf8, k_attn_rows_mf8)
+// two E4M3 codes (the low or high half of w) as two bf16: gfx950's packed convert at scale 1, exact
+template <bool HI>
+__device__ __forceinline__ uint32_t mf8_cvt2(uint32_t w) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+// eight codes (two dwords, ascending) as the 8 bf16 of an MFMA operand
+__device__ __forceinline__ bf16x8 mf8_cvt8(uint32_t lo, uint32_t hi) {
+    return __builtin_bit_cast(bf16x8, make_uint4(mf8_cvt2<false>(lo), mf8_cvt2<true>(lo), mf8_cvt2<false>(hi), mf8_cvt2<true>(hi)));
+}
+// eight f32 as three bf16x8 planes (split3)
+__device__ __forceinline__ void mf8_split8(const float (&v)[8], bf16x8& ph, bf16x8& pm, bf16x8& pl) {
+    uint32_t h[4], m[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        uint16_t h0, m0, l0, h1, m1, l1;
+        split3(v[e], h0, m0, l0);
+        split3(v[e + 1], h1, m1, l1);
+        h[e / 2] = h0 | ((uint32_t)h1 << 16);
+        m[e / 2] = m0 | ((uint32_t)m1 << 16);
+        l[e / 2] = l0 | ((uint32_t)l1 << 16);
+    }
+    ph = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
+    pm = __builtin_bit_cast(bf16x8, make_uint4(m[0], m[1], m[2], m[3]));
+    pl = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
+}
+// key of the tile that k-index 8 g + i of P.V means
+__device__ __forceinline__ int mf8_key(int g, int i) { return i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4); }
+
 // ============================================================================
 // Decoder KV element type.  f32 by default (the CPU reference's cache); the opt-in 16-bit
 // mode (VOX_DECODER_KV_FP16, voxtral.c:189-190, voxtral_decoder.c:180-243) stores IEEE half:

@@ -272,6 +272,18 @@ hipError_t launch_attn_mf8_fused(const AttnSlots& p, const AttnFuse& f, int nb, 
 hipError_t launch_attn_mf8_fused(const AttnSlotsRag& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
                                  int KVH, int splits, hipStream_t st);
 hipError_t launch_attn_mf8_codes(uint16_t* bits, hipStream_t st);  // bits[256]: every code through the kernel's convert
+// The M > 1 attention over the encoder's FP8 rings on the bf16 matrix pipe (k_attn_rows_mf8,
+// vox_hip_enc_attn_mf8.hip): the process-wide opt-in (VOX_HIP_ENC_ATTN_MF8=1 gives the
+// initial value) and the launcher attn_mf_launch takes with it on where attn_rows_mf8_ok (head_dim
+// 64, FP8 ring of at least a 32-key tile).  Arguments, grid and partials are k_attn_mf's (bat: the
+// EncRows form); the count is enqueued launches of either form.
+int enc_attn_mf8_mode();
+void enc_attn_mf8_set(int on);
+long long enc_attn_mf8_count();
+bool attn_rows_mf8_ok(int hd, int kvt, int cap);
+hipError_t launch_attn_rows_mf8(bool bat, dim3 grid, const float* Q, int ldq, const float* Kc, const float* Vc, int cap,
+                                float* O, int ldo, int M, int H, int KVH, int q_pos0, int k_first, int window, float scale,
+                                int ns, float* part, const EncRows& er, uint16_t* xs, hipStream_t st);
 constexpr int STEP_GRAPHS = 8;       // step graphs by attention split count 1, 2, 4, ..., 128
 hipError_t launch_attn_batch_dbg(const AttnPtrs& p, const AttnFuse& f, int nb, int cap, int window, float scale, int H,
                                  int KVH, int splits, hipStream_t st);

@@ -151,6 +151,7 @@ EXPORTS = [
     "vox_hip_batch_wpack", "vox_hip_skinny_wpack",
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_set_attn_mf8", "vox_hip_attn_mf8", "vox_hip_attn_mf8_stats", "vox_hip_attn_decode_kv8", "vox_hip_attn_mf8_codes",
+    "vox_hip_set_enc_attn_mf8", "vox_hip_enc_attn_mf8", "vox_hip_enc_attn_mf8_stats", "vox_hip_enc_attn_kv8",
     "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -226,6 +227,9 @@ def lib():
         "vox_hip_set_attn_mf8": (I, [I]), "vox_hip_attn_mf8": (I, []),
         "vox_hip_attn_mf8_stats": (I, [ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_attn_decode_kv8": (I, [fp, fp, P, P, I, I, P, I, I, I, I]), "vox_hip_attn_mf8_codes": (I, [P]),
+        "vox_hip_set_enc_attn_mf8": (I, [I]), "vox_hip_enc_attn_mf8": (I, []),
+        "vox_hip_enc_attn_mf8_stats": (I, [ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_enc_attn_kv8": (I, [fp, fp, P, P, I, I, I, I, I, F, I, I, I, I]),
         "vox_hip_model_gemmf_q8_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_gemmf_q8_rows": (I, [I, I, I, fp, P, fp, fp, I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -454,6 +458,42 @@ def attn_mf8_codes() -> np.ndarray:
     if lib().vox_hip_attn_mf8_codes(bits.ctypes.data) != 0:
         _err("attn_mf8_codes")
     return bits
+
+
+def set_enc_attn_mf8(on: bool):
+    """the encoder's attention over FP8 encoder rings on the bf16 matrix pipe, process-wide
+    (vox_hip_set_enc_attn_mf8; off by default, VOX_HIP_ENC_ATTN_MF8=1 gives the initial value;
+    refused inside a begun batched call)"""
+    if lib().vox_hip_set_enc_attn_mf8(int(bool(on))) != 0:
+        _err("set_enc_attn_mf8")
+
+
+def enc_attn_mf8() -> int:
+    return lib().vox_hip_enc_attn_mf8()
+
+
+def enc_attn_mf8_stats() -> int:
+    """vox_hip_enc_attn_mf8_stats: launches of k_attn_rows_mf8 enqueued, single and batched form"""
+    n = ctypes.c_longlong(0)
+    if lib().vox_hip_enc_attn_mf8_stats(ctypes.byref(n)) != 0:
+        _err("enc_attn_mf8_stats")
+    return n.value
+
+
+def enc_attn_kv8(Q, kring, vring, H: int, KVH: int, scale: float, window: int, q_pos0: int, use_splits: bool,
+                 mf8: bool) -> np.ndarray:
+    """vox_hip_enc_attn_kv8: the M > 1 causal / windowed attention over FP8 ring codes.  Q [M, H * 64]
+    f32 at positions q_pos0 + i, kring / vring [cap, KVH * 64] uint8 with position p at slot p % cap;
+    mf8 False the default kernel, True k_attn_rows_mf8 -> [M, H * 64]"""
+    Q = np.ascontiguousarray(Q, np.float32)
+    kc, vc = np.ascontiguousarray(kring, np.uint8), np.ascontiguousarray(vring, np.uint8)
+    M, cap = Q.shape[0], kc.shape[0]
+    assert Q.shape == (M, H * 64) and kc.shape == vc.shape == (cap, KVH * 64)
+    out = np.empty_like(Q)
+    if lib().vox_hip_enc_attn_kv8(fptr(out), fptr(Q), kc.ctypes.data, vc.ctypes.data, cap, M, H, KVH, 64, float(scale),
+                                  int(window), int(q_pos0), int(bool(use_splits)), int(bool(mf8))) != 0:
+        _err("enc_attn_kv8")
+    return out
 
 
 def gemmf_q8() -> int:
