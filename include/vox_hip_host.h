@@ -54,6 +54,10 @@ int vh_set_attn_mf8(int on);
  * (vox_hip_set_enc_attn_mf8, voxtral_hip.h: exact products, another f32 summation order; off by
  * default).  Returns 0; -1 inside a begun batched call. */
 int vh_set_enc_attn_mf8(int on);
+/* The encoder's attention over IEEE-half encoder rings (vh_set_enc_kv_dtype(ctx, 1)) on the f16 matrix
+ * pipe (vox_hip_set_enc_attn_mf16, voxtral_hip.h: ring elements as stored, queries and weights as three
+ * f16 planes; off by default).  Returns 0; -1 inside a begun batched call. */
+int vh_set_enc_attn_mf16(int on);
 const char *vh_last_error(void);
 
 /* vox_stream_init (voxtral.c:1242-1286) */

@@ -383,6 +383,32 @@ int vox_hip_enc_attn_mf8_stats(long long *launches);
 int vox_hip_enc_attn_kv8(float *out, const float *Q, const uint8_t *Kring, const uint8_t *Vring, int cap, int M, int H,
                          int KVH, int hd, float scale, int window, int q_pos0, int use_splits, int mf8);
 
+/* The M > 1 causal / windowed attention over IEEE-half encoder K/V rings on the f16 matrix pipe
+ * (k_attn_rows_mf16): process-wide, off by default, VOX_HIP_ENC_ATTN_MF16=1 gives the
+ * initial value.  With it on, every encoder attention launch over half rings (head_dim 64) -- the
+ * one-shot passes, the streaming chunks with or without key splits, the one-row chunks and the batched
+ * pass of encode_mel_batch and the scheduler -- takes the MFMA kernel: ring elements enter
+ * v_mfma_f32_16x16x32_f16 as stored, queries and softmax weights as three f16 planes of the
+ * row-scaled value (within 2^-39 of the row's largest magnitude), products are exact in the f32
+ * accumulator.  Subnormal half ring values are kept by the instruction (measured).  f32
+ * and FP8 rings and head_dim 128 launch what they launched.  No captured graph holds an encoder
+ * attention, so nothing is recaptured; inside a begun batched call (vox_hip_batch_begin_rows ..
+ * vox_hip_batch_finish) the setter is refused (-1).  Returns 0. */
+int vox_hip_set_enc_attn_mf16(int on);
+int vox_hip_enc_attn_mf16(void);
+/* *launches: launches of k_attn_rows_mf16 enqueued by this process, single-stream and batched form */
+int vox_hip_enc_attn_mf16_stats(long long *launches);
+/* Test entry: the M > 1 attention over caller-supplied half rings (host pointers): Q[M][H * hd] f32
+ * rows at positions q_pos0 + i, Kring / Vring[cap][KVH * hd] IEEE-half bits with position p at slot
+ * p % cap, out[M][H * hd]; hd = 64, cap >= 32.  Query i sees keys max(0, q_pos0 + i - window + 1) ..
+ * q_pos0 + i.  use_splits 0 passes no workspace (one key range), 1 lets the launcher split the key
+ * range and combine.  mf16 0: the default kernel; 1: k_attn_rows_mf16, whatever the switch says. */
+int vox_hip_enc_attn_kv16(float *out, const float *Q, const uint16_t *Kring, const uint16_t *Vring, int cap, int M, int H,
+                          int KVH, int hd, float scale, int window, int q_pos0, int use_splits, int mf16);
+/* Test entry: one wave of k_attn_rows_mf16's MFMA call on caller-supplied IEEE-half bits:
+ * out[i] = a_bits[i] * b_bits[i] as f32, each product alone on the accumulator's diagonal. */
+int vox_hip_enc_attn_mf16_probe(float *out, const uint16_t *a_bits, const uint16_t *b_bits, int n);
+
 /* Per-stream device state: encoder/decoder rolling KV, conv-stem tails, adapter buffer,
  * scratch and a HIP stream.  One model serves many streams. */
 vox_hip_stream_t *vox_hip_stream_create(vox_hip_model_t *m);

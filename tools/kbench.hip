@@ -1522,8 +1522,9 @@ int main(int argc, char** argv) {
     }
     if (getenv("VOX_KB_ONLY") && !strcmp(getenv("VOX_KB_ONLY"), "encattn")) {
         // the encoder's M > 1 attention (32 heads of 64, window 750, rings of 1838 slots) per ring type
-        // as an encoder pass sees it: 32 layers' rings, one launch per layer in turn; f32 rings, FP8
-        // rings through k_attn_mf<64, kv8_t> and through k_attn_rows_mf8.  The 1500-row
+        // as an encoder pass sees it: 32 layers' rings, one launch per layer in turn; f32 rings, half
+        // rings through k_attn_mf<64, half> and through k_attn_rows_mf16, FP8 rings
+        // through k_attn_mf<64, kv8_t> and through k_attn_rows_mf8.  The 1500-row
         // case spans more positions than the ring holds (the product's passes stop at 1024 rows): its
         // slots alias, which costs what distinct slots cost.
         const int EHn = 32, Ehd = 64, EQn = EHn * Ehd, NLe = 32, ecp = 1838, Mmax = 1500;
@@ -1532,20 +1533,21 @@ int main(int argc, char** argv) {
         const size_t wsn = (size_t)EHn * 25 * 16 * (Ehd + 2);
         float* ews = (float*)dmalloc(wsn * 4, 0);
         struct C { const char* n; int M, q0; bool split; };
-        for (int kvt : {0, 2}) {
-            const size_t esz = kvt == 2 ? 1 : 4, per = (size_t)ecp * EQn;
+        for (int kvt : {0, 1, 2}) {
+            const size_t esz = kvt == 2 ? 1 : kvt == 1 ? 2 : 4, per = (size_t)ecp * EQn;
             std::vector<float*> Ks(NLe), Vs(NLe);
             for (int l = 0; l < NLe; l++) {
                 Ks[l] = (float*)dmalloc(per * esz, 1);
                 Vs[l] = (float*)dmalloc(per * esz, 1);
             }
-            for (int mf8 = 0; mf8 <= (kvt == 2); mf8++) {
-                enc_attn_mf8_set(mf8);
+            for (int mf = 0; mf <= (kvt != 0); mf++) {  // mf: the ring type's MFMA kernel
+                enc_attn_mf8_set(mf && kvt == 2);
+                enc_attn_mf16_set(mf && kvt == 1);
                 for (C c : {C{"677 rows from 0", 677, 0, false}, C{"25 rows x 775 keys + combine", 25, 2000, true},
                             C{"1500 rows full window", 1500, 750, false}}) {
                     int l = 0;
                     char nm[96];
-                    snprintf(nm, sizeof nm, "enc attn %s %s", c.n, kvt == 0 ? "f32" : mf8 ? "fp8 mf8" : "fp8");
+                    snprintf(nm, sizeof nm, "enc attn %s %s", c.n, kvt == 0 ? "f32" : kvt == 1 ? (mf ? "half mf16" : "half") : mf ? "fp8 mf8" : "fp8");
                     const int keys = c.q0 + c.M - std::max(0, c.q0 - 749);
                     add(nm, timeit([&] {
                             CK(launch_attn_rows_mf(Ehd, eq, EQn, Ks[l % NLe], Vs[l % NLe], ecp, eo, EQn, c.M, EHn, EHn, c.q0, 0, 750,
@@ -1555,6 +1557,7 @@ int main(int argc, char** argv) {
                 }
             }
             enc_attn_mf8_set(0);
+            enc_attn_mf16_set(0);
             for (int l = 0; l < NLe; l++) {
                 CK(hipFree(Ks[l]));
                 CK(hipFree(Vs[l]));

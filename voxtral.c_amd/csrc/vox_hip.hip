@@ -3394,6 +3394,88 @@ extern "C" int vox_hip_enc_attn_kv8(float* out, const float* Q, const uint8_t* K
     return rc;
 }
 
+// The M > 1 attention over the encoder's IEEE-half rings on the f16 matrix pipe (k_attn_rows_mf16,
+// DESIGN.md 37): process-wide and off by default (VOX_HIP_ENC_ATTN_MF16=1 gives the initial value).  No
+// captured graph holds an encoder attention (the step graphs are the decoder's), so nothing is
+// recaptured; inside a begun batched call, where the scheduler's encoder passes run, the setter is refused.
+extern "C" int vox_hip_set_enc_attn_mf16(int on) {
+    if (g_begun_calls > 0) return set_err("set_enc_attn_mf16: a begun batched call was not finished");
+    enc_attn_mf16_set(on);
+    return 0;
+}
+extern "C" int vox_hip_enc_attn_mf16(void) { return enc_attn_mf16_mode(); }
+extern "C" int vox_hip_enc_attn_mf16_stats(long long* launches) {
+    if (!launches) return set_err("enc_attn_mf16_stats: null argument");
+    *launches = enc_attn_mf16_count();
+    return 0;
+}
+
+// The M > 1 attention over caller-supplied half rings (tests): Q [M][H * hd] f32 rows at positions
+// q_pos0 + i, rings [cap][KVH * hd] half bits holding position p at slot p % cap; out [M][H * hd].
+// use_splits 0 passes no workspace (one key range); mf16 picks the kernel of this call whatever
+// the process switch says (0: k_attn_mf<64, half>, 1: k_attn_rows_mf16).
+extern "C" int vox_hip_enc_attn_kv16(float* out, const float* Q, const uint16_t* Kring, const uint16_t* Vring, int cap,
+                                     int M, int H, int KVH, int hd, float scale, int window, int q_pos0, int use_splits,
+                                     int mf16) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (!out || !Q || !Kring || !Vring) return set_err("enc_attn_kv16: null argument");
+    if (hd != 64 || M < 1 || cap < 32 || KVH < 1 || H % KVH || window < 1 || q_pos0 < 0 || (mf16 != 0 && mf16 != 1))
+        return set_err("enc_attn_kv16: bad arguments");
+    if (g_begun_calls > 0) return set_err("enc_attn_kv16: a begun batched call was not finished");
+    const size_t ring = (size_t)cap * KVH * hd * 2, qn = (size_t)M * H * hd;
+    const size_t wsn = use_splits ? (size_t)H * M * 16 * (hd + 2) : 0;  // twin_attention's workspace
+    uint16_t *dk = nullptr, *dv = nullptr;
+    float *dq = nullptr, *dout = nullptr, *dws = nullptr;
+    const int was = enc_attn_mf16_mode();
+    int rc = -1;
+    do {
+        if (hipMalloc((void**)&dk, ring) != hipSuccess || hipMalloc((void**)&dv, ring) != hipSuccess ||
+            hipMalloc((void**)&dq, qn * 4) != hipSuccess || hipMalloc((void**)&dout, qn * 4) != hipSuccess ||
+            (wsn && hipMalloc((void**)&dws, wsn * 4) != hipSuccess)) {
+            set_err("enc_attn_kv16: out of device memory");
+            break;
+        }
+        enc_attn_mf16_set(mf16);
+        const bool ok = hipMemcpy(dk, Kring, ring, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dv, Vring, ring, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(dq, Q, qn * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemset(dout, 0, qn * 4) == hipSuccess &&
+                        launch_attn_rows_mf(hd, dq, H * hd, reinterpret_cast<const float*>(dk),
+                                            reinterpret_cast<const float*>(dv), cap, dout, H * hd, M, H, KVH, q_pos0, 0, window,
+                                            scale, nullptr, dws, wsn, nullptr, KV_F16) == hipSuccess &&
+                        hipDeviceSynchronize() == hipSuccess &&
+                        hipMemcpy(out, dout, qn * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        enc_attn_mf16_set(was);
+        if (!ok) {
+            set_err("enc_attn_kv16: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+        rc = 0;
+    } while (0);
+    for (void* d : {(void*)dk, (void*)dv, (void*)dq, (void*)dout, (void*)dws})
+        if (d) hipFree(d);
+    return rc;
+}
+
+// One wave of k_attn_rows_mf16's MFMA call on caller-supplied f16 bits (tests): out[i] = a[i] * b[i],
+// each product alone on the accumulator's diagonal.
+extern "C" int vox_hip_enc_attn_mf16_probe(float* out, const uint16_t* a_bits, const uint16_t* b_bits, int n) {
+    if (!g_inited && !vox_hip_init()) return -1;
+    if (!out || !a_bits || !b_bits || n < 1 || n > (1 << 20)) return set_err("enc_attn_mf16_probe: bad arguments");
+    uint16_t *da = nullptr, *db = nullptr;
+    float* dout = nullptr;
+    const bool ok = hipMalloc((void**)&da, (size_t)n * 2) == hipSuccess && hipMalloc((void**)&db, (size_t)n * 2) == hipSuccess &&
+                    hipMalloc((void**)&dout, (size_t)n * 4) == hipSuccess &&
+                    hipMemcpy(da, a_bits, (size_t)n * 2, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(db, b_bits, (size_t)n * 2, hipMemcpyHostToDevice) == hipSuccess &&
+                    launch_mf16_probe(dout, da, db, n, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) set_err("enc_attn_mf16_probe: %s", hipGetErrorString(hipGetLastError()));
+    for (void* d : {(void*)da, (void*)db, (void*)dout})
+        if (d) hipFree(d);
+    return ok ? 0 : -1;
+}
+
 extern "C" int vox_hip_stream_set_profiling(vox_hip_stream_t* s, int enable) {
     s->profiling = enable;
     s->prof_ms = 0;

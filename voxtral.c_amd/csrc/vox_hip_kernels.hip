@@ -3173,8 +3173,12 @@ static hipError_t attn_mf_launch(int hd, int kvt, dim3 grid, const float* Q, int
     uint16_t* kxs = ns == 1 && writes_planes && att_planes() ? xs : nullptr;
     // the encoder's FP8 rings with vox_hip_set_enc_attn_mf8: the bf16-MFMA kernel
     const bool mf8 = attn_rows_mf8_ok(hd, kvt, cap) && enc_attn_mf8_mode();
+    // the encoder's half rings with vox_hip_set_enc_attn_mf16: the f16-MFMA kernel
+    const bool mf16 = attn_rows_mf16_ok(hd, kvt, cap) && enc_attn_mf16_mode();
     const hipError_t e = mf8 ? launch_attn_rows_mf8(BAT, grid, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0, k_first, window,
                                                     scale, ns, ws, er, kxs, st)
+                       : mf16 ? launch_attn_rows_mf16(BAT, grid, Q, ldq, Kc, Vc, cap, O, ldo, M, H, KVH, q_pos0, k_first, window,
+                                                      scale, ns, ws, er, kxs, st)
                              : kv_ring(kvt, hd, [&](auto ring) {
         using R = decltype(ring);
         using KT = typename R::type;

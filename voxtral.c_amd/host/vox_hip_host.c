@@ -585,6 +585,7 @@ int vh_set_delay(vh_ctx_t *ctx, int delay_ms) {
 int vh_set_wpack_batch(int on) { return vox_hip_set_wpack_batch(on); }
 int vh_set_attn_mf8(int on) { return vox_hip_set_attn_mf8(on); }
 int vh_set_enc_attn_mf8(int on) { return vox_hip_set_enc_attn_mf8(on); }
+int vh_set_enc_attn_mf16(int on) { return vox_hip_set_enc_attn_mf16(on); }
 
 /* ------------------------------------------------------------------------
  * Streaming (voxtral.c:827-851, 1013-1145, 1288-1316, 1640-1667)

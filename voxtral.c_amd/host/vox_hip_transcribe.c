@@ -35,7 +35,10 @@
  * keys on the matrix pipe (vh_set_attn_mf8(1): exact products, another f32 summation order).
  * --enc-attn-mf8 (no reference counterpart) runs the encoder's attention over FP8 encoder rings
  * (--enc-kv8) on the bf16 matrix pipe (vh_set_enc_attn_mf8(1): exact products, another f32 summation
- * order; without --enc-kv8 it changes nothing).  The
+ * order; without --enc-kv8 it changes nothing).
+ * --enc-attn-mf16 (no reference counterpart) runs the encoder's attention over IEEE-half encoder
+ * rings (--enc-kv16) on the f16 matrix pipe (vh_set_enc_attn_mf16(1): ring elements as stored, queries
+ * and weights as three f16 planes; without --enc-kv16 it changes nothing).  The
  * reference's stderr lines ("Audio:", "Encoder:", "Decoder:") are kept so its
  * benchmark.py regexes parse this program's output too.
  */
@@ -63,7 +66,7 @@ static void drain(vh_stream_t *s, int *text_tokens, int alt) {
 int main(int argc, char **argv) {
     const char *model = NULL, *wav = NULL;
     float interval = -1.0f, alt_cutoff = -1.0f;
-    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, enc_kv8 = 0, q8_gemmf = 0, kv_grow = 0, wpack_batch = 0, attn_mf8 = 0, enc_attn_mf8 = 0;
+    int delay_ms = -1, continuous = 0, mx4 = 0, kv8 = 0, enc_kv16 = 0, enc_kv8 = 0, q8_gemmf = 0, kv_grow = 0, wpack_batch = 0, attn_mf8 = 0, enc_attn_mf8 = 0, enc_attn_mf16 = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-d") && i + 1 < argc) model = argv[++i];
         else if (!strcmp(argv[i], "-i") && i + 1 < argc) wav = argv[++i];
@@ -78,6 +81,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--q8-gemmf")) q8_gemmf = 1;
         else if (!strcmp(argv[i], "--attn-mf8")) attn_mf8 = 1;
         else if (!strcmp(argv[i], "--enc-attn-mf8")) enc_attn_mf8 = 1;
+        else if (!strcmp(argv[i], "--enc-attn-mf16")) enc_attn_mf16 = 1;
         else if (!strcmp(argv[i], "--kv-grow") && i + 1 < argc) kv_grow = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--wpack-batch")) wpack_batch = 1;
         else {
@@ -91,7 +95,7 @@ int main(int argc, char **argv) {
     }
     if (!model || !wav || kv_grow < 0 || (alt_cutoff != -1.0f && (alt_cutoff < 0 || alt_cutoff > 1))) {
         fprintf(stderr, "usage: %s -d consolidated.safetensors -i audio.wav [-I secs] [--delay ms] "
-                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8] [--q8-gemmf] [--kv-grow slots] [--wpack-batch] [--attn-mf8] [--enc-attn-mf8]\n",
+                        "[--alt 0..1] [--continuous] [--mx4] [--kv8] [--enc-kv16 | --enc-kv8] [--q8-gemmf] [--kv-grow slots] [--wpack-batch] [--attn-mf8] [--enc-attn-mf8] [--enc-attn-mf16]\n",
                 argv[0]);
         return 2;
     }
@@ -100,6 +104,7 @@ int main(int argc, char **argv) {
     if (wpack_batch && vh_set_wpack_batch(1)) return 1;
     if (attn_mf8 && vh_set_attn_mf8(1)) return 1;
     if (enc_attn_mf8 && vh_set_enc_attn_mf8(1)) return 1;
+    if (enc_attn_mf16 && vh_set_enc_attn_mf16(1)) return 1;
     vh_ctx_t *ctx = vh_load(model);
     if (!ctx) return 1;
     if (vox_hip_wpack_batch()) {

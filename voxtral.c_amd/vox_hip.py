@@ -152,6 +152,8 @@ EXPORTS = [
     "vox_hip_set_gemm_planes", "vox_hip_gemm_planes", "vox_hip_set_gemmf_wait",
     "vox_hip_set_attn_mf8", "vox_hip_attn_mf8", "vox_hip_attn_mf8_stats", "vox_hip_attn_decode_kv8", "vox_hip_attn_mf8_codes",
     "vox_hip_set_enc_attn_mf8", "vox_hip_enc_attn_mf8", "vox_hip_enc_attn_mf8_stats", "vox_hip_enc_attn_kv8",
+    "vox_hip_set_enc_attn_mf16", "vox_hip_enc_attn_mf16", "vox_hip_enc_attn_mf16_stats", "vox_hip_enc_attn_kv16",
+    "vox_hip_enc_attn_mf16_probe",
     "vox_hip_set_gemmf_q8", "vox_hip_gemmf_q8", "vox_hip_model_gemmf_q8_stats", "vox_hip_gemmf_q8_rows",
     "vox_hip_stream_create", "vox_hip_stream_free",
     "vox_hip_stream_reset", "vox_hip_stream_reset_decoder", "vox_hip_stream_encode_mel",
@@ -230,6 +232,10 @@ def lib():
         "vox_hip_set_enc_attn_mf8": (I, [I]), "vox_hip_enc_attn_mf8": (I, []),
         "vox_hip_enc_attn_mf8_stats": (I, [ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_enc_attn_kv8": (I, [fp, fp, P, P, I, I, I, I, I, F, I, I, I, I]),
+        "vox_hip_set_enc_attn_mf16": (I, [I]), "vox_hip_enc_attn_mf16": (I, []),
+        "vox_hip_enc_attn_mf16_stats": (I, [ctypes.POINTER(ctypes.c_longlong)]),
+        "vox_hip_enc_attn_kv16": (I, [fp, fp, P, P, I, I, I, I, I, F, I, I, I, I]),
+        "vox_hip_enc_attn_mf16_probe": (I, [fp, P, P, I]),
         "vox_hip_model_gemmf_q8_stats": (I, [P, ctypes.POINTER(ctypes.c_longlong)]),
         "vox_hip_gemmf_q8_rows": (I, [I, I, I, fp, P, fp, fp, I]),
         "vox_hip_stream_create": (P, [P]), "vox_hip_stream_free": (None, [P]),
@@ -493,6 +499,53 @@ def enc_attn_kv8(Q, kring, vring, H: int, KVH: int, scale: float, window: int, q
     if lib().vox_hip_enc_attn_kv8(fptr(out), fptr(Q), kc.ctypes.data, vc.ctypes.data, cap, M, H, KVH, 64, float(scale),
                                   int(window), int(q_pos0), int(bool(use_splits)), int(bool(mf8))) != 0:
         _err("enc_attn_kv8")
+    return out
+
+
+def set_enc_attn_mf16(on: bool):
+    """the encoder's attention over IEEE-half encoder rings on the f16 matrix pipe, process-wide
+    (vox_hip_set_enc_attn_mf16; off by default, VOX_HIP_ENC_ATTN_MF16=1 gives the initial value;
+    refused inside a begun batched call)"""
+    if lib().vox_hip_set_enc_attn_mf16(int(bool(on))) != 0:
+        _err("set_enc_attn_mf16")
+
+
+def enc_attn_mf16() -> int:
+    return lib().vox_hip_enc_attn_mf16()
+
+
+def enc_attn_mf16_stats() -> int:
+    """vox_hip_enc_attn_mf16_stats: launches of k_attn_rows_mf16 enqueued, single and batched form"""
+    n = ctypes.c_longlong(0)
+    if lib().vox_hip_enc_attn_mf16_stats(ctypes.byref(n)) != 0:
+        _err("enc_attn_mf16_stats")
+    return n.value
+
+
+def enc_attn_kv16(Q, kring, vring, H: int, KVH: int, scale: float, window: int, q_pos0: int, use_splits: bool,
+                  mf16: bool) -> np.ndarray:
+    """vox_hip_enc_attn_kv16: the M > 1 causal / windowed attention over half rings.  Q [M, H * 64]
+    f32 at positions q_pos0 + i, kring / vring [cap, KVH * 64] uint16 (IEEE-half bits) with position p
+    at slot p % cap; mf16 False the default kernel, True k_attn_rows_mf16 -> [M, H * 64]"""
+    Q = np.ascontiguousarray(Q, np.float32)
+    kc, vc = np.ascontiguousarray(kring, np.uint16), np.ascontiguousarray(vring, np.uint16)
+    M, cap = Q.shape[0], kc.shape[0]
+    assert Q.shape == (M, H * 64) and kc.shape == vc.shape == (cap, KVH * 64)
+    out = np.empty_like(Q)
+    if lib().vox_hip_enc_attn_kv16(fptr(out), fptr(Q), kc.ctypes.data, vc.ctypes.data, cap, M, H, KVH, 64, float(scale),
+                                   int(window), int(q_pos0), int(bool(use_splits)), int(bool(mf16))) != 0:
+        _err("enc_attn_kv16")
+    return out
+
+
+def enc_attn_mf16_probe(a_bits, b_bits) -> np.ndarray:
+    """vox_hip_enc_attn_mf16_probe: a[i] * b[i] of IEEE-half bits through one wave of
+    k_attn_rows_mf16's MFMA call -> f32 [n]"""
+    a, b = np.ascontiguousarray(a_bits, np.uint16), np.ascontiguousarray(b_bits, np.uint16)
+    assert a.ndim == 1 and a.shape == b.shape and a.size > 0
+    out = np.empty(a.size, np.float32)
+    if lib().vox_hip_enc_attn_mf16_probe(fptr(out), a.ctypes.data, b.ctypes.data, a.size) != 0:
+        _err("enc_attn_mf16_probe")
     return out
 
 
